@@ -86,6 +86,11 @@ def parse():
     ap.add_argument("--debug-single-device", action="store_true",
                     help="functional check of the N > 1 flow on ONE GPU: every rank uses cuda:0 and gloo (host-staged) instead "
                          "of RCCL; the numbers it prints are meaningless")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (blend output, decoded image; the encode's latent "
+                         "moments with --encode) as DIR/<name>.npy, float32, at most 48 MiB in all: an array larger than its cap is "
+                         "replaced by a fixed, seeded sample of its elements (DIR/manifest.json says which).  Inputs are seeded: the "
+                         "same arguments give the same inputs on every run")
     return ap.parse_args()
 
 
@@ -239,6 +244,31 @@ def _quiet(fn):
         return fn()
     finally:
         builtins.print = keep
+
+
+DUMP_SEED = 0
+DUMP_FULL_ELEMS = 8 << 20       # the whole blend output of the default 1024^2 latent (N=2, C=4), or the encoder moments: 32 MiB
+DUMP_IMAGE_ELEMS = 4 << 20      # a 16 MiB sample of the 8K image (805 MB of float32 in full)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: name -> (tensor, max elements).  A tensor above its cap is written as the values at a fixed set of flat indices
+    (seeded by DUMP_SEED and the tensor's size only, so two builds sample the same positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = {}
+    for name, (t, cap) in arrays.items():
+        flat = t.detach().reshape(-1)
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype), "sampled": flat.numel() > cap}
+        if entry["sampled"]:
+            idx = torch.randint(flat.numel(), (cap,), generator=torch.Generator().manual_seed(DUMP_SEED)).unique()   # sorted
+            flat = flat[idx.to(flat.device)]
+            entry.update(sample_seed=DUMP_SEED, sample_size=int(idx.numel()))
+        a = flat.cpu().numpy() if entry["sampled"] else t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if t.dtype == torch.float64 else np.float32))
+        manifest[name] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def err_metrics(out: torch.Tensor, ref: torch.Tensor):
@@ -428,6 +458,8 @@ def run_encode(args, E, pl, ld, dev):
         y = quiet(lambda: hook(x))
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latent": (y, DUMP_FULL_ELEMS)})
     lat = (side // 8) * (side // 8)
     # per-kernel roofline of one more encode (HIP events around every conv / attention launch, same stream)
     prof = Profile()
@@ -564,10 +596,14 @@ def run_single_process(args):
         for d in sorted(set(devs)):
             torch.cuda.synchronize(d)
 
+    last = {}
+
     def step():
+        last.clear()            # the previous step's outputs are not kept alive through this one
+        outs = None
         for _ in range(args.evals):
-            blend_eval()
-        return hook(z) if hook is not None else None
+            outs = blend_eval()
+        last.update(outs=outs, image=hook(z) if hook is not None else None)
 
     def timed(fn, k):
         sync_all()
@@ -580,6 +616,18 @@ def run_single_process(args):
     for _ in range(args.warmup):
         _quiet(step)
     elapsed = timed(lambda: _quiet(step), args.steps)
+    if args.dump_outputs and last:
+        dump = {}
+        if last["outs"] is not None:      # every band's owned rows, assembled like the one-device blend output
+            canvas = torch.zeros(N, C, L, L)
+            for i in order:
+                b = sb.bands[i]
+                canvas[:, :, b.own_lo:b.own_hi] = last["outs"][i][:, :, b.own_lo:b.own_hi].cpu()
+            dump["blend_out"] = (canvas, DUMP_FULL_ELEMS)
+        if last["image"] is not None:
+            dump["image"] = (last["image"], DUMP_IMAGE_ELEMS)
+        dump_outputs(args.dump_outputs, dump)
+    last.clear()
     t_blend = timed(blend_eval, args.evals)
     t_vae = timed(lambda: _quiet(lambda: hook(z)), 1) if hook is not None else None
     check = None
@@ -775,10 +823,22 @@ def main():
             step()
         sync_all()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        image = None
+        for k in range(args.steps):
+            image = step()
+            if k + 1 < args.steps:
+                image = None    # the previous step's image is not kept alive through the next one
         sync_all()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            # what the caller of the timed path holds after its last step (rank 0 of N > 1: its own band of the blend output and
+            # the assembled image); written before the untimed passes below reuse the buffers
+            dump = {"blend_out" if world == 1 else f"blend_out_rows_{band.row_lo}_{band.row_hi}":
+                    (blend_out if world == 1 else blend_out[:, :, band.row_lo:band.row_hi], DUMP_FULL_ELEMS)}
+            if image is not None:
+                dump["image"] = (image, DUMP_IMAGE_ELEMS)
+            dump_outputs(args.dump_outputs, dump)
+        image = None
         # per-stage split, untimed extras (same work, separate clocks)
         sync_all()
         tb = time.perf_counter()

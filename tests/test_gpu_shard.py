@@ -269,12 +269,13 @@ def test_process_context_bringup_one_rank_uses_rccl(plugin, cuda):
     assert res[0] is True and res[1] is True and res[2] is True, res
 
 
-@pytest.mark.parametrize("world", [2, 3, 8])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_bench_flow_n_ranks_on_one_device_matches_the_single_rank_image(cuda, world):
     """The complete N-rank bench flow -- tile-row bands + halo exchange of the blend, sequence-parallel estimator, VAE tiles dealt to the
     ranks, decoded rectangles gathered to rank 0 inside the step -- as `world` processes sharing cuda:0 over gloo (host-staged transport:
-    two RCCL ranks cannot sit on one device), on a 2048 x 2048 image at decoder tile 64 (16 tiles; world = 8: the rank count the
-    driver's scaling run uses -- three tile rows of the blend over eight bands, five of them empty; two VAE tiles per rank).  bench.py's own `debug_check` compares
+    two RCCL ranks cannot sit on one device), on a 2048 x 2048 image at decoder tile 64 (16 tiles; world = 4: more ranks than the
+    three tile rows of the blend, so one band is empty; four VAE tiles per rank).  At most 4 ranks: with this process they are the
+    processes that have the shared GPU open at once, and a GPU machine allows no more than 6.  bench.py's own `debug_check` compares
     rank 0's ASSEMBLED image with the plain single-rank decode of the same latent: the sequence-parallel estimator sums its statistics
     in another order, so the bound is 1e-4 of the image range (observed ~2e-5), not bit equality.  (Until round 4 this flow was only ever
     run by hand: profiles/r3b.)"""

@@ -71,17 +71,17 @@ def test_best_tile_size_matches_upstream(built_lib):
     from oracle import vae_oracle as vo
     pl = sh.load_plugin()
     hook = pl.tilevae.VAEHook(None, 256, is_decoder=True, fast_decoder=True, fast_encoder=True, color_fix=False)
-    ref_hook = None
-    if sh.reference_available():
-        ref_hook = sh.load_reference().tilevae.VAEHook(None, 256, is_decoder=True, fast_decoder=True, fast_encoder=True, color_fix=False)
-    for upper in (48, 64, 96, 250, 256, 512, 3072):
-        for lower in list(range(1, 70)) + [upper - 33, upper - 31, upper - 1, upper, upper + 5]:
-            if lower < 1:
-                continue
-            got = hook.get_best_tile_size(lower, upper)
-            assert got == vo.best_tile_size(lower, upper), (lower, upper)
-            if ref_hook is not None:
-                assert got == ref_hook.get_best_tile_size(lower, upper), (lower, upper)
+    from upstream_pin import upstream
+    pairs = [(lower, upper) for upper in (48, 64, 96, 250, 256, 512, 3072)
+             for lower in list(range(1, 70)) + [upper - 33, upper - 31, upper - 1, upper, upper + 5] if lower >= 1]
+    got = [hook.get_best_tile_size(lower, upper) for lower, upper in pairs]
+    for (lower, upper), g in zip(pairs, got):
+        assert g == vo.best_tile_size(lower, upper), (lower, upper)
+
+    def upstream_sizes(ref):
+        ref_hook = ref.tilevae.VAEHook(None, 256, is_decoder=True, fast_decoder=True, fast_encoder=True, color_fix=False)
+        return [ref_hook.get_best_tile_size(lower, upper) for lower, upper in pairs]
+    assert upstream().equal("best_tile_size", upstream_sizes, got)
 
 
 def test_dma_protocol_in_the_device_assembly():

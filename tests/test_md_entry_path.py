@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import entry_driver as ed
-from hostsim import stub_host as sh
+from upstream_pin import upstream
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "entry.npz")
 IDS = [c["name"] for c in ed.ENTRY_CASES]
@@ -31,14 +31,13 @@ def test_oracle_matches_upstream_goldens(case, golden_entry):
     assert [list(c[1:]) for c in calls] == golden_entry[case["name"] + "/calls"].tolist()
 
 
-@pytest.mark.skipif(not sh.reference_available(), reason="/root/reference not mounted")
 @pytest.mark.parametrize("case", ed.ENTRY_CASES, ids=IDS)
 def test_oracle_matches_upstream_entry_path(case):
-    ref = sh.load_reference()
-    want, calls_ref = ed.drive(ref, case, "cpu", ed.ref_regions(ref))
+    """Outputs and model calls of the oracle against the upstream delegate (stored in tests/golden/upstream.npz where the upstream
+    checkout is not importable: tests/upstream_pin.py)."""
     got, calls = ed.oracle_run(case)
-    assert calls == calls_ref, f"model calls: oracle {calls} vs upstream {calls_ref}"
-    assert torch.equal(got, want)
+    assert upstream().equal(f"entry_path/{case['name']}", lambda ref: ed.drive(ref, case, "cpu", ed.ref_regions(ref)), (got, calls)), \
+        f"oracle's model calls: {calls}"
 
 
 def test_stand_in_model_sees_every_input():

@@ -53,9 +53,14 @@ const char* mdtile_last_error(void);
 /* Arithmetic of the matrix-core kernels (convs, attention).  Default MDTILE_PRECISION_BF16X3: every fp32 factor is split into two
  * bf16 halves (16 significand bits), three bf16 MFMAs per product, fp32 accumulation (~1e-5 relative to fp32 end to end; the stated
  * tolerance of the path is 1e-3).  MDTILE_PRECISION_F32: exact-fp32 MFMA kernels everywhere (bit-comparable to an fp32 fmaf chain),
- * ~4x slower.  Process-wide; env MDTILE_CONV_MODE=f32 / MDTILE_ATTN_MODE=f32 preset it. */
+ * ~4x slower.  MDTILE_PRECISION_BF16: one bf16 MFMA per product, bf16_rn(a) x bf16_rn(b) (the hi halves the splitters and weight packers
+ * already produce), fp32 accumulation; everything outside the matrix-core products stays fp32 (residual stream, GroupNorm statistics,
+ * softmax, conv_in).  Error class of bf16 operands: ~2^-9 relative per product, ~1e-3 of the output range end to end -- the arithmetic of a
+ * half-precision VAE (dtype_vae = bfloat16), at up to a third of the MFMAs.  Process-wide; env MDTILE_CONV_MODE=f32 / MDTILE_ATTN_MODE=f32
+ * preset it (and win over MDTILE_PRECISION_BF16 for the kernels they cover). */
 #define MDTILE_PRECISION_BF16X3 0
 #define MDTILE_PRECISION_F32 1
+#define MDTILE_PRECISION_BF16 2
 int mdtile_set_precision(int mode);
 int mdtile_get_precision(void);
 

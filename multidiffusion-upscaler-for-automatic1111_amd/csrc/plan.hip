@@ -18,7 +18,9 @@ void set_error(const char* fmt, ...) {
 
 extern "C" int mdtile_version(void) { return MDTILE_VERSION; }
 
-// ---- arithmetic of the matrix-core kernels: split-bf16 ("bf16x3") by default, exact fp32 MFMA on request ----
+// ---- arithmetic of the matrix-core kernels: split-bf16 ("bf16x3") by default, exact fp32 MFMA or single bf16 on request ----
+// g_precision bits: 1 = convs on exact fp32, 2 = attention on exact fp32 (MDTILE_CONV_MODE / MDTILE_ATTN_MODE presets, either or both),
+// 4 = single-term bf16 MFMAs (MDTILE_PRECISION_BF16).  A strict bit wins over bit 4 for the kernels it covers.
 namespace mdt {
 static int g_precision = [] {
     const char* c = getenv("MDTILE_CONV_MODE");
@@ -27,16 +29,19 @@ static int g_precision = [] {
 }();
 bool conv_strict_f32() { return (g_precision & 1) != 0; }
 bool attn_strict_f32() { return (g_precision & 2) != 0; }
+bool mfma_single_term() { return (g_precision & 4) != 0; }
 }  // namespace mdt
 extern "C" int mdtile_set_precision(int mode) {
-    if (mode != MDTILE_PRECISION_BF16X3 && mode != MDTILE_PRECISION_F32) {
+    if (mode != MDTILE_PRECISION_BF16X3 && mode != MDTILE_PRECISION_F32 && mode != MDTILE_PRECISION_BF16) {
         mdt::set_error("mdtile_set_precision: unknown mode %d", mode);
         return MDTILE_E_ARG;
     }
-    mdt::g_precision = mode == MDTILE_PRECISION_F32 ? 3 : 0;
+    mdt::g_precision = mode == MDTILE_PRECISION_F32 ? 3 : mode == MDTILE_PRECISION_BF16 ? 4 : 0;
     return MDTILE_OK;
 }
-extern "C" int mdtile_get_precision(void) { return mdt::g_precision == 3 ? MDTILE_PRECISION_F32 : MDTILE_PRECISION_BF16X3; }
+extern "C" int mdtile_get_precision(void) {
+    return mdt::g_precision == 3 ? MDTILE_PRECISION_F32 : (mdt::g_precision & 4) ? MDTILE_PRECISION_BF16 : MDTILE_PRECISION_BF16X3;
+}
 extern "C" const char* mdtile_last_error(void) { return mdt::g_err; }
 
 // 1-D origins: count = ceil((extent-ov)/(tile-ov)); step is a double; origin = min(trunc(i*step), extent-tile).

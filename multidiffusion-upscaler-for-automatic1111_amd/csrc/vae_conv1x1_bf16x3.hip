@@ -54,162 +54,16 @@ __device__ __forceinline__ void split8c(const float (&v)[8], u32x4& hi, u32x4& l
 // PXT = pixels per block.  128-cout blocks take 128 px: 64 KB of LDS and ~100 registers -> TWO blocks per CU, so that the store-bound
 // epilogue of one block (128 couts x 128 px x 4 B through 4-byte-per-lane stores) runs under the K loop of the other; with one
 // resident block per CU the epilogue was fully exposed (256 -> 128 at 2224^2: ~30 us per block of which ~half epilogue).
-template <int MT, int PXT>
-__global__ __launch_bounds__(512, PXT == 128 ? 4 : 2) void k_conv1x1_bf16x3(const Conv1Params P) {
-    constexpr int BM = MT * 32;
-    constexpr int IN_REC1 = 2 * 2 * PXT;             // records per hl per stage: [ks][kg][px]
-    constexpr int NG = PXT / 128;                    // 8-channel groups a thread stages per phase (512 threads x NG = 4 groups x PXT px)
-    constexpr int WAVES_M = MT / 2, WAVES_C = 8 / WAVES_M, NCOL = (PXT / 32) / WAVES_C;   // column tiles (32 px) per wave
-    static_assert(NCOL >= 1 && NG >= 1, "block shape");
-    constexpr int W_REC = 2 * 2 * MT * 64;           // [hl][ks][mt][lane]
-    constexpr int NWREG = W_REC / 512;               // 4 (MT = 8), 2 (MT = 4) or 1 (MT = 2)
-    constexpr int IN_STAGE = 2 * IN_REC1;
-    __shared__ u32x4 smem[2 * IN_STAGE + 2 * W_REC];
-    u32x4* const in_l = smem;
-    u32x4* const w_l = smem + 2 * IN_STAGE;
-
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int ptile = (slot / P.NCB) * 8 + xcd, cb = slot % P.NCB;
-    if (ptile >= P.ptiles) return;
-    const int b = blockIdx.y;
-    const size_t p0 = (size_t)ptile * PXT;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kg = lane >> 5;
-    const int wm = wave % WAVES_M, wc = wave / WAVES_M;
-    const float* xb = P.x + (size_t)b * P.Cin * P.HW;
-
-    // staging map: thread -> pixel (tid % PXT) and NG consecutive 8-channel groups gi = (tid / PXT) * NG + g of the phase's four
-    // (gi = 2 * K-step + kg: channels 32 ph + 8 gi + j, LDS record gi * PXT + px)
-    const int spx = tid & (PXT - 1), sgb = (tid / PXT) * NG;
-    const bool pin = p0 + spx < P.HW;
-    const size_t soff = pin ? p0 + spx : 0;
-    float rin[2][NG][8];         // [register set][8-channel group][channel]
-    u32x4 rwt[2][NWREG];
-
-    auto load_input = [&](int set, int ph) {       // phase ph: channels 32 ph .. 32 ph + 31
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float* src = xb + (size_t)(ph * 32 + (sgb + g) * 8) * P.HW + soff;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) rin[set][g][j] = src[(size_t)j * P.HW];
-        }
-    };
-    auto store_input = [&](int set, int stage) {
-        u32x4* dst = in_l + stage * IN_STAGE;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = pin ? rin[set][g][j] : 0.0f;
-            u32x4 hi, lo;
-            split8c(v, hi, lo);
-            const int rec = (sgb + g) * PXT + spx;
-            dst[rec] = hi;
-            dst[IN_REC1 + rec] = lo;
-        }
-    };
-    const u32x4* wsrc = P.w + (size_t)cb * P.NP * W_REC;
-    auto load_weights = [&](int set, int ph) {
-        const u32x4* src = wsrc + (size_t)ph * W_REC;
-#pragma unroll
-        for (int i = 0; i < NWREG; ++i) rwt[set][i] = src[tid + 512 * i];
-    };
-    auto store_weights = [&](int set, int stage) {
-        u32x4* dst = w_l + stage * W_REC;
-#pragma unroll
-        for (int i = 0; i < NWREG; ++i) dst[tid + 512 * i] = rwt[set][i];
-    };
-
-    f32x16 acc[2][NCOL];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < NCOL; ++n)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][n][q] = 0.0f;
-
-    load_input(0, 0);
-    load_weights(0, 0);
-    if (P.NP > 1) {
-        load_input(1, 1);
-        load_weights(1, 1);
-    }
-    store_input(0, 0);
-    store_weights(0, 0);
-    __syncthreads();
-
-    // phase ph sits in LDS stage ph & 1 and came through register set ph & 1; while it computes, phase ph + 2 is requested into the
-    // same register set (free since its contents went to LDS) and phase ph + 1 -- requested a whole phase ago -- is written to LDS
-    // behind the MFMAs.  Two phases per trip keep the register-set index a compile-time constant.
-    auto phase = [&](int ph, auto set_tag) {
-        constexpr int set = decltype(set_tag)::value;
-        if (ph + 2 < P.NP) {
-            load_input(set, ph + 2);
-            load_weights(set, ph + 2);
-        }
-        const u32x4* wst = w_l + set * W_REC;
-        const u32x4* ist = in_l + set * IN_STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 a[2][2];   // [m][hl]
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int hl = 0; hl < 2; ++hl)
-                    a[m][hl] = __builtin_bit_cast(bf16x8, wst[((hl * 2 + ks) * MT + wm * 2 + m) * 64 + lane]);
-#pragma unroll
-            for (int n = 0; n < NCOL; ++n) {
-                const int rec = (ks * 2 + kg) * PXT + (wc * NCOL + n) * 32 + l31;
-                const bf16x8 bh = __builtin_bit_cast(bf16x8, ist[rec]), bl = __builtin_bit_cast(bf16x8, ist[IN_REC1 + rec]);
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], bh, acc[m][n], 0, 0, 0);   // w_lo * x_hi
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bl, acc[m][n], 0, 0, 0);   // w_hi * x_lo
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bh, acc[m][n], 0, 0, 0);   // w_hi * x_hi
-                }
-            }
-        }
-        if (ph + 1 < P.NP) {
-            store_weights(set ^ 1, set ^ 1);
-            store_input(set ^ 1, set ^ 1);
-        }
-        __syncthreads();
-    };
-    for (int ph = 0; ph < P.NP; ph += 2) {
-        phase(ph, std::integral_constant<int, 0>{});
-        if (ph + 1 < P.NP) phase(ph + 1, std::integral_constant<int, 1>{});
-    }
-
-    // epilogue: + bias (+ residual).  C/D layout of a 32x32 MFMA: col = lane & 31, row = (q&3) + 8*(q>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int cbase = cb * BM + (wm * 2 + m) * 32 + 4 * kg;
-        float bq[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int co = cbase + (q & 3) + 8 * (q >> 2);
-            bq[q] = P.bias ? P.bias[co < P.Cout ? co : P.Cout - 1] : 0.0f;
-        }
-#pragma unroll
-        for (int n = 0; n < NCOL; ++n) {
-            const size_t p = p0 + (wc * NCOL + n) * 32 + l31;
-            if (p < P.HW) {
-                const size_t o0 = ((size_t)b * P.Cout) * P.HW + p;
-                float rq[16];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int co = cbase + (q & 3) + 8 * (q >> 2);
-                    rq[q] = P.res ? P.res[o0 + (size_t)(co < P.Cout ? co : P.Cout - 1) * P.HW] : 0.0f;
-                }
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int co = cbase + (q & 3) + 8 * (q >> 2);
-                    if (co < P.Cout) P.y[o0 + (size_t)co * P.HW] = acc[m][n][q] + bq[q] + rq[q];
-                }
-            }
-        }
-    }
-}
+#define MDT_C1_TERMS 3
+#define MDT_C1_KERNEL k_conv1x1_bf16x3
+#include "vae_conv1x1_body.h"
+#undef MDT_C1_KERNEL
+#undef MDT_C1_TERMS
+#define MDT_C1_TERMS 1
+#define MDT_C1_KERNEL k_conv1x1_bf16x1
+#include "vae_conv1x1_body.h"
+#undef MDT_C1_KERNEL
+#undef MDT_C1_TERMS
 
 // =====================================================================================================================
 // Streaming form for the wide images (round 3): the convs above are HBM-bound there (7.6 GB against 0.32 TFLOP for 256 -> 128 at 2224^2)
@@ -236,144 +90,16 @@ constexpr int S_NST = 3;
 
 // WM = waves along the couts (64 each): WM = 2 -> block of 128 couts x 512 px, WM = 4 -> 256 couts x 256 px (a conv with cout % 256 == 0
 // reads its input once).  Every wave owns 64 couts x 128 px = 2 x 4 accumulator tiles in both forms.
-template <int WM>
-__global__ __launch_bounds__(512, 2) void k_conv1x1_stream(const Conv1Params P) {
-    constexpr int MT = 2 * WM, WC = 8 / WM, NCOL = 4, SPX = 128 * WC;     // m-tiles, waves along the pixels, column tiles per wave, px per block
-    constexpr int S_IN_F = 16 * SPX;                  // floats per input stage ([16 ch][SPX])
-    constexpr int S_W_REC = 2 * MT * 64;              // weight records per K-step: [hl][mt][lane]
-    constexpr int IN_PW = (16 * SPX / 256) / 8;       // input DMA pieces (1 KB) per wave and phase: 4 / 2
-    constexpr int W_PW = (S_W_REC / 64) / 8;          // weight pieces per wave and phase: 1 / 2
-    static_assert(IN_PW + W_PW == (WM == 2 ? 5 : 4), "the counted vmcnt below");
-    // ring of raw fp32 input stages, then the weight ring; the epilogue's 8 wave-private transpose buffers (8 KB each) overlay the start
-    __shared__ __attribute__((aligned(16))) float smem[S_NST * S_IN_F + S_NST * S_W_REC * 4];
-    float* const in_l = smem;
-    u32x4* const w_l = reinterpret_cast<u32x4*>(smem + S_NST * S_IN_F);
-    static_assert(sizeof(smem) >= 8 * 8192, "transpose buffers");
-
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    const int ptile = (slot / P.NCB) * 8 + xcd, cb = slot % P.NCB;
-    if (ptile >= P.ptiles) return;
-    const int b = blockIdx.y;
-    const size_t p0 = (size_t)ptile * SPX;
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, kg = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave % WM, wc = wave / WM;
-    const char* xb = reinterpret_cast<const char*>(P.x + (size_t)b * P.Cin * P.HW);
-    const int NP16 = P.NP * 2;                    // 16-channel K-steps
-
-    // DMA map of a stage: piece d = wave + 8 i -> channel d / (SPX / 256), 256-px part d % (SPX / 256); lanes past the end of the image
-    // re-read the row's last quad (never stored)
-    constexpr int PARTS = SPX / 256;
-    unsigned voff[IN_PW];
-#pragma unroll
-    for (int i = 0; i < IN_PW; ++i) {
-        const int d = wave + 8 * i;
-        size_t px = p0 + (size_t)(d % PARTS) * 256 + 4 * lane;
-        if (px > P.HW - 4) px = P.HW - 4;
-        voff[i] = (unsigned)(px * 4);
-    }
-    const u32x4* wsrc = P.w + (size_t)cb * P.NP * (2 * 2 * MT * 64);
-    auto issue = [&](int ph, int stage) {
-#pragma unroll
-        for (int i = 0; i < IN_PW; ++i) {
-            const int d = wave + 8 * i, c = d / PARTS;
-            dma16s(xb + (size_t)(ph * 16 + c) * P.HW * 4, voff[i], in_l + stage * S_IN_F + c * SPX + (d % PARTS) * 256);
-        }
-        // weights of K-step ph: packed as [phase32][hl][ks][mt][lane]; piece e = wave + 8 i -> hl = e / MT, m-tile e % MT
-#pragma unroll
-        for (int i = 0; i < W_PW; ++i) {
-            const int e = wave + 8 * i, hl = e / MT, mt = e % MT;
-            const u32x4* src = wsrc + ((size_t)((ph >> 1) * 2 + hl) * 2 + (ph & 1)) * (MT * 64) + mt * 64;
-            dma16s(src, lane * 16, w_l + stage * S_W_REC + hl * (MT * 64) + mt * 64);
-        }
-    };
-
-    f32x16 acc[2][NCOL];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < NCOL; ++n)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][n][q] = 0.0f;
-
-    issue(0, 0);
-    if (NP16 > 1) issue(1, 1);
-    for (int ph = 0; ph < NP16; ++ph) {
-        const int stage = ph % S_NST;
-        // this wave's pieces in flight, oldest first: phase ph (IN_PW + W_PW), phase ph + 1 (IN_PW + W_PW)
-        if (ph + 1 < NP16) {
-            if (WM == 2) __builtin_amdgcn_s_waitcnt(0x0F75);       // vmcnt(5)
-            else __builtin_amdgcn_s_waitcnt(0x0F74);               // vmcnt(4)
-        } else {
-            __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
-        }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (ph + 2 < NP16) issue(ph + 2, (ph + 2) % S_NST);        // the stage phase ph - 1 sat in: every wave is past its reads
-        const float* ist = in_l + stage * S_IN_F + (8 * kg) * SPX + wc * (NCOL * 32) + l31;
-        const u32x4* wst = w_l + stage * S_W_REC + (wm * 2) * 64 + lane;
-        bf16x8 a[2][2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int hl = 0; hl < 2; ++hl) a[m][hl] = __builtin_bit_cast(bf16x8, wst[hl * (MT * 64) + m * 64]);
-#pragma unroll
-        for (int n = 0; n < NCOL; ++n) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = ist[j * SPX + n * 32];
-            u32x4 hi, lo;
-            split8c(v, hi, lo);
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, hi), bl = __builtin_bit_cast(bf16x8, lo);
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], bh, acc[m][n], 0, 0, 0);   // w_lo * x_hi
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bl, acc[m][n], 0, 0, 0);   // w_hi * x_lo
-                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bh, acc[m][n], 0, 0, 0);   // w_hi * x_hi
-            }
-        }
-    }
-    __syncthreads();          // every wave is done with the rings: their start becomes 8 wave-private transpose buffers of 8 KB
-
-    // epilogue: per (m-tile, cout half) pass the wave writes its 16 couts x 128 px to LDS ([16][128] fp32, one ds_write_b32 per value:
-    // lanes = consecutive pixels) and reads them back as float4 along the pixels: 512-byte runs per cout row for the residual loads
-    // and the stores.  C/D layout of a 32x32 MFMA: col = lane & 31, row = (q&3) + 8*(q>>2) + 4*(lane>>5).
-    float* T = smem + wave * 2048;
-    const size_t pw = p0 + (size_t)wc * (NCOL * 32);             // first pixel of this wave's 128
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int n = 0; n < NCOL; ++n)
-#pragma unroll
-                for (int qq = 0; qq < 8; ++qq) {
-                    const int q = 8 * half + qq;
-                    T[((q & 3) + 8 * ((q >> 2) & 1) + 4 * kg) * 128 + n * 32 + l31] = acc[m][n][q];
-                }
-            // rows of the pass: local row r (0..15) <-> cout cb*BM + (wm*2 + m)*32 + 16*half + r
-            const int cbase = cb * (MT * 32) + (wm * 2 + m) * 32 + 16 * half;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int f = lane + 64 * i, r = f >> 5, pq = f & 31;
-                const float4 t = *reinterpret_cast<const float4*>(T + r * 128 + 4 * pq);
-                const size_t px = pw + 4 * pq;
-                const int co = cbase + r;
-                if (px < P.HW) {
-                    const size_t o = ((size_t)b * P.Cout + co) * P.HW + px;
-                    const float bv = P.bias ? P.bias[co] : 0.0f;
-                    float4 o4 = make_float4(t.x + bv, t.y + bv, t.z + bv, t.w + bv);
-                    if (P.res) {
-                        const float4 r4 = *reinterpret_cast<const float4*>(P.res + o);
-                        o4.x += r4.x; o4.y += r4.y; o4.z += r4.z; o4.w += r4.w;
-                    }
-                    *reinterpret_cast<float4*>(P.y + o) = o4;
-                }
-            }
-        }
-    }
-}
+#define MDT_C1_TERMS 3
+#define MDT_C1_KERNEL k_conv1x1_stream
+#include "vae_conv1x1_stream_body.h"
+#undef MDT_C1_KERNEL
+#undef MDT_C1_TERMS
+#define MDT_C1_TERMS 1
+#define MDT_C1_KERNEL k_conv1x1_stream1t
+#include "vae_conv1x1_stream_body.h"
+#undef MDT_C1_KERNEL
+#undef MDT_C1_TERMS
 
 // OI fp32 -> records [cb][phase][hl][ks][mt][lane] of 8 bf16: cout = cb*BM + mt*32 + (lane & 31),
 // cin = phase*32 + ks*16 + (lane >> 5)*8 + j.  Zero outside [Cout).
@@ -449,7 +175,10 @@ int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_
         P.NCB = cout / (MT * 32);
         P.NP = cin / 32;
         dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-        if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream<2>, grid, block, 0, s, P);
+        if (mfma_single_term()) {      // MDTILE_PRECISION_BF16
+            if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream1t<2>, grid, block, 0, s, P);
+            else hipLaunchKernelGGL(k_conv1x1_stream1t<4>, grid, block, 0, s, P);
+        } else if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream<2>, grid, block, 0, s, P);
         else hipLaunchKernelGGL(k_conv1x1_stream<4>, grid, block, 0, s, P);
         MDT_LAUNCH_CHECK();
         return MDTILE_OK;
@@ -459,7 +188,11 @@ int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_
     P.NCB = round_up1(cout, MT * 32) / (MT * 32);
     P.NP = cin / 32;
     dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-    if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x3<8, 256>), grid, block, 0, s, P);
+    if (mfma_single_term()) {
+        if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x1<8, 256>), grid, block, 0, s, P);
+        else if (MT == 4) hipLaunchKernelGGL((k_conv1x1_bf16x1<4, 128>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_conv1x1_bf16x1<2, 256>), grid, block, 0, s, P);
+    } else if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x3<8, 256>), grid, block, 0, s, P);
     else if (MT == 4) hipLaunchKernelGGL((k_conv1x1_bf16x3<4, 128>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((k_conv1x1_bf16x3<2, 256>), grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();

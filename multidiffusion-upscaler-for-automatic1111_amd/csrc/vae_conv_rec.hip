@@ -64,6 +64,7 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
     while (__builtin_amdgcn_s_memrealtime() - t0 < d) __builtin_amdgcn_s_sleep(32);
 }
 
+#define MDT_REC_TERMS 3
 #define MDT_REC_KERNEL k_conv3x3_rec
 #define MDT_REC_ST 0
 #include "vae_conv_rec_direct_body.h"
@@ -74,6 +75,20 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
 #include "vae_conv_rec_direct_body.h"
 #undef MDT_REC_KERNEL
 #undef MDT_REC_ST
+#undef MDT_REC_TERMS
+// one-term forms (MDTILE_PRECISION_BF16)
+#define MDT_REC_TERMS 1
+#define MDT_REC_KERNEL k_conv3x3_rec1t
+#define MDT_REC_ST 0
+#include "vae_conv_rec_direct_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#define MDT_REC_KERNEL k_conv3x3_rec1t_st
+#define MDT_REC_ST 1
+#include "vae_conv_rec_direct_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#undef MDT_REC_TERMS
 
 // =====================================================================================================================
 // nearest-2x upsample + 3x3 conv in sub-pixel form (four 2x2 convs on the un-upsampled grid, see vae_conv_bf16x3.hip
@@ -83,6 +98,7 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
 // Weight chunk [hl][bb][v][mt][lane] per (a, cb, k, u) in a 3-slot ring.  Persistent like k_conv3x3_rec; an item has 2 NK
 // phases, which need not be a multiple of 3, so the ring position of an item's first chunk (r0) rotates from item to item:
 // the next item's chunks 0 / 1 go to the two slots the last phase is NOT reading.
+#define MDT_REC_TERMS 3
 #define MDT_REC_KERNEL k_upconv_rec
 #define MDT_REC_ST 0
 #include "vae_conv_rec_upconv_body.h"
@@ -93,6 +109,20 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
 #include "vae_conv_rec_upconv_body.h"
 #undef MDT_REC_KERNEL
 #undef MDT_REC_ST
+#undef MDT_REC_TERMS
+// one-term forms (MDTILE_PRECISION_BF16)
+#define MDT_REC_TERMS 1
+#define MDT_REC_KERNEL k_upconv_rec1t
+#define MDT_REC_ST 0
+#include "vae_conv_rec_upconv_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#define MDT_REC_KERNEL k_upconv_rec1t_st
+#define MDT_REC_ST 1
+#include "vae_conv_rec_upconv_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#undef MDT_REC_TERMS
 
 // =====================================================================================================================
 // fp32 NCHW -> record image (+ optional fixed-statistics GroupNorm + SiLU): entry points of the record path (conv_in /
@@ -297,8 +327,13 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
         const int cus = num_cus();
         stagger(items, cus, (unsigned)P.NK * 400u + 2000u);
         dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-        if (d_part) hipLaunchKernelGGL(k_upconv_rec_st, grid, block, 0, s, P);
-        else hipLaunchKernelGGL(k_upconv_rec, grid, block, 0, s, P);
+        if (mfma_single_term()) {
+            if (d_part) hipLaunchKernelGGL(k_upconv_rec1t_st, grid, block, 0, s, P);
+            else hipLaunchKernelGGL(k_upconv_rec1t, grid, block, 0, s, P);
+        } else {
+            if (d_part) hipLaunchKernelGGL(k_upconv_rec_st, grid, block, 0, s, P);
+            else hipLaunchKernelGGL(k_upconv_rec, grid, block, 0, s, P);
+        }
         MDT_LAUNCH_CHECK();
         return MDTILE_OK;
     }
@@ -308,7 +343,11 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
     const int cus = num_cus();                    // one block per CU (155 KB LDS, 2 waves per SIMD)
     if (cout % 128 == 0) stagger(items, cus, (unsigned)P.NK * 900u + 1500u);
     dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-    if (d_part) hipLaunchKernelGGL((k_conv3x3_rec_st<2, 2, 4>), grid, block, 0, s, P);
+    if (mfma_single_term()) {
+        if (d_part) hipLaunchKernelGGL((k_conv3x3_rec1t_st<2, 2, 4>), grid, block, 0, s, P);
+        else if (cout % 128 == 0) hipLaunchKernelGGL((k_conv3x3_rec1t<2, 2, 4>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_conv3x3_rec1t<1, 1, 2>), grid, block, 0, s, P);
+    } else if (d_part) hipLaunchKernelGGL((k_conv3x3_rec_st<2, 2, 4>), grid, block, 0, s, P);
     else if (cout % 128 == 0) hipLaunchKernelGGL((k_conv3x3_rec<2, 2, 4>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((k_conv3x3_rec<1, 1, 2>), grid, block, 0, s, P);      // conv_out: one 32-cout tile, bias padded to 32 by the caller
     MDT_LAUNCH_CHECK();

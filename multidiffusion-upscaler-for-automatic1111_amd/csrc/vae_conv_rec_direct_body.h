@@ -2,9 +2,12 @@
 //   MDT_REC_KERNEL = k_conv3x3_rec,    MDT_REC_ST = 0 : the shipping kernel -- its code is what it was before the statistics variant existed
 //                                                      (a shared __device__ body template changed hipcc's code for it: 8642 -> 8491 instructions)
 //   MDT_REC_KERNEL = k_conv3x3_rec_st, MDT_REC_ST = 1 : + the GroupNorm statistics of the output (epilogue_item<.., ST = true>): slow mode's pooled sites
+//   MDT_REC_TERMS = 3 (the kernels above) or 1 (k_conv3x3_rec1t / k_conv3x3_rec1t_st, MDTILE_PRECISION_BF16): the one-term form issues only
+//   w_hi x x_hi and reads only the hi fragments; its DMA pieces, ring slots and counted waits are the three-term kernel's, lo planes included
 template <int MW, int WM, int NROW>
 __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
     constexpr bool ST = MDT_REC_ST != 0;
+    constexpr int NT = MDT_REC_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), planes read
     constexpr int WR = 8 / WM, TH = WR * NROW, MT = MW * WM, HN = NROW / 2;
     constexpr int ROWS = TH + 2, COLS = 34;
     using IS = InStage<ROWS>;
@@ -99,14 +102,14 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[((hl * 3 + dx) * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[((hl * 3 + dx) * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int stage, int dy, int dx, int h) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + (dy + h * HN) * COLS + dx;
 #pragma unroll
         for (int n = 0; n < HN; ++n)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     WorkItem cur, nxt;
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                 MDT_PIN();
                 // ---- this half-step's MFMAs: term-major over its accumulators (a dependent MFMA is MW*HN issues away)
 #pragma unroll
-                for (int term = 0; term < 3; ++term)
+                for (int term = 3 - NT; term < 3; ++term)
 #pragma unroll
                     for (int n = 0; n < HN; ++n)
 #pragma unroll

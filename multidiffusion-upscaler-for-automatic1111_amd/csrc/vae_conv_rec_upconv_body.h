@@ -1,7 +1,9 @@
 // Body of k_upconv_rec / k_upconv_rec_st (csrc/vae_conv_rec.hip includes this file twice; see vae_conv_rec_direct_body.h for why the text is
-// shared by inclusion and not through a body template): MDT_REC_ST = 1 adds the GroupNorm statistics of the output.
+// shared by inclusion and not through a body template): MDT_REC_ST = 1 adds the GroupNorm statistics of the output, MDT_REC_TERMS = 1 is the
+// one-term form (k_upconv_rec1t / _st: w_hi x x_hi only, hi fragments only, the DMA / wait protocol of the three-term kernel unchanged).
 __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
     constexpr bool ST = MDT_REC_ST != 0;
+    constexpr int NT = MDT_REC_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), planes read
     constexpr int MT = 4, MW = 2, WM = 2, NROW = 2, TH = 8;
     constexpr int ROWS = TH + 2, COLS = 34;
     using IS = InStage<ROWS>;
@@ -88,14 +90,14 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[(((hl * 2 + bb) * 2 + v) * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[(((hl * 2 + bb) * 2 + v) * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int xfrag, int stage, int u, int s) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + u * COLS + s;
 #pragma unroll
         for (int n = 0; n < NROW; ++n)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     Item cur, nxt;
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                     }
                     MDT_PIN();
 #pragma unroll
-                    for (int term = 0; term < 3; ++term)
+                    for (int term = 3 - NT; term < 3; ++term)
 #pragma unroll
                         for (int n = 0; n < NROW; ++n)
 #pragma unroll

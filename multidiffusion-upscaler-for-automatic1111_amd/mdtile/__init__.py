@@ -7,6 +7,7 @@ missing or a call fails, an exception is raised.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
@@ -166,16 +167,38 @@ def lib() -> ctypes.CDLL:
     return L
 
 
-PRECISION_BF16X3, PRECISION_F32 = 0, 1
+PRECISION_BF16X3, PRECISION_F32, PRECISION_BF16 = 0, 1, 2
 
 
 def set_precision(mode: int) -> None:
-    """PRECISION_BF16X3 (default: split-bf16 matrix-core kernels) or PRECISION_F32 (exact-fp32 MFMA kernels everywhere)."""
+    """Arithmetic of the matrix-core kernels (convs, attention), process-wide:
+    PRECISION_BF16X3 (default): split-bf16 operands, three bf16 MFMAs per product, fp32 accumulation (~1e-5 relative to fp32);
+    PRECISION_F32: exact-fp32 MFMA kernels everywhere (~4x slower);
+    PRECISION_BF16: one bf16 MFMA per product, bf16_rn(a) x bf16_rn(b) with fp32 accumulation -- the arithmetic of a half-precision
+    (bfloat16) VAE; tensors in and out, the residual stream, GroupNorm statistics and softmax stay fp32.
+    Raises MdtileError on any other value."""
     _check(lib().mdtile_set_precision(int(mode)), "mdtile_set_precision")
 
 
 def get_precision() -> int:
     return int(lib().mdtile_get_precision())
+
+
+@contextlib.contextmanager
+def precision(mode: int):
+    """`with mdtile.precision(mdtile.PRECISION_BF16): ...` -- sets the mode for the block and restores the previous one on the way out
+    (also when the block raises).  The mode is process-wide: work queued on any stream inside the block runs in it.  A block that asks
+    for the mode already in force changes nothing.  A load-time preset of only one strict bit (MDTILE_CONV_MODE=f32 without
+    MDTILE_ATTN_MODE=f32, or the reverse) reads as PRECISION_BF16X3 and is restored as that."""
+    prev = get_precision()
+    if int(mode) == prev:
+        yield
+        return
+    set_precision(mode)
+    try:
+        yield
+    finally:
+        set_precision(prev)
 
 
 def exported_symbols() -> List[str]:

@@ -13,7 +13,10 @@ device assembly and checks the emitted instruction stream instead:
       {0, 2, 3, 4} in k_conv3x3_rec2 and {0, 6, 7, 8, 9} in k_upconv_rec2 (one counted wait per step position, csrc/vae_conv_rec2.hip),
       {0, 2, 5, 15} in k_conv3x3_recd (probes/csrc/vae_conv_recd.hip, checked with --probes only: the dripped epilogue's slot traffic may stay in flight behind the chunk)
     * MFMA counts per unrolled trip match the source (conv: 36 half-steps x 12; upconv: 24 combo-steps x 12; attention: 24 / slab)
-usage: python tools/asm_guard.py   (exit code 0 = ok; prints one line per kernel)      -- also run by tests/test_host_abi.py
+    * with --one-term: the one-term forms of MDTILE_PRECISION_BF16 (k_conv3x3_rec1t, k_upconv_rec1t, their _st forms, k_conv3x3_rec2_1t, k_upconv_rec2_1t,
+      k_conv1x1_stream1t, k_attn_bf16x1) keep their three-term twins' DMA count and barrier waits exactly; their MFMA multiples are a third
+usage: python tools/asm_guard.py [--one-term] [--probes]   (exit code 0 = ok; prints one line per kernel)      -- also run by tests/test_host_abi.py
+       (--one-term adds the one-term kernels; mdtile/build.py runs the guard with it, tests/test_precision_bf16_host.py checks them)
 """
 from __future__ import annotations
 
@@ -140,6 +143,24 @@ def main() -> int:
         (att, "k_attn_bf16x3ILi256", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=6)),
         (att, "k_attn_bf16x3ILi128", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=6)),
     ]
+    # --one-term: also the one-term forms of MDTILE_PRECISION_BF16 (mdtile/build.py passes it): the DMA pieces and counted waits of their
+    # three-term twins, a third of the MFMAs
+    one_term = [
+        (c11, "k_conv1x1_stream1tILi2", dict(dma_min=5, barrier_vmcnt=[0, 5], mfma_multiple=8)),
+        (c11, "k_conv1x1_stream1tILi4", dict(dma_min=4, barrier_vmcnt=[0, 4], mfma_multiple=8)),
+        (rec, "k_conv3x3_rec1tILi2ELi2ELi4", dict(dma_min=8, barrier_vmcnt=[0, 5], mfma_multiple=4)),
+        (rec, "k_conv3x3_rec1tILi1ELi1ELi2", dict(dma_min=4, barrier_vmcnt=[0, 5], mfma_multiple=1)),
+        (rec, "k_upconv_rec1tE", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=4)),
+        (rec, "k_conv3x3_rec1t_stILi2ELi2ELi4", dict(dma_min=8, barrier_vmcnt=[0, 5], mfma_multiple=4)),
+        (rec, "k_upconv_rec1t_stE", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=4)),
+        (rec2, "k_conv3x3_rec2_1tILi2ELi2ELi4", dict(dma_min=8, barrier_vmcnt=[0, 2, 3, 4], mfma_multiple=4)),
+        (rec2, "k_upconv_rec2_1tE", dict(dma_min=8, barrier_vmcnt=[0, 6, 7, 8, 9], mfma_multiple=4)),
+        (att, "k_attn_bf16x1ILi512", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=2)),
+        (att, "k_attn_bf16x1ILi256", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=2)),
+        (att, "k_attn_bf16x1ILi128", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=2)),
+    ]
+    if "--one-term" in sys.argv:
+        plan += one_term
     if recd is not None:      # dripped epilogue: vmcnt(5) at dy = 1, and behind a slot phase a lower bound of the slot's own memory instructions (15 / 2)
         plan.append((recd, "k_conv3x3_recdE", dict(dma_min=8, barrier_vmcnt=[0, 2, 5, 15], mfma_multiple=12)))
     for table, sub, expect in plan:

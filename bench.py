@@ -2,7 +2,7 @@
 """
 bench.py -- latent-px/s of the tile-blend + tiled-VAE-decode hot path on an 8K image (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...                     (no launcher environment: bench.py starts its N ranks itself, same line, rc 0)
     python bench.py --gpus N --single-process ...    (ONE process driving N devices: mdtile_shard_init + VAEHook.devices, the form a webui uses)
@@ -15,7 +15,7 @@ The UNet itself is out of scope: the blend consumes pre-ge
 offline).  Inputs are resident in HBM before the timed region; nothing is cached between steps.  In fast mode the decoder tiles shed the
 part of their padding that the remaining 3x3 convs cannot carry into the valid rectangle ("live-window narrowing", scripts/tilevae.py:
 live_windows; the assembled image is bit-identical to the whole-tile sweep; `config.vae_live_window`, MDTILE_LIVE_WINDOW=0 = whole tiles).
-`whole_tiles` in the JSON line is the same step timed with the narrowing off, with `bit_identical_image` = torch.equal of the two 8K images.
+`whole_tiles` in the JSON line (--full) is the same step timed with the narrowing off, with `bit_identical_image` = torch.equal of the two 8K images.
 
 N > 1: strong scaling of the same image -- diffusion tiles in row bands per rank with a neighbour halo exchange of the
 overlap-row partial sums, VAE tiles dealt round-robin, the fast-mode GroupNorm estimator split by rows across the ranks
@@ -24,11 +24,15 @@ assembled 8192x8192 image, like the single-GPU run).  ONE RCCL communicator per 
 carries the whole data plane; torch.distributed runs on gloo for the control plane only (id broadcast, votes, barrier, the max
 over ranks of the clock).  If the engine's communicator cannot be brought up on every rank, the job creates ONE torch "nccl"
 group instead and the same collectives run there.
-The JSON line carries `roofline` (the kernel class with the largest share of the step: the split-bf16 MFMA 3x3 conv;
+A plain run only sets up, warms up, times its steps, writes --dump-outputs and prints the JSON line.  With `--full` it then runs
+the untimed passes (on N = 1 unless said otherwise), and the line carries what they measured (null without `--full`):
+`stage_ms` (every form), `roofline` (every rank; the kernel class with the largest share of the step: the split-bf16 MFMA 3x3 conv;
 flops = the ones executed, peak = 2500/3 TFLOP/s for a kernel that spends 3 bf16 MFMAs per product; `traffic` = HBM bytes
 per launch when MDTILE_PMC_SUMMARY points at tools/pmc_summary.py's json of a previous rocprofv3 --pmc pass),
-`roofline_blend` (the HBM-bound blend kernel) and `cpu_baseline` (the oracle = CPU port of the reference algorithm, timed
-on this box's host cores on a bounded sample).
+`roofline_blend` (the HBM-bound blend kernel), `whole_tiles`, `value_f32`, `parity`, `companions` and `cpu_baseline` (the
+oracle = CPU port of the reference algorithm, timed on this box's host cores on a bounded sample); `--encode` adds its roofline
+and parity, `--single-process` its `debug_check`.  The --no-* options drop single passes of a --full run.  `--debug-single-device`
+(N > 1 ranks on one GPU) is a functional check whatever --full says: its `debug_check` is always computed.
 """
 from __future__ import annotations
 
@@ -52,6 +56,9 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA
 # split-bf16 kernels issue 3 bf16 MFMAs per fp32-class product: their ceiling in ALGORITHMIC (fp32-equivalent) flops
 MFMA_BF16X3_PEAK_TFLOPS = MFMA_BF16_PEAK_TFLOPS / 3.0
 
+# the untimed passes a plain run leaves out (each can also be dropped from a --full run on its own)
+FULL_PASSES = ("no_cpu_baseline", "no_whole_tile_pass", "no_f32_pass", "no_profile_pass", "no_oracle_pass", "no_stress_pass", "no_companions")
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -67,10 +74,15 @@ def parse():
     ap.add_argument("--vae-tile", type=int, default=256)
     ap.add_argument("--slow-vae", action="store_true", help="slow-mode GroupNorm (pooled per norm) instead of fast mode")
     ap.add_argument("--no-vae", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every untimed pass: the per-stage split, the per-kernel and blend rooflines, the whole-tile and "
+                         "strict-fp32 companion steps, the parity legs against the oracle, the companion configurations and the CPU baseline (several "
+                         "minutes at the default size).  Without it the run only sets up, warms up, times its steps, dumps its outputs if asked and prints "
+                         "the line; the fields of the skipped passes are null.  The --no-* options below drop single passes of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-whole-tile-pass", action="store_true", help="skip the companion step with the live-window narrowing off (whole_tiles in the JSON line)")
     ap.add_argument("--no-f32-pass", action="store_true", help="skip the strict-fp32 companion decode (parity.rel_err_vs_f32, value_f32)")
-    ap.add_argument("--no-profile-pass", action="store_true", help="skip the per-stage split and the HIP-event roofline pass (PMC runs)")
+    ap.add_argument("--no-profile-pass", action="store_true", help="skip the HIP-event roofline pass and the decode of the per-stage split (PMC runs)")
     ap.add_argument("--no-oracle-pass", action="store_true", help="skip parity.rel_err_vs_oracle (assembled cfg3 decode vs the oracle on the GPU, untimed)")
     ap.add_argument("--no-stress-pass", action="store_true", help="skip parity.rel_err_vs_oracle_stress (cfg3 decode of the trained-like 'stress' decoder vs the oracle on the GPU, untimed)")
     ap.add_argument("--encode", action="store_true", help="the ENCODE direction instead (SURVEY section 8 f1): one line for the tiled VAE encode of an "
@@ -91,7 +103,11 @@ def parse():
                          "moments with --encode) as DIR/<name>.npy, float32, at most 48 MiB in all: an array larger than its cap is "
                          "replaced by a fixed, seeded sample of its elements (DIR/manifest.json says which).  Inputs are seeded: the "
                          "same arguments give the same inputs on every run")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        for name in FULL_PASSES:
+            setattr(args, name, True)
+    return args
 
 
 class Profile:
@@ -462,19 +478,21 @@ def run_encode(args, E, pl, ld, dev):
         dump_outputs(args.dump_outputs, {"latent": (y, DUMP_FULL_ELEMS)})
     lat = (side // 8) * (side // 8)
     # per-kernel roofline of one more encode (HIP events around every conv / attention launch, same stream)
-    prof = Profile()
-    with Instrument(E, prof):
-        quiet(lambda: hook(x))
-    agg = prof.summary()
-    mm = {k: v for k, v in agg.items() if k.startswith("k_")}
-    dom = max(mm, key=lambda k_: mm[k_][2])
-    n, work, secs = mm[dom]
-    peak = MFMA_BF16X3_PEAK_TFLOPS if ("bf16x3" in dom or "_rec" in dom) else MFMA_F32_PEAK_TFLOPS
-    roofline = {"kernel": dom, "bound": "mfma", "achieved": round(work / secs / 1e12, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                "frac": round(work / secs / 1e12 / peak, 4), "traffic": None, "launches": n, "avg_us": round(secs / n * 1e6, 1),
-                "share_of_encode": round(secs / (ms * 1e-3), 3),
-                "breakdown_s": {k: round(v[2], 4) for k, v in sorted(agg.items())},
-                "breakdown_tflops": {k: round(v[1] / v[2] / 1e12, 2) for k, v in sorted(mm.items())}}
+    roofline = None
+    if args.full:
+        prof = Profile()
+        with Instrument(E, prof):
+            quiet(lambda: hook(x))
+        agg = prof.summary()
+        mm = {k: v for k, v in agg.items() if k.startswith("k_")}
+        dom = max(mm, key=lambda k_: mm[k_][2])
+        n, work, secs = mm[dom]
+        peak = MFMA_BF16X3_PEAK_TFLOPS if ("bf16x3" in dom or "_rec" in dom) else MFMA_F32_PEAK_TFLOPS
+        roofline = {"kernel": dom, "bound": "mfma", "achieved": round(work / secs / 1e12, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                    "frac": round(work / secs / 1e12 / peak, 4), "traffic": None, "launches": n, "avg_us": round(secs / n * 1e6, 1),
+                    "share_of_encode": round(secs / (ms * 1e-3), 3),
+                    "breakdown_s": {k: round(v[2], 4) for k, v in sorted(agg.items())},
+                    "breakdown_tflops": {k: round(v[1] / v[2] / 1e12, 2) for k, v in sorted(mm.items())}}
     # parity: one tile of the timed image vs the oracle on this GPU (fast mode only)
     parity = None
     if not args.no_oracle_pass and not args.slow_vae:
@@ -522,7 +540,7 @@ def run_encode(args, E, pl, ld, dev):
                        "stress_recipe": getattr(enc_s, "stress_info", None)})
     return {"metric": "latent-px/sec tiled-VAE-encode, 8K image", "value": round(lat / (ms * 1e-3), 1), "unit": "latent-px/s", "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 2), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32" if E.get_precision() == E.PRECISION_F32 else "bf16x3+f32", "data": "synthetic",
+            "dtype": "f32" if E.get_precision() == E.PRECISION_F32 else "bf16x3+f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"tiled VAE ENCODE of a {side}x{side} image (encoder tile {tile}, {'slow' if args.slow_vae else 'fast'} mode, SD encoder ch=128, random weights) "
                                    f"-> {side // 8}x{side // 8} latent moments", "image": [side, side], "vae_tile": tile},
             "roofline": roofline, "parity": parity, "cpu_baseline": None,
@@ -628,10 +646,11 @@ def run_single_process(args):
             dump["image"] = (last["image"], DUMP_IMAGE_ELEMS)
         dump_outputs(args.dump_outputs, dump)
     last.clear()
-    t_blend = timed(blend_eval, args.evals)
-    t_vae = timed(lambda: _quiet(lambda: hook(z)), 1) if hook is not None else None
-    check = None
-    if hook is not None:
+    t_blend = t_vae = check = None
+    if args.full:
+        t_blend = timed(blend_eval, args.evals)
+        t_vae = timed(lambda: _quiet(lambda: hook(z)), 1) if hook is not None else None
+    if args.full and hook is not None:
         # the assembled image of the N-device sweep against the plain one-device sweep of the same latent (same kernels, same frozen
         # statistics: bit for bit) -- and the sharded blend's canvas rows against the one-device blend
         img = _quiet(lambda: hook(z)).float()
@@ -641,23 +660,24 @@ def run_single_process(args):
         check = {"assembled_image_bit_identical_to_one_device": bool(torch.equal(img, ref)),
                  "assembled_image_rel_err_vs_one_device": float((img - ref).abs().max().item() / ref.abs().max().item()), "image_shape": list(img.shape)}
         del img, ref
-    kw = dict(weights=sb.local[0]["weights"]) if method == E.METHOD_MD else dict(tile_w=sb.local[0]["tile_wt"], rescale=sb.local[0]["rescale"])
-    with torch.cuda.device(dev0):
-        full0 = torch.randn(plan.num_tiles * N, C, plan.tile_h, plan.tile_w, generator=torch.Generator(device="cpu").manual_seed(1)).to(dev0)
-        one = E.blend(plan, method, [full0], N, C, packed=True, **kw)
-    outs = blend_eval()
-    sync_all()
-    worst = 0.0
-    for i in order:
-        b = sb.bands[i]
-        worst = max(worst, float((outs[i][:, :, b.row_lo:b.row_hi].to(dev0) - one[:, :, b.row_lo:b.row_hi]).abs().max().item()))
-    check = dict(check or {}, sharded_blend_max_abs_diff_vs_one_device=worst)
-    del full0, one
+    if args.full:
+        kw = dict(weights=sb.local[0]["weights"]) if method == E.METHOD_MD else dict(tile_w=sb.local[0]["tile_wt"], rescale=sb.local[0]["rescale"])
+        with torch.cuda.device(dev0):
+            full0 = torch.randn(plan.num_tiles * N, C, plan.tile_h, plan.tile_w, generator=torch.Generator(device="cpu").manual_seed(1)).to(dev0)
+            one = E.blend(plan, method, [full0], N, C, packed=True, **kw)
+        outs = blend_eval()
+        sync_all()
+        worst = 0.0
+        for i in order:
+            b = sb.bands[i]
+            worst = max(worst, float((outs[i][:, :, b.row_lo:b.row_hi].to(dev0) - one[:, :, b.row_lo:b.row_hi]).abs().max().item()))
+        check = dict(check or {}, sharded_blend_max_abs_diff_vs_one_device=worst)
+        del full0, one
     value = L * L / elapsed
     print(json.dumps({
         "metric": "latent-px/sec tile-blend+VAE-decode, 8K image", "value": round(value, 1), "unit": "latent-px/s", "n_gpus": n, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f32" if E.get_precision() == E.PRECISION_F32 else "bf16x3+f32", "data": "synthetic",
+        "dtype": "f32" if E.get_precision() == E.PRECISION_F32 else "bf16x3+f32", "data": "synthetic", "full": args.full,
         "config": {"workload": f"{'SDXL ' if L == 1024 else ''}{8 * L}x{8 * L} (latent {L}x{L}): {args.evals} x [tile gather + {'MultiDiffusion' if args.method == 'md' else 'Mixture-of-Diffusers'} "
                                f"blend, {plan.num_tiles} tiles {plan.tile_w}x{plan.tile_h} overlap {plan.overlap}, N=2,C=4] + "
                                + ("no VAE" if hook is None else f"tiled VAE decode (tile {args.vae_tile}, fast mode, SD decoder ch=128, random weights)"),
@@ -665,7 +685,7 @@ def run_single_process(args):
                    "sharding": f"ONE process, {n} devices: tile-row bands + halo exchange (mdtile.Shard / ShardedBlend); VAE tiles dealt to the devices by area "
                                "(VAEHook.devices), estimator on the first device, rectangles copied to the first device inside the step"},
         "process_model": "single-process multi-device (mdtile_shard_init + VAEHook.devices)", "devices": devs, "devices_visible": visible,
-        "stage_ms": {"blend_eval": round(t_blend * 1e3, 4), "vae_decode": None if t_vae is None else round(t_vae * 1e3, 2)},
+        "stage_ms": None if t_blend is None else {"blend_eval": round(t_blend * 1e3, 4), "vae_decode": None if t_vae is None else round(t_vae * 1e3, 2)},
         "transport": transport, "debug_check": check, "roofline": None, "cpu_baseline": None,
         "note": "per-kernel roofline, parity legs and cpu_baseline are on the N = 1 line; this line times the single-process form of the N-device flow"}))
     shard.destroy()
@@ -840,13 +860,14 @@ def main():
             dump_outputs(args.dump_outputs, dump)
         image = None
         # per-stage split, untimed extras (same work, separate clocks)
-        sync_all()
-        tb = time.perf_counter()
-        for _ in range(args.evals):
-            blend_eval()
-        sync_all()
-        t_blend_eval = (time.perf_counter() - tb) / args.evals
-        t_vae = None
+        t_blend_eval = t_vae = None
+        if args.full:
+            sync_all()
+            tb = time.perf_counter()
+            for _ in range(args.evals):
+                blend_eval()
+            sync_all()
+            t_blend_eval = (time.perf_counter() - tb) / args.evals
         if hook is not None and not args.no_profile_pass:
             tv = time.perf_counter()
             hook(z)
@@ -1002,7 +1023,7 @@ def main():
     # (tools/gpu_pass.sh pmc -> tools/pmc_summary.py; counters cannot be read from inside the process).  The summary records the digest
     # of the libmdtile build it was taken on: a summary of another build is REJECTED (traffic stays null).
     pmc_path = os.environ.get("MDTILE_PMC_SUMMARY", "") or os.path.join(ROOT, "profiles", "pmc_hbm_summary_current.json")
-    if rank == 0 and pmc_path and os.path.exists(pmc_path):
+    if rank == 0 and not args.no_profile_pass and pmc_path and os.path.exists(pmc_path):
         with open(pmc_path) as f:
             pmc = json.load(f)
         from mdtile import build as _mb
@@ -1258,8 +1279,9 @@ def main():
                        "vae_tile": None if hook is None else args.vae_tile,
                        "vae_live_window": None if hook is None else bool(pl.tilevae.LIVE_WINDOW and not args.slow_vae),   # padded border the remaining convs cannot carry into the valid rectangle is not computed (same pixels, bit for bit)
                        "sharding": "none" if world == 1 else f"tile-row bands x{world} + halo exchange; VAE tiles round-robin, estimator split by rows, image gathered to rank 0 inside the step"},
-            "stage_ms": {"blend_eval": round(t_blend_eval * 1e3, 4), "vae_decode": None if t_vae is None else round(t_vae * 1e3, 2)},
-            "stage_px_per_s": {"blend_eval": round(L * L / t_blend_eval, 1), "vae_decode": None if t_vae is None else round(L * L / t_vae, 1)},
+            "full": args.full,
+            "stage_ms": None if t_blend_eval is None else {"blend_eval": round(t_blend_eval * 1e3, 4), "vae_decode": None if t_vae is None else round(t_vae * 1e3, 2)},
+            "stage_px_per_s": None if t_blend_eval is None else {"blend_eval": round(L * L / t_blend_eval, 1), "vae_decode": None if t_vae is None else round(L * L / t_vae, 1)},
             "whole_tiles": whole,
             "value_f32": None if value_f32 is None else round(value_f32, 1), "ms_per_step_f32": None if ms_f32 is None else round(ms_f32, 2),
             "parity": parity,

@@ -6,7 +6,7 @@ cp $L /tmp/libmdtile_current.so
 for r in 1 2; do
   for which in other current; do
     if [ $which = other ]; then cp $OTHER $L; else cp /tmp/libmdtile_current.so $L; fi
-    (timeout 300 python bench.py --no-vae --steps 20 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+    (timeout 300 python bench.py --full --no-vae --steps 20 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); b = d.get('roofline_blend') or d.get('roofline')
 print('$which', 'cold us', b.get('avg_us'), 'warm us', (b.get('warm') or {}).get('avg_us'))")

@@ -91,3 +91,13 @@ def test_no_gpu_is_a_loud_error_not_a_cpu_run(bench, monkeypatch):
     with pytest.raises(SystemExit) as ex:
         bench.main()
     assert "MI355X" in str(ex.value.code)
+
+
+def test_plain_run_leaves_out_the_untimed_passes(bench, monkeypatch):
+    """A plain run drops every untimed pass; `--full` runs them all, and a --no-* option still drops its own pass from a --full run."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    args = bench.parse()
+    assert not args.full and all(getattr(args, k) for k in bench.FULL_PASSES)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full", "--no-f32-pass"])
+    args = bench.parse()
+    assert args.full and args.no_f32_pass and not any(getattr(args, k) for k in bench.FULL_PASSES if k != "no_f32_pass")

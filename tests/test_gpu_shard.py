@@ -332,9 +332,9 @@ def test_bare_bench_command_launches_its_own_ranks(cuda):
 @pytest.mark.parametrize("n", [2, 8])
 def test_single_process_bench_form(cuda, n):
     """`python bench.py --gpus N --single-process`: mdtile.Shard(dev_ids) + ShardedBlend + VAEHook.devices in ONE process (what a webui can
-    use) -- timed line with n_gpus = N, the assembled image bit-identical to the one-device sweep, the sharded blend equal to the
-    one-device blend on every band's rows (one-GPU box: cuda:0 listed N times, copy transport)."""
-    d = _bench_line(["--gpus", str(n), "--single-process"] + _SMALL)
+    use) -- timed line with n_gpus = N, and with --full the assembled image bit-identical to the one-device sweep, the sharded blend
+    equal to the one-device blend on every band's rows (one-GPU box: cuda:0 listed N times, copy transport)."""
+    d = _bench_line(["--gpus", str(n), "--single-process", "--full"] + _SMALL)
     assert d["n_gpus"] == n and d["process_model"].startswith("single-process") and len(d["devices"]) == n, d
     assert d["transport"].startswith(("rccl", "copy")), d["transport"]
     chk = d["debug_check"]

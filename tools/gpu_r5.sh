@@ -24,7 +24,7 @@ for w in $WHAT; do
         (timeout 300 python probes/conv_drip_ab.py --b 3 --shapes 5,4 2>&1 | grep -v amdgpu.ids) >> $O/conv_drip_ab_$TAG.log 2>&1
         for d in 1 33 97 2 4 6 12 14 16 30; do echo "MDTILE_REC_DBG=$d (PROBES twin)" >> $O/conv_drip_ablation_$TAG.log; (timeout 200 python probes/conv_drip_ab.py --shapes 0 --dbg $d 2>&1 | grep -v "amdgpu.ids\|probes\]") >> $O/conv_drip_ablation_$TAG.log 2>&1; done
         cat $O/conv_drip_ab_$TAG.log;;
-    encode) (timeout 900 python bench.py --encode --steps 2 --warmup 1 2>&1 | tail -1) > $O/bench_encode_$TAG.json 2>&1; cut -c1-3000 $O/bench_encode_$TAG.json;;
+    encode) (timeout 900 python bench.py --encode --full --steps 2 --warmup 1 2>&1 | tail -1) > $O/bench_encode_$TAG.json 2>&1; cut -c1-3000 $O/bench_encode_$TAG.json;;
     stress) (timeout 900 python -m pytest tests/test_gpu_vae_stress.py -m gpu -q -s -p no:cacheprovider 2>&1 | grep "stress\|attention at\|passed\|failed") > $O/pytest_stress_$TAG.log 2>&1; cat $O/pytest_stress_$TAG.log;;
     sqbench) cd /tmp; BF="--steps 1 --warmup 0 --no-cpu-baseline --no-profile-pass --no-f32-pass --no-oracle-pass --no-whole-tile-pass --no-stress-pass --no-companions"
         (timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/sqm_a_$TAG -o p -- python $R/bench.py $BF 2>&1 | tail -2) > $O/sqm_a_$TAG.log 2>&1

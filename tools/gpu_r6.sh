@@ -2,7 +2,7 @@
 # what: every step of tools/gpu_r5.sh / gpu_r3.sh (tests | smoke | bench | benchq | prof | pmc | sqbench | encode | slow | ...) plus
 #   r6new    this round's new GPU tests (bare / single-process bench forms, encoder stress parity, statistics calls, stream copy)
 #   bare8    `python bench.py --gpus 8 --steps 1 --warmup 0` with NO launcher environment on this one-GPU box (rc, the JSON line)
-#   sp8      `python bench.py --gpus 8 --single-process --steps 1 --warmup 1` (cuda:0 listed eight times)
+#   sp8      `python bench.py --gpus 8 --single-process --full --steps 1 --warmup 1` (cuda:0 listed eight times)
 #   blendab  probes/blend_r6_ab.py: the shipping blend kernel, the LDS-staged form and the stream-copy floor, cold and warm, same process
 #   attnab   probes/attn_ab.py <other .so>: two builds of the attention kernel alternated in one process
 #   contend  the co-residency probes (probes/contention_*.py);   convf32  probes/convf32_probe.py over the block shapes under test
@@ -17,7 +17,7 @@ for w in $WHAT; do
   case $w in
     r6new) (timeout 2400 python -m pytest tests/test_gpu_shard.py tests/test_gpu_vae_stress.py tests/test_gpu_conv_stats.py tests/test_gpu_blend.py -m gpu -q --tb=short -p no:cacheprovider -s --durations=10 2>&1 | grep -v "Tiled VAE\|amdgpu.ids\|Sampling" | tail -70) > $O/pytest_r6new_$TAG.log 2>&1; tail -45 $O/pytest_r6new_$TAG.log;;
     bare8) (timeout 1500 python bench.py --gpus 8 --steps 1 --warmup 0 --no-cpu-baseline --no-profile-pass > $O/bench_bare8_$TAG.json 2> $O/bench_bare8_$TAG.err; echo "rc=$?" >> $O/bench_bare8_$TAG.err); tail -3 $O/bench_bare8_$TAG.err | cut -c1-300; cut -c1-2500 $O/bench_bare8_$TAG.json;;
-    sp8) (timeout 1500 python bench.py --gpus 8 --single-process --steps 1 --warmup 1 > $O/bench_sp8_$TAG.json 2> $O/bench_sp8_$TAG.err; echo "rc=$?" >> $O/bench_sp8_$TAG.err); tail -3 $O/bench_sp8_$TAG.err | cut -c1-300; cut -c1-2500 $O/bench_sp8_$TAG.json;;
+    sp8) (timeout 1500 python bench.py --gpus 8 --single-process --full --steps 1 --warmup 1 > $O/bench_sp8_$TAG.json 2> $O/bench_sp8_$TAG.err; echo "rc=$?" >> $O/bench_sp8_$TAG.err); tail -3 $O/bench_sp8_$TAG.err | cut -c1-300; cut -c1-2500 $O/bench_sp8_$TAG.json;;
     blendab) (timeout 900 python probes/blend_r6_ab.py 2>&1 | grep -v amdgpu.ids) > $O/blend_r6_ab_$TAG.log 2>&1
         if [ -f probes/_ab/libmdtile_r5_blend.so ]; then (MDTILE_AB_LIB=probes/_ab/libmdtile_r5_blend.so timeout 600 python probes/blend_r6_ab.py 2>&1 | grep -v amdgpu.ids) >> $O/blend_r6_ab_$TAG.log 2>&1; fi
         cat $O/blend_r6_ab_$TAG.log;;

@@ -376,6 +376,22 @@ int mdtile_crop_store(const float* d_tile, int N, int C, int th, int tw, const i
                       int is_decoder, float* d_result, int RH, int RW, mdtile_stream_t stream);
 /* tile extraction z[:, :, y1:y2, x1:x2] (tilevae.py:532-535) == mdtile_gather_rect with dtype f32 */
 
+/* mdtile_crop_store of every finished tile of one call into result [N,C,RH,RW] (fp32, on the calling device), one launch per
+ * MDTILE_VAE_ASSEMBLE_CHUNK tiles.  A tile [N,C,th,tw] may live on another device: it is read through the peer mapping, which the call
+ * enables (mdtile_enable_peer_access); a tile on a device the calling device cannot read, a bad bbox or a window outside the result
+ * returns an error before anything is launched. */
+#define MDTILE_VAE_ASSEMBLE_CHUNK 32
+typedef struct mdtile_vae_tile {
+    const float* tile;
+    int th, tw;
+    int in_bbox4[4];
+    int out_bbox4[4];
+} mdtile_vae_tile;
+int mdtile_vae_assemble(const mdtile_vae_tile* tiles, int n_tiles, int N, int C, int is_decoder, float* d_result, int RH, int RW,
+                        mdtile_stream_t stream);
+/* idempotent: kernels running on `device` may read memory of `peer` afterwards (MDTILE_E_ARG when the hardware cannot) */
+int mdtile_enable_peer_access(int device, int peer);
+
 /* fast-mode estimator input (tilevae.py:545-559): scale_factor = tile_size / max(H, W); nearest-exact resample of
  * z [N,C,H,W] to [N,C,oh,ow] (sizes from mdtile_vae_fast_size), per-channel re-standardisation (unbiased std over
  * N,H,W of both), clamp to [min z, max z].  d_ws: mdtile_vae_fast_ws_size(C) bytes. */

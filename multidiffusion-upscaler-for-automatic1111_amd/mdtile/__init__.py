@@ -29,6 +29,7 @@ CONV_EXACT_F32 = 2
 ATTN_EXACT_F32 = 1
 ATTN_V_CHANNEL_MAJOR = 2
 MAX_BATCHES, MAX_REGIONS = 320, 16
+VAE_ASSEMBLE_CHUNK = 32
 
 _DTYPES = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 
@@ -44,6 +45,10 @@ class _Region(ctypes.Structure):
 
 class _P2P(ctypes.Structure):
     _fields_ = [("peer", c_int), ("send", c_void_p), ("send_bytes", c_size_t), ("recv", c_void_p), ("recv_bytes", c_size_t)]
+
+
+class _VaeTile(ctypes.Structure):
+    _fields_ = [("tile", c_void_p), ("th", c_int), ("tw", c_int), ("in_bbox4", c_int * 4), ("out_bbox4", c_int * 4)]
 
 
 class _BlendArgs(ctypes.Structure):
@@ -141,6 +146,8 @@ _SIGNATURES = {
     "mdtile_vae_attn_takes_channel_major": (c_int, [c_int, c_int]),
     "mdtile_vae_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "mdtile_crop_store": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP, _IP, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "mdtile_vae_assemble": (c_int, [POINTER(_VaeTile), c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "mdtile_enable_peer_access": (c_int, [c_int, c_int]),
     "mdtile_vae_fast_size": (c_int, [c_int, c_int, c_int, _IP, _IP]),
     "mdtile_vae_fast_ws_size": (c_size_t, [c_int]),
     "mdtile_vae_fast_input": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -985,6 +992,26 @@ def crop_store(tile: torch.Tensor, in_bbox, out_bbox, result: torch.Tensor, is_d
     ib, ob = (c_int * 4)(*in_bbox), (c_int * 4)(*out_bbox)
     _check(lib().mdtile_crop_store(_p(tile), N, C, th, tw, ib, ob, int(is_decoder), _p(result), result.shape[2], result.shape[3],
                                    _stream()), "mdtile_crop_store")
+
+
+def vae_assemble(tiles: Sequence[Tuple[torch.Tensor, Sequence[int], Sequence[int]]], result: torch.Tensor, is_decoder: bool = True) -> None:
+    """crop_store of every (tile, in_bbox, out_bbox) into `result`, one launch per VAE_ASSEMBLE_CHUNK tiles, on the current stream of the
+    current device, which must own `result`.  A tile may live on another device: it is read through the peer mapping (enabled by the call;
+    MdtileError when this device cannot read that one)."""
+    _dev_tensor(result, "result", torch.float32)
+    N, C, RH, RW = result.shape
+    table = (_VaeTile * max(1, len(tiles)))()
+    for k, (t, ib, ob) in enumerate(tiles):
+        _dev_tensor(t, f"tiles[{k}]", torch.float32)
+        if tuple(t.shape[:2]) != (N, C):
+            raise MdtileError(f"tiles[{k}] has shape {tuple(t.shape)}, the result {tuple(result.shape)}")
+        table[k] = _VaeTile(t.data_ptr(), t.shape[2], t.shape[3], (c_int * 4)(*ib), (c_int * 4)(*ob))
+    _check(lib().mdtile_vae_assemble(table, len(tiles), N, C, int(is_decoder), _p(result), RH, RW, _stream()), "mdtile_vae_assemble")
+
+
+def enable_peer_access(device: int, peer: int) -> None:
+    """Kernels running on `device` may read memory of `peer` afterwards (idempotent); MdtileError when the hardware cannot."""
+    _check(lib().mdtile_enable_peer_access(int(device), int(peer)), "mdtile_enable_peer_access")
 
 
 def vae_fast_input(z: torch.Tensor, tile_size: int) -> torch.Tensor:

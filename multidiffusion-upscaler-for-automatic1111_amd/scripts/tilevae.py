@@ -18,6 +18,7 @@ upstream :492-496).
 """
 from __future__ import annotations
 
+import contextlib
 from time import time
 from typing import Dict, List, Optional, Tuple
 
@@ -78,6 +79,69 @@ def custom_group_norm(input, num_groups, mean, var, weight=None, bias=None, eps=
     return mdtile.gn_apply(input, mean, var, weight, bias, num_groups, eps, silu)
 
 
+def _on_device(d):
+    """torch.cuda.device(d), or nothing for d None (one device: the current one)."""
+    return contextlib.nullcontext() if d is None else torch.cuda.device(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one process, several devices: the device list (preload.py: --mdtile-devices)
+# ---------------------------------------------------------------------------------------------------------------------
+def with_vae_device_first(slots: List[int], vae_device: int) -> List[int]:
+    """Slot 0 is the VAE's own device: moved to the front (its first entry), or put there when the list lacks it; the order of the
+    others is kept."""
+    slots = list(slots)
+    if vae_device in slots:
+        slots.remove(vae_device)
+    return [vae_device] + slots
+
+
+def parse_devices(value: Optional[str], vae_device: int, device_count: int, can_access_peer) -> Optional[List[int]]:
+    """The value of --mdtile-devices ("0,1,3" or "all") -> VAEHook.devices, or None (one device).  Repeats are kept (a device may fill
+    several slots); the VAE's device becomes slot 0 (with_vae_device_first).  An index that is no CUDA device makes the whole option void
+    (warning); a device whose memory the VAE's device cannot read (can_access_peer(vae_device, d) false) is dropped (warning); fewer than
+    two slots left give None.  Pure: the caller passes torch.cuda.device_count() and torch.cuda.can_device_access_peer."""
+    if value is None or not str(value).strip():
+        return None
+    value = str(value).strip()
+    if value.lower() == "all":
+        slots = list(range(device_count))
+    else:
+        try:
+            slots = [int(v) for v in value.split(",") if v.strip()]
+        except ValueError:
+            print(f"[Tiled VAE]: --mdtile-devices {value!r} is not a comma-separated list of CUDA indices; the option is ignored")
+            return None
+    bad = [d for d in slots if not 0 <= d < device_count]
+    if bad:
+        print(f"[Tiled VAE]: --mdtile-devices {value!r}: no CUDA device {bad[0]} ({device_count} visible); the option is ignored")
+        return None
+    no_peer = sorted({d for d in slots if d != vae_device and not can_access_peer(vae_device, d)})
+    if no_peer:
+        print(f"[Tiled VAE]: --mdtile-devices: cuda:{vae_device} cannot read the memory of {', '.join(f'cuda:{d}' for d in no_peer)}; "
+              "dropped from the list")
+        slots = [d for d in slots if d not in no_peer]
+    slots = with_vae_device_first(slots, vae_device)
+    return slots if len(slots) > 1 else None
+
+
+def _cmd_line_devices(net) -> Optional[List[int]]:
+    """--mdtile-devices (preload.py) for the hooks of `net` (the VAE's decoder); None when the option is not set."""
+    import modules.shared as shared
+    value = getattr(shared.cmd_opts, "mdtile_devices", None)
+    if not value:
+        return None
+    if not torch.cuda.is_available():
+        print("[Tiled VAE]: --mdtile-devices needs CUDA devices; the option is ignored")
+        return None
+    p = next(net.parameters(), None)
+    dev = p.device if p is not None and p.device.type == "cuda" else torch.device(devices.get_optimal_device())
+    if dev.type != "cuda":
+        return None
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    return parse_devices(value, index, torch.cuda.device_count(), torch.cuda.can_device_access_peer)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 class VAEHook:
 
@@ -102,11 +166,12 @@ class VAEHook:
         # process-per-GPU runs: the rank whose call returns the ASSEMBLED image, as upstream's single tensor (:630-656) -- the other
         # ranks' tile rectangles travel to it in one grouped exchange; None leaves every rank with only its own tiles filled in
         self.gather_to: Optional[int] = None
-        # single-process multi-device decode (what a webui process can use): CUDA device indices, e.g. [0, 1, 2, 3]; the tiles are
-        # dealt to the devices by area, each with its own copy of the packed weights; fast mode only (no collective needed:
-        # the frozen statistics are computed once and copied).  A device may be listed twice (functional runs on one GPU).
+        # one process, several devices (what a webui process can use; preload.py: --mdtile-devices): CUDA device indices, one per SLOT,
+        # e.g. [0, 1, 2, 3].  Slot 0 is the VAE's own device (put in front when the list lacks it); the tiles are dealt to the slots by
+        # area, each slot with its own copy of the packed weights and of the statistics, in every mode (_multi_slot_forward).  A device
+        # may fill several slots (functional runs on one GPU).
         self.devices: Optional[List[int]] = None
-        self._dev_programs = {}
+        self.last_tile_slots: Optional[List[int]] = None    # the slot that decoded each tile in the last call
 
     def __call__(self, x):
         original_device = next(self.net.parameters()).device
@@ -425,98 +490,118 @@ class VAEHook:
             sm, sv, sp = torch.zeros(BG, device=dev), torch.zeros(BG, device=dev), torch.zeros(1, device=dev)
         return sharding.allreduce_stats(sm, sv, sp), False
 
-    # ---- single-process multi-device sweep ---------------------------------------------------------------------------------
-    def _program_on(self, index: int) -> List[Step]:
-        """The task queue with its weights packed on CUDA device `index` (built once per device)."""
-        import copy
-        if index not in self._dev_programs:
-            d = torch.device("cuda", index)
-            src = next(self.net.parameters()).device
-            net = self.net if src == d else copy.deepcopy(self.net).to(d)
-            with torch.cuda.device(d):
-                self._dev_programs[index] = build_task_queue(net, self.is_decoder, self._pack, self.engine)
-        return self._dev_programs[index]
+    # ---- one process, several devices ------------------------------------------------------------------------------------------------
+    def _slots(self, dev) -> Optional[List[int]]:
+        """self.devices with the VAE's own device as slot 0 (with_vae_device_first); None: one device."""
+        dev = torch.device(dev)
+        if not self.devices or dev.type != "cuda":
+            return None
+        slots = with_vae_device_first([int(i) for i in self.devices], dev.index if dev.index is not None else torch.cuda.current_device())
+        return slots if len(slots) > 1 else None
 
-    def _multi_device_sweep(self, z: Tensor, steps0: List[Step], frozen, in_bboxes, out_bboxes, dtype, t0) -> Tensor:
-        """Fast mode on several devices of ONE process: the tiles are dealt to the devices by area (mdtile/sharding.py: deal_tiles, the deal of
-        the process-per-GPU path), each device with its own stream, its own packed weights and a copy of the frozen statistics; launches
-        are asynchronous, so one Python thread keeps all devices busy -- the tiles are issued device by device in rounds (every device's
-        first tile, then every device's second ...), so no device waits for the host to finish another device's list.  The output tiles
-        are disjoint (out_bboxes never overlap): each device crops into its own canvas and its rectangles are copied to the first
-        device at the end (peer copies over xGMI)."""
-        E = self.engine
-        N, _, height, width = z.shape
-        devs = [torch.device("cuda", i) for i in self.devices]
-        norm_idx = [i for i, s in enumerate(steps0) if s.kind == "norm"]
-        norm_ord = {i: k for k, i in enumerate(norm_idx)}
-        per = []
-        for d in devs:
-            with torch.cuda.device(d):
-                steps = self._program_on(d.index)
-                fz = [(v.to(d), m.to(d)) for (v, m) in frozen]
-                coefs = [E.gn_coeffs(m, v, steps[i].norm[0], steps[i].norm[1], steps[i].channels, 32, 1e-6) for i, (v, m) in zip(norm_idx, fz)]
-                per.append(dict(steps=steps, frozen=fz, coefs=coefs, z=z.to(d), result=None, flags=[], mine=[]))
+    def _slot_program(self, index: int) -> List[Step]:
+        """The task queue with its weights packed on CUDA device `index`, for slots 1 and up.  Cached on the VAE module: A1111 makes new
+        hooks for every generation, and a program is a deep copy + re-pack of the whole VAE.  The key holds every parameter's (data_ptr,
+        _version), so an in-place weight load (load_state_dict into the same module: how A1111 swaps a VAE) rebuilds it."""
+        import copy
+        net = self.net
+        key = tuple((p.data_ptr(), p._version) for p in net.parameters())
+        cache = getattr(net, "_mdtile_slot_programs", None)
+        if cache is None:
+            cache = net._mdtile_slot_programs = {}
+        hit = cache.get(index)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        d = torch.device("cuda", index)
+        if next(net.parameters()).device != d:
+            # the copy leaves out what the plugin hangs on the module: the hooks (with their packed programs) and this cache
+            memo = {id(v): None for k, v in vars(net).items() if k in ("forward", "original_forward", "_mdtile_slot_programs")}
+            net = copy.deepcopy(net, memo).to(d)
+        with torch.cuda.device(d):
+            steps = build_task_queue(net, self.is_decoder, self._pack, self.engine)
+        cache[index] = (key, steps)
+        return steps
+
+    def _multi_slot_forward(self, z: Tensor, steps0: List[Step], frozen, all_frozen: bool, in_bboxes, out_bboxes, slots: List[int], dtype,
+                            t0) -> Tensor:
+        """vae_tile_forward on several device slots of ONE process, bit-identical to one device.  The tiles are dealt to the slots by area
+        (mdtile/sharding.py: deal_tiles); each slot runs the one-device sweeps over its tiles with its own program, z and statistics, on its
+        device's current stream, all driven from this thread.  Fast mode: the slots' _sweep_frozen generators are interleaved chunk by chunk.
+        Slow mode / color_fix / fast mode's NaN fallback: _sweep_lockstep over all slots, pooled on slot 0 in the one-device tile order.
+        The slots keep their finished tiles; slot 0's stream waits for the others (events) and reads every tile into the one image in
+        mdtile_vae_assemble (peer reads); one host synchronize of slot 0 at the end, after which the tiles may go."""
         from mdtile import sharding as _sh
-        owner = _sh.deal_tiles(in_bboxes, len(devs))
-        lists = [[i for i in range(len(in_bboxes)) if owner[i] == k] for k in range(len(devs))]
-        issue = [(lst[r], k) for r in range(max(len(lst) for lst in lists)) for k, lst in enumerate(lists) if r < len(lst)]
-        for i, k in issue:
-            if state.interrupted:
-                break
-            L, d = per[k], devs[k]
+        E = self.engine
+        n = len(in_bboxes)
+        devs = [torch.device("cuda", i) for i in slots]
+        dev0 = z.device
+        owner = _sh.deal_tiles(in_bboxes, len(slots))
+        self.last_tile_slots = list(owner)
+        lanes = []                                       # (run, steps, frozen, device) per slot
+        for k, d in enumerate(devs):
             with torch.cuda.device(d):
-                b = in_bboxes[i]
-                x = E.gather_rect(L["z"], b[0], b[2], b[1] - b[0], b[3] - b[2])
-                windows, live_bbox = self._live_plan(L["steps"], in_bboxes[i], out_bboxes[i])
-                x = self._run_tile_rec(L["steps"], x, L["frozen"], L["coefs"], norm_ord, windows)
-                if L["result"] is None:
-                    oh, ow = (height * 8, width * 8) if self.is_decoder else (height // 8, width // 8)
-                    L["result"] = torch.zeros((N, x.shape[1], oh, ow), device=d, dtype=torch.float32)
-                L["flags"].append(torch.isnan(x).all())
-                E.crop_store(x, live_bbox, out_bboxes[i], L["result"], self.is_decoder)
-                L["mine"].append(i)
-        if all(L["result"] is None for L in per):
-            # interrupted before any tile finished: as the single-device path (and upstream, :644-650)
-            if not self.is_decoder:
-                raise RuntimeError("[Tiled VAE]: interrupted before any encoder tile finished")
-            from modules.sd_vae_approx import cheap_approximation
-            return torch.cat([torch.nn.functional.interpolate(cheap_approximation(x).unsqueeze(0), scale_factor=8, mode="nearest-exact")
-                              for x in z], dim=0).to(devs[0], dtype=dtype)
-        if per[0]["result"] is None:      # the first device finished nothing (interrupt): it still hosts the assembled canvas
-            with torch.cuda.device(devs[0]):
-                ref_res = next(L["result"] for L in per if L["result"] is not None)
-                per[0]["result"] = torch.zeros(ref_res.shape, device=devs[0], dtype=torch.float32)
-        out = per[0]["result"]             # interrupted runs return the finished tiles, like upstream
-        bad = False
-        for k, L in enumerate(per):
-            torch.cuda.current_stream(devs[k]).synchronize()
-            bad = bad or (L["flags"] and bool(torch.stack(L["flags"]).any().item()))
-            if k == 0 or L["result"] is None:
-                continue
-            for i in L["mine"]:
-                x1, x2, y1, y2 = out_bboxes[i]
-                out[:, :, y1:y2, x1:x2].copy_(L["result"][:, :, y1:y2, x1:x2])
-        if bad:
-            devices.test_for_nans(torch.full((1,), float("nan")), "vae")
+                steps = steps0 if k == 0 else self._slot_program(d.index)
+                fz = frozen if (k == 0 or frozen is None) else [(v.to(d), m.to(d)) for v, m in frozen]
+                run = VAEHook._Run(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, [i for i in range(n) if owner[i] == k], keep_tiles=True)
+            lanes.append((run, steps, fz, d))
+        if all_frozen:
+            done = object()
+            pending = [(d, self._sweep_frozen(run, steps, fz)) for run, steps, fz, d in lanes]
+            while pending:                               # one chunk of every slot per round: no device waits while another's list is issued
+                still = []
+                for d, gen in pending:
+                    with torch.cuda.device(d):
+                        if next(gen, done) is not done:
+                            still.append((d, gen))
+                pending = still
+        else:
+            self._sweep_lockstep(lanes)
+        runs = [lane[0] for lane in lanes]
+        s0 = torch.cuda.current_stream(dev0)
+        for run, _, _, d in lanes[1:]:
+            if d != dev0:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(d))
+                s0.wait_event(ev)
+        kept = [t for run in runs for t in run.kept]
+        with torch.cuda.device(dev0):
+            result = None
+            if kept:
+                N, _, height, width = z.shape
+                oh, ow = (height * 8, width * 8) if self.is_decoder else (height // 8, width // 8)
+                result = torch.zeros((N, kept[0][0].shape[1], oh, ow), device=dev0, dtype=torch.float32)
+                E.vae_assemble(kept, result, self.is_decoder)
+            flags = [torch.stack(run.nan_flags).any().to(dev0) for run in runs if run.nan_flags]
+            if flags and bool(torch.stack(flags).any().item()):
+                devices.test_for_nans(torch.full((1,), float("nan")), "vae")     # the host's NansException (or not: --disable-nan-check)
+            if result is None:                           # interrupted before any tile finished (upstream :644-650)
+                if not self.is_decoder:
+                    raise RuntimeError("[Tiled VAE]: interrupted before any encoder tile finished")
+                from modules.sd_vae_approx import cheap_approximation
+                return torch.cat([torch.nn.functional.interpolate(cheap_approximation(x).unsqueeze(0), scale_factor=8, mode="nearest-exact")
+                                  for x in z], dim=0).to(dev0, dtype=dtype)
+            torch.cuda.synchronize(dev0)                 # the assembly has read every slot's tiles: they may go now
+        del kept, runs, lanes
         self.last_seconds = time() - t0
-        torch.cuda.synchronize(devs[0])
-        print(f"[Tiled VAE]: Done in {time() - t0:.3f}s on {len(devs)} devices")
-        return out.to(dtype)
+        print(f"[Tiled VAE]: Done in {self.last_seconds:.3f}s on {len(slots)} device slots")
+        return result.to(dtype)
 
     # ---- the tile sweep (upstream vae_tile_forward, :507-656) ------------------------------------------------------------------------
-    # vae_tile_forward is the driver: split, estimator, deal the tiles, run ONE of three sweeps, assemble.
+    # vae_tile_forward is the driver: split, estimator, deal the tiles, run ONE of two sweeps, assemble.
     #   _sweep_frozen      every norm frozen (fast mode): each tile runs start to finish on its own -- stacked by shape on the record path
     #   _sweep_lockstep    slow mode / color_fix: all tiles advance from norm to norm, statistics pooled at each one
-    #   _multi_device_sweep  fast mode on several devices of one process (above)
+    # With several device slots (_multi_slot_forward, above) each slot runs the same sweeps over its own tiles.
     class _Run:
-        """State of one vae_tile_forward call shared by the sweeps: this rank's tiles, the result canvas, the NaN flags, the live windows."""
+        """State of one vae_tile_forward call shared by the sweeps: this rank's (slot's) tiles, the result canvas, the NaN flags, the live
+        windows.  keep_tiles (device slots): finished tiles are kept for mdtile_vae_assemble instead of being cropped into a canvas."""
 
-        def __init__(self, hook, z, in_bboxes, out_bboxes, mine):
+        def __init__(self, hook, z, in_bboxes, out_bboxes, mine, keep_tiles: bool = False):
             self.hook, self.z, self.in_bboxes, self.out_bboxes, self.mine = hook, z, in_bboxes, out_bboxes, list(mine)
             E = hook.engine
             sel = set(mine)
             self.tiles = {i: TileState(E.gather_rect(z, b[0], b[2], b[1] - b[0], b[3] - b[2])) for i, b in enumerate(in_bboxes) if i in sel}
             self.result = None
+            self.kept = [] if keep_tiles else None      # (tile, its input bbox, output bbox) of every finished tile
             self.nan_flags = []
             self.live = {}          # tile -> (windows of its upsample convs, the input bbox of what is left of it): live_windows
             self.interrupted = False
@@ -525,6 +610,11 @@ class VAEHook:
             """crop_valid_region + `result[...] = tile` of one finished tile (upstream :630-632); the canvas appears with the first one."""
             hook, E, z = self.hook, self.hook.engine, self.z
             x = self.tiles[i].x
+            if self.kept is not None:
+                self.nan_flags.append(torch.isnan(x).all())
+                self.kept.append((x, self.live[i][1] if i in self.live else self.in_bboxes[i], self.out_bboxes[i]))
+                self.tiles[i] = None
+                return
             if self.result is None:
                 N, _, height, width = z.shape
                 oh, ow = (height * 8, width * 8) if hook.is_decoder else (height // 8, width // 8)
@@ -533,8 +623,9 @@ class VAEHook:
             E.crop_store(x, self.live[i][1] if i in self.live else self.in_bboxes[i], self.out_bboxes[i], self.result, hook.is_decoder)
             self.tiles[i] = None
 
-    def _sweep_frozen(self, run: "VAEHook._Run", steps: List[Step], frozen) -> None:
-        """Every norm is already resolved: each tile runs start to finish on its own (upstream: one sweep, :578-642)."""
+    def _sweep_frozen(self, run: "VAEHook._Run", steps: List[Step], frozen):
+        """Every norm is already resolved: each tile runs start to finish on its own (upstream: one sweep, :578-642).  A generator that yields
+        after every chunk (stack of tiles, or single tile) it has issued: one device drains it, device slots interleave theirs."""
         E, z, tiles, mine = self.engine, run.z, run.tiles, run.mine
         N, dev = z.shape[0], z.device
         use_rec = REC_PATH and hasattr(E, "rec_from_f32")
@@ -609,6 +700,7 @@ class VAEHook:
                         tb = 1
                         continue
                     c0 += tb
+                    yield chunk
             return
         for i in mine:
             if state.interrupted:
@@ -618,6 +710,7 @@ class VAEHook:
             if use_rec:
                 st.x = self._run_tile_rec(steps, st.x, frozen, coefs, norm_ord, run.live[i][0])
                 run.finish(i)
+                yield [i]
                 continue
             while True:
                 self._run_until_norm(steps, st)
@@ -626,48 +719,84 @@ class VAEHook:
                 self._apply_norm(steps, st, *frozen[k])
                 k += 1
             run.finish(i)
+            yield [i]
 
-    def _sweep_lockstep(self, run: "VAEHook._Run", steps: List[Step], frozen) -> None:
+    @staticmethod
+    def _lockstep_order(lanes, forward: bool):
+        """(lane, tile) in the order _sweep_lockstep advances them to the next norm: every slot walks its tiles forward or reversed (the zig-zag);
+        several slots take turns, one tile each, so that no device waits while another's tiles are issued."""
+        orders = [(lane, () if lane[0].interrupted else lane[0].mine if forward else list(reversed(lane[0].mine))) for lane in lanes]
+        for r in range(max((len(o) for _, o in orders), default=0)):
+            for lane, o in orders:
+                if r < len(o):
+                    yield lane, o[r]
+
+    def _sweep_lockstep(self, lanes) -> None:
         """Slow mode: all tiles advance in lockstep from norm to norm, the statistics pooled over the tiles (and ranks) at each one
-        (upstream :289-361, :578-642 zig-zag); semi-fast (color_fix): the first len(frozen) norms use the frozen statistics instead."""
-        tiles, mine = run.tiles, run.mine
-        world = self.shard[1]
+        (upstream :289-361, :578-642 zig-zag); semi-fast (color_fix): the first len(frozen) norms use the frozen statistics instead.
+        lanes: [(run, steps, frozen, device)], one per device slot (device None: one device, the current one).  With several slots each
+        tile's (var, mean) rows go to slot 0 and are pooled in the order the one-device sweep visits the tiles, and the pooled pair goes
+        back to every slot: the same rows in the same order, the same bits."""
+        E, world = self.engine, self.shard[1]
+        dev0 = lanes[0][0].z.device
+        n_frozen = 0 if lanes[0][2] is None else len(lanes[0][2])
         forward, k_norm = True, 0
         while True:
-            use_frozen = frozen is not None and k_norm < len(frozen)
-            gp = GroupNormParam(self.engine)
-            for i in (() if run.interrupted else mine if forward else reversed(mine)):
+            use_frozen = k_norm < n_frozen
+            gp = GroupNormParam(E)
+            rows = {}                                    # several slots: tile -> its (var, mean, pixels) on its slot's device
+            for (run, steps, _, d), i in self._lockstep_order(lanes, forward):
                 if state.interrupted:
-                    run.interrupted = True
+                    for lane in lanes:
+                        lane[0].interrupted = True
                     break
-                self._run_until_norm(steps, tiles[i], want_stats=not use_frozen)
-                if tiles[i].pc < len(steps) and not use_frozen:
-                    gp.add_tile(tiles[i].x, tiles[i].stats)
-            if run.interrupted and world == 1:
+                st = run.tiles[i]
+                with _on_device(d):
+                    self._run_until_norm(steps, st, want_stats=not use_frozen)
+                    if st.pc < len(steps) and not use_frozen:
+                        if len(lanes) == 1:
+                            gp.add_tile(st.x, st.stats)
+                        else:
+                            rows[i] = (*(st.stats if st.stats is not None else E.gn_stats(st.x, 32)), st.x.shape[2] * st.x.shape[3])
+            if lanes[0][0].interrupted and world == 1:
                 return
             # several ranks: an interrupted rank runs no more tiles but keeps walking the norms to the next POOLED barrier, where the
             # `head` exchange tells every rank (see _pooled_across_ranks) -- all of them leave this loop at the same barrier
             if use_frozen:
                 # a frozen norm is no barrier upstream (the tile runs straight through it): no pooling, no collective,
                 # no change of the zig-zag direction.  A later pooled norm always exists in this branch.
-                for i in (() if run.interrupted else mine):
-                    self._apply_norm(steps, tiles[i], *frozen[k_norm])
+                for run, steps, fz, d in lanes:
+                    with _on_device(d):
+                        for i in (() if run.interrupted else run.mine):
+                            self._apply_norm(steps, run.tiles[i], *fz[k_norm])
                 k_norm += 1
                 continue
+            # (copied only now: a copy between two devices makes each one's stream wait for the other's, which inside the loop above would
+            # tie every slot to the tiles issued before it on slot 0)
+            for i in (sorted(rows) if forward else sorted(rows, reverse=True)):
+                var, mean, px = rows[i]
+                gp.add_stats(var.to(dev0), mean.to(dev0), px)
             if world == 1:
-                pooled = gp.summary()
+                with _on_device(lanes[0][3]):
+                    pooled = gp.summary()
             else:
-                pooled, any_interrupted = self._pooled_across_ranks(gp, steps, run.z.device, run.interrupted)
+                run = lanes[0][0]
+                pooled, any_interrupted = self._pooled_across_ranks(gp, lanes[0][1], run.z.device, run.interrupted)
                 if any_interrupted:
                     run.interrupted = True
                     return
             k_norm += 1
+            for run, steps, _, d in lanes:
+                with _on_device(d):
+                    if pooled is None:
+                        for i in run.mine:
+                            run.finish(i)
+                        continue
+                    var, mean = pooled if d is None or d == dev0 else (pooled[0].to(d), pooled[1].to(d))
+                    for i in run.mine:
+                        self._apply_norm(steps, run.tiles[i], var, mean)
             if pooled is None:
-                for i in mine:
-                    run.finish(i)
                 return
-            for i in mine:
-                self._apply_norm(steps, tiles[i], *pooled)
             forward = not forward
 
     @torch.no_grad()
@@ -685,6 +814,9 @@ class VAEHook:
         in_bboxes, out_bboxes = self.split_tiles(height, width)
         steps = self.program()
         rank, world = self.shard
+        slots = self._slots(dev)
+        if slots and world > 1:
+            raise RuntimeError("[Tiled VAE]: VAEHook.devices (one process, several devices) and a process-per-GPU shard cannot be combined")
 
         frozen = None
         if self.fast_mode:
@@ -697,19 +829,21 @@ class VAEHook:
             else:
                 frozen = self.estimate_group_norm(zs, steps)
         all_frozen = frozen is not None and len(frozen) == sum(1 for s in steps if s.kind == "norm")
-        if all_frozen and self.devices and len(self.devices) > 1 and dev.type == "cuda":
-            return self._multi_device_sweep(z, steps, frozen, in_bboxes, out_bboxes, dtype, t0)
+        if slots:
+            return self._multi_slot_forward(z, steps, frozen, all_frozen, in_bboxes, out_bboxes, slots, dtype, t0)
 
         owner = [0] * len(in_bboxes)
         if world > 1:
             from mdtile import sharding as _sh
             owner = _sh.deal_tiles(in_bboxes, world)      # by tile area (mdtile/sharding.py: deal_tiles), the same list on every rank
         mine = [i for i in range(len(in_bboxes)) if owner[i] == rank] if world > 1 else list(range(len(in_bboxes)))
+        self.last_tile_slots = [0] * len(in_bboxes) if world == 1 else None
         run = VAEHook._Run(self, z, in_bboxes, out_bboxes, mine)
         if all_frozen:
-            self._sweep_frozen(run, steps, frozen)
+            for _ in self._sweep_frozen(run, steps, frozen):
+                pass
         else:
-            self._sweep_lockstep(run, steps, frozen)
+            self._sweep_lockstep([(run, steps, frozen, None)])
         return self._assemble(run, owner, dtype, t0)
 
     def _assemble(self, run: "VAEHook._Run", owner, dtype, t0) -> Tensor:
@@ -799,13 +933,16 @@ class Script(scripts.Script):
         if not hasattr(decoder, "original_forward"):
             decoder.original_forward = decoder.forward
         self.hooked = True
+        slots = _cmd_line_devices(decoder)
         decoder.forward = VAEHook(decoder, decoder_tile_size, is_decoder=True, fast_decoder=fast_decoder,
                                   fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)
+        decoder.forward.devices = None if slots is None else list(slots)
         encoder = vae.encoder
         if not hasattr(encoder, "original_forward"):
             encoder.original_forward = encoder.forward
         encoder.forward = VAEHook(encoder, encoder_tile_size, is_decoder=False, fast_decoder=fast_decoder,
                                   fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)
+        encoder.forward.devices = None if slots is None else list(slots)
 
     def postprocess(self, p, processed, enabled: bool, *args):
         if not enabled:

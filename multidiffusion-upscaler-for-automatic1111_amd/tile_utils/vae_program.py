@@ -186,9 +186,13 @@ class GroupNormParam:
     def add_tile(self, tile: Tensor, stats=None):
         """stats: (var, mean) of `tile` when its producer has already left them (TileState.stats); else one pass over the tile."""
         var, mean = stats if stats is not None else self.engine.gn_stats(tile, 32)
+        self.add_stats(var, mean, tile.shape[2] * tile.shape[3])
+
+    def add_stats(self, var: Tensor, mean: Tensor, pixels: int):
+        """The (var, mean) rows of a tile of `pixels` px, computed elsewhere (another device slot)."""
         self.var_list.append(var)
         self.mean_list.append(mean)
-        self.pixel_list.append(tile.shape[2] * tile.shape[3])
+        self.pixel_list.append(pixels)
 
     def summary(self) -> Optional[Tuple[Tensor, Tensor]]:
         if not self.var_list:

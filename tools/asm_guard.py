@@ -15,6 +15,7 @@ device assembly and checks the emitted instruction stream instead:
     * MFMA counts per unrolled trip match the source (conv: 36 half-steps x 12; upconv: 24 combo-steps x 12; attention: 24 / slab)
     * with --one-term: the one-term forms of MDTILE_PRECISION_BF16 (k_conv3x3_rec1t, k_upconv_rec1t, their _st forms, k_conv3x3_rec2_1t, k_upconv_rec2_1t,
       k_conv1x1_stream1t, k_attn_bf16x1) keep their three-term twins' DMA count and barrier waits exactly; their MFMA multiples are a third
+    * k_vae_assemble (csrc/vae_assemble.hip): no packed-fp32 instruction with op_sel, 16-byte loads and stores present
 usage: python tools/asm_guard.py [--one-term] [--probes]   (exit code 0 = ok; prints one line per kernel)      -- also run by tests/test_host_abi.py
        (--one-term adds the one-term kernels; mdtile/build.py runs the guard with it, tests/test_precision_bf16_host.py checks them)
 """
@@ -184,6 +185,24 @@ def main() -> int:
         print(f"{hit[0][:70]:70s} {len(ins):6d} instr  {len(pk):3d} packed-fp32 instructions, {len(bad)} with op_sel  {'ok' if pk and not bad else 'FAIL'}")
         if not pk or bad:
             errs.append(f"{hit[0]}: {len(bad)} packed instructions carry op_sel (first: {bad[:1]})")
+    # the tile assembly (csrc/vae_assemble.hip: k_vae_assemble) runs behind the sweeps of every device slot, beside their MFMA waves: none of its
+    # packed-fp32 instructions may carry op_sel either.  A copy needs no packed arithmetic, so unlike conv_in's rule this one
+    # asks for none; it asks for the 16-byte loads and stores of the aligned rows instead.  (Its line says "clean", not "ok": the tests count
+    # the DMA-protocol kernels by their "ok".)
+    va = kernels(device_asm(os.path.join(CSRC, "vae_assemble.hip")))
+    hit = [n for n in va if "k_vae_assemble" in n]
+    if not hit:
+        errs.append("kernel k_vae_assemble not found in the device assembly")
+    else:
+        ins = va[hit[0]]
+        bad = [l for l in ins if l.startswith("v_pk_") and re.search(r"op_sel:\[", l)]
+        n_ld = sum(1 for l in ins if l.startswith("global_load_dwordx4"))
+        n_st = sum(1 for l in ins if l.startswith("global_store_dwordx4"))
+        good = not bad and n_ld > 0 and n_st > 0
+        print(f"{hit[0][:70]:70s} {len(ins):6d} instr  {len(bad)} packed-fp32 instructions with op_sel, {n_ld} / {n_st} 16-byte loads / stores  "
+              f"{'clean' if good else 'FAIL'}")
+        if not good:
+            errs.append(f"{hit[0]}: {len(bad)} packed instructions carry op_sel (first: {bad[:1]}), {n_ld} / {n_st} 16-byte loads / stores")
     for e in errs:
         print("ASM GUARD:", e)
     return 1 if errs else 0

@@ -79,9 +79,9 @@ def custom_group_norm(input, num_groups, mean, var, weight=None, bias=None, eps=
     return mdtile.gn_apply(input, mean, var, weight, bias, num_groups, eps, silu)
 
 
-def _on_device(d):
-    """torch.cuda.device(d), or nothing for d None (one device: the current one)."""
-    return contextlib.nullcontext() if d is None else torch.cuda.device(d)
+def _on_device(d: torch.device):
+    """torch.cuda.device(d), or nothing off the GPU (the CPU tests' torch doubles of the engine)."""
+    return torch.cuda.device(d) if d.type == "cuda" else contextlib.nullcontext()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -168,8 +168,8 @@ class VAEHook:
         self.gather_to: Optional[int] = None
         # one process, several devices (what a webui process can use; preload.py: --mdtile-devices): CUDA device indices, one per SLOT,
         # e.g. [0, 1, 2, 3].  Slot 0 is the VAE's own device (put in front when the list lacks it); the tiles are dealt to the slots by
-        # area, each slot with its own copy of the packed weights and of the statistics, in every mode (_multi_slot_forward).  A device
-        # may fill several slots (functional runs on one GPU).
+        # area, each slot with its own copy of the packed weights and of the statistics, in every mode (vae_tile_forward: one _Lane per
+        # slot).  A device may fill several slots (functional runs on one GPU).
         self.devices: Optional[List[int]] = None
         self.last_tile_slots: Optional[List[int]] = None    # the slot that decoded each tile in the last call
 
@@ -195,6 +195,11 @@ class VAEHook:
     def split_tiles(self, h, w):
         return self.engine.vae_split_tiles(h, w, self.tile_size, self.is_decoder)
 
+    def _out_shape(self, z: Tensor, channels: int) -> Tuple[int, int, int, int]:
+        """The result's shape for the input z: 8x its size (decoder) or an eighth of it (encoder)."""
+        N, _, height, width = z.shape
+        return (N, channels, height * 8, width * 8) if self.is_decoder else (N, channels, height // 8, width // 8)
+
     # ---- program ------------------------------------------------------------------------------------------------------
     def program(self) -> List[Step]:
         dev = next(self.net.parameters()).device
@@ -214,7 +219,7 @@ class VAEHook:
     def _run_until_norm(self, steps: List[Step], st: TileState, want_stats: bool = False):
         """Advance one tile to its next GroupNorm (exclusive) or to the end.
         want_stats (slow mode, the norm ahead is pooled): the conv that produces the norm's input also leaves its (var, mean) in st.stats
-        where a kernel does that in its epilogue (PackedConv.leaves_stats) -- GroupNormParam.add_tile then needs no pass over the tile."""
+        where a kernel does that in its epilogue (PackedConv.leaves_stats) -- the pooling then needs no pass over the tile."""
         while st.pc < len(steps):
             s = steps[st.pc]
             if s.kind == "norm":
@@ -281,7 +286,7 @@ class VAEHook:
         conv_out (cout < 32) behind a pooled norm_out: no hand-over kernel applies a norm for so few couts, so the alternative is a norm pass
         (1R + 1W) + the exact-fp32 conv -- 3.8 ms per 2224^2 tile against 1.9 ms for conversion pass + narrow record conv (profiles/r5q:
         kernel_stats_slow.csv, 61 ms of a slow-mode 8K decode)."""
-        if not (SLOW_REC and REC_PATH and hasattr(self.engine, "rec_from_f32") and self._takes_rec(s)):
+        if not (SLOW_REC and self._takes_rec(s)):
             return False
         c = s.conv
         return bool(s.upsample or (getattr(c, "cin", 0) >= 512 and getattr(c, "cout", 0) >= 512) or 0 < getattr(c, "cout", 0) < 32)
@@ -306,10 +311,10 @@ class VAEHook:
         return tb
 
     # ---- fast mode, every norm frozen: record-image hand-over between the 3x3 convs ----------------------------------
-    @staticmethod
-    def _takes_rec(step: Step) -> bool:
+    def _takes_rec(self, step: Step) -> bool:
+        """The conv of `step` runs on the record kernels: REC_PATH on, an engine with record images, a conv they take."""
         fn = getattr(step.conv, "takes_rec", None)
-        return bool(fn and not step.downsample and fn(step.upsample))
+        return bool(REC_PATH and hasattr(self.engine, "rec_from_f32") and fn and not step.downsample and fn(step.upsample))
 
     def _demand(self, steps: List[Step], i: int):
         """Forms in which the value produced by steps[i] has to exist: (fp32 NCHW?, record image: None | "raw" | index of the
@@ -329,20 +334,16 @@ class VAEHook:
             return need_f32, "raw"
         return True, None
 
-    def _run_tile_rec(self, steps: List[Step], x: Tensor, frozen, coefs, norm_ord, windows=None, first: int = 0, last: Optional[int] = None,
-                      xrec=None):
+    def _run_tile_rec(self, steps: List[Step], x: Tensor, frozen, coefs, norm_ord, windows=None):
         """One tile start to finish with frozen statistics (upstream's single sweep, :578-642).  A 3x3 conv that the record
         kernels take reads its input as a record image; whoever produces that input writes it in that form -- the previous
-        record conv's epilogue (norm + SiLU + split fused), or mdtile_rec_from_f32 behind conv_in / attention.
-        windows (live_windows): the upsample convs listed there compute only that window of their input plane.
-        first / last / xrec: run steps[first:last] only; a sweep cut in front of an upsample conv (between two resblocks: no residual is
-        pending there) hands over (x, xrec) -- returned instead of x when `last` is given -- and is resumed with them."""
+        record conv's epilogue (norm + SiLU + split fused), or mdtile_rec_from_f32 behind conv_in / attention.  Where they take
+        none (_takes_rec), a norm is applied by gn_apply or rides on the next conv as its (a, s) coefficients, as in _apply_norm.
+        windows (live_windows): the upsample convs listed there compute only that window of their input plane."""
         E = self.engine
         res: List[Tensor] = []
-        pre = None
-        stop = len(steps) if last is None else last
-        for i in range(first, stop):
-            s = steps[i]
+        pre = xrec = None
+        for i, s in enumerate(steps):
             if s.kind == "store_res":
                 res.append(x if s.conv is None else s.conv(x))
             elif s.kind == "norm":
@@ -380,9 +381,6 @@ class VAEHook:
                 x, xrec = s.attn(x, res.pop()), None
             elif s.kind == "tanh":
                 x = E.tanh(x)
-        if last is not None:
-            assert not res and pre is None, "a sweep can only be cut between two resblocks"
-            return x, xrec
         return x
 
     @staticmethod
@@ -466,7 +464,7 @@ class VAEHook:
             return None
         return frozen
 
-    def _pooled_across_ranks(self, gp: "GroupNormParam", steps, dev, interrupted: bool = False):
+    def _pooled_across_ranks(self, gp: "GroupNormParam", dev, interrupted: bool = False):
         """Slow mode on several GPUs: all-reduce(sum) of [sum px*mean, sum px*var, sum px] (2*B*32+1 floats) per barrier, on the
         job's data plane (the engine's RCCL communicator when the process has one, mdtile/sharding.py).
         Returns (pooled or None, any rank interrupted).  The interrupt rides in the `head` exchange every rank enters at every pooled
@@ -522,119 +520,58 @@ class VAEHook:
         cache[index] = (key, steps)
         return steps
 
-    def _multi_slot_forward(self, z: Tensor, steps0: List[Step], frozen, all_frozen: bool, in_bboxes, out_bboxes, slots: List[int], dtype,
-                            t0) -> Tensor:
-        """vae_tile_forward on several device slots of ONE process, bit-identical to one device.  The tiles are dealt to the slots by area
-        (mdtile/sharding.py: deal_tiles); each slot runs the one-device sweeps over its tiles with its own program, z and statistics, on its
-        device's current stream, all driven from this thread.  Fast mode: the slots' _sweep_frozen generators are interleaved chunk by chunk.
-        Slow mode / color_fix / fast mode's NaN fallback: _sweep_lockstep over all slots, pooled on slot 0 in the one-device tile order.
-        The slots keep their finished tiles; slot 0's stream waits for the others (events) and reads every tile into the one image in
-        mdtile_vae_assemble (peer reads); one host synchronize of slot 0 at the end, after which the tiles may go."""
-        from mdtile import sharding as _sh
-        E = self.engine
-        n = len(in_bboxes)
-        devs = [torch.device("cuda", i) for i in slots]
-        dev0 = z.device
-        owner = _sh.deal_tiles(in_bboxes, len(slots))
-        self.last_tile_slots = list(owner)
-        lanes = []                                       # (run, steps, frozen, device) per slot
-        for k, d in enumerate(devs):
-            with torch.cuda.device(d):
-                steps = steps0 if k == 0 else self._slot_program(d.index)
-                fz = frozen if (k == 0 or frozen is None) else [(v.to(d), m.to(d)) for v, m in frozen]
-                run = VAEHook._Run(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, [i for i in range(n) if owner[i] == k], keep_tiles=True)
-            lanes.append((run, steps, fz, d))
-        if all_frozen:
-            done = object()
-            pending = [(d, self._sweep_frozen(run, steps, fz)) for run, steps, fz, d in lanes]
-            while pending:                               # one chunk of every slot per round: no device waits while another's list is issued
-                still = []
-                for d, gen in pending:
-                    with torch.cuda.device(d):
-                        if next(gen, done) is not done:
-                            still.append((d, gen))
-                pending = still
-        else:
-            self._sweep_lockstep(lanes)
-        runs = [lane[0] for lane in lanes]
-        s0 = torch.cuda.current_stream(dev0)
-        for run, _, _, d in lanes[1:]:
-            if d != dev0:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(d))
-                s0.wait_event(ev)
-        kept = [t for run in runs for t in run.kept]
-        with torch.cuda.device(dev0):
-            result = None
-            if kept:
-                N, _, height, width = z.shape
-                oh, ow = (height * 8, width * 8) if self.is_decoder else (height // 8, width // 8)
-                result = torch.zeros((N, kept[0][0].shape[1], oh, ow), device=dev0, dtype=torch.float32)
-                E.vae_assemble(kept, result, self.is_decoder)
-            flags = [torch.stack(run.nan_flags).any().to(dev0) for run in runs if run.nan_flags]
-            if flags and bool(torch.stack(flags).any().item()):
-                devices.test_for_nans(torch.full((1,), float("nan")), "vae")     # the host's NansException (or not: --disable-nan-check)
-            if result is None:                           # interrupted before any tile finished (upstream :644-650)
-                if not self.is_decoder:
-                    raise RuntimeError("[Tiled VAE]: interrupted before any encoder tile finished")
-                from modules.sd_vae_approx import cheap_approximation
-                return torch.cat([torch.nn.functional.interpolate(cheap_approximation(x).unsqueeze(0), scale_factor=8, mode="nearest-exact")
-                                  for x in z], dim=0).to(dev0, dtype=dtype)
-            torch.cuda.synchronize(dev0)                 # the assembly has read every slot's tiles: they may go now
-        del kept, runs, lanes
-        self.last_seconds = time() - t0
-        print(f"[Tiled VAE]: Done in {self.last_seconds:.3f}s on {len(slots)} device slots")
-        return result.to(dtype)
-
     # ---- the tile sweep (upstream vae_tile_forward, :507-656) ------------------------------------------------------------------------
-    # vae_tile_forward is the driver: split, estimator, deal the tiles, run ONE of two sweeps, assemble.
+    # vae_tile_forward is the ONE driver: split, estimator, deal the tiles to lanes (one for one device or a rank, one per device slot),
+    # run ONE of two sweeps over the lanes, then one tail (_collect):
     #   _sweep_frozen      every norm frozen (fast mode): each tile runs start to finish on its own -- stacked by shape on the record path
     #   _sweep_lockstep    slow mode / color_fix: all tiles advance from norm to norm, statistics pooled at each one
-    # With several device slots (_multi_slot_forward, above) each slot runs the same sweeps over its own tiles.
-    class _Run:
-        """State of one vae_tile_forward call shared by the sweeps: this rank's (slot's) tiles, the result canvas, the NaN flags, the live
-        windows.  keep_tiles (device slots): finished tiles are kept for mdtile_vae_assemble instead of being cropped into a canvas."""
+    class _Lane:
+        """The tiles of one vae_tile_forward call that one device sweeps -- all of them (one device), this rank's (VAEHook.shard) or one
+        device slot's (VAEHook.devices) -- with that device's program, input and frozen statistics, and what the sweeps leave: the tiles'
+        state, their live windows, the NaN flags, the interrupt.  keep_tiles (several lanes): finished tiles are kept for
+        mdtile_vae_assemble instead of being cropped into the lane's canvas."""
 
-        def __init__(self, hook, z, in_bboxes, out_bboxes, mine, keep_tiles: bool = False):
-            self.hook, self.z, self.in_bboxes, self.out_bboxes, self.mine = hook, z, in_bboxes, out_bboxes, list(mine)
-            E = hook.engine
-            sel = set(mine)
-            self.tiles = {i: TileState(E.gather_rect(z, b[0], b[2], b[1] - b[0], b[3] - b[2])) for i, b in enumerate(in_bboxes) if i in sel}
+        def __init__(self, hook, z, in_bboxes, out_bboxes, mine: List[int], steps: List[Step], frozen, keep_tiles: bool):
+            self.hook, self.z, self.in_bboxes, self.out_bboxes, self.mine = hook, z, in_bboxes, out_bboxes, mine
+            self.steps, self.frozen, self.device = steps, frozen, z.device
+            self.tiles = {i: TileState(self.gather(i)) for i in mine}
             self.result = None
             self.kept = [] if keep_tiles else None      # (tile, its input bbox, output bbox) of every finished tile
             self.nan_flags = []
             self.live = {}          # tile -> (windows of its upsample convs, the input bbox of what is left of it): live_windows
             self.interrupted = False
 
+        def gather(self, i: int) -> Tensor:
+            """The input of tile i, cut out of z."""
+            x1, x2, y1, y2 = self.in_bboxes[i]
+            return self.hook.engine.gather_rect(self.z, x1, y1, x2 - x1, y2 - y1)
+
         def finish(self, i: int):
-            """crop_valid_region + `result[...] = tile` of one finished tile (upstream :630-632); the canvas appears with the first one."""
-            hook, E, z = self.hook, self.hook.engine, self.z
-            x = self.tiles[i].x
-            if self.kept is not None:
-                self.nan_flags.append(torch.isnan(x).all())
-                self.kept.append((x, self.live[i][1] if i in self.live else self.in_bboxes[i], self.out_bboxes[i]))
-                self.tiles[i] = None
-                return
-            if self.result is None:
-                N, _, height, width = z.shape
-                oh, ow = (height * 8, width * 8) if hook.is_decoder else (height // 8, width // 8)
-                self.result = torch.zeros((N, x.shape[1], oh, ow), device=z.device, dtype=torch.float32)
-            self.nan_flags.append(torch.isnan(x).all())       # upstream tests every tile (:626); here ONE host read per decode
-            E.crop_store(x, self.live[i][1] if i in self.live else self.in_bboxes[i], self.out_bboxes[i], self.result, hook.is_decoder)
+            """crop_valid_region + `result[...] = tile` of one finished tile (upstream :630-632; the canvas appears with the first one), or
+            the tile kept for the assembly."""
+            hook, x = self.hook, self.tiles[i].x
+            in_bbox = self.live[i][1] if i in self.live else self.in_bboxes[i]
+            if self.kept is None and self.result is None:
+                self.result = torch.zeros(hook._out_shape(self.z, x.shape[1]), device=self.device, dtype=torch.float32)
+            self.nan_flags.append(torch.isnan(x).all())       # upstream tests every tile (:626); here ONE host read per call
+            if self.kept is None:
+                hook.engine.crop_store(x, in_bbox, self.out_bboxes[i], self.result, hook.is_decoder)
+            else:
+                self.kept.append((x, in_bbox, self.out_bboxes[i]))
             self.tiles[i] = None
 
-    def _sweep_frozen(self, run: "VAEHook._Run", steps: List[Step], frozen):
+    def _sweep_frozen(self, lane: "VAEHook._Lane"):
         """Every norm is already resolved: each tile runs start to finish on its own (upstream: one sweep, :578-642).  A generator that yields
-        after every chunk (stack of tiles, or single tile) it has issued: one device drains it, device slots interleave theirs."""
-        E, z, tiles, mine = self.engine, run.z, run.tiles, run.mine
+        after every chunk (stack of tiles, or single tile) it has issued: vae_tile_forward drains the lanes' generators in turns."""
+        E, z, tiles, steps, frozen = self.engine, lane.z, lane.tiles, lane.steps, lane.frozen
         N, dev = z.shape[0], z.device
         use_rec = REC_PATH and hasattr(E, "rec_from_f32")
+        norm_ord = {i: k for k, i in enumerate(i for i, s in enumerate(steps) if s.kind == "norm")}
+        coefs = [E.gn_coeffs(mean, var, steps[i].norm[0], steps[i].norm[1], steps[i].channels, 32, 1e-6)
+                 for i, (var, mean) in zip(norm_ord, frozen)]
         if use_rec:
-            norm_ord = {i: k for k, i in enumerate(i for i, s in enumerate(steps) if s.kind == "norm")}
-            coefs = [E.gn_coeffs(mean, var, steps[i].norm[0], steps[i].norm[1], steps[i].channels, 32, 1e-6)
-                     for i, (var, mean) in zip(norm_ord, frozen)]
-            for i in mine:
-                run.live[i] = self._live_plan(steps, run.in_bboxes[i], run.out_bboxes[i])
+            for i in lane.mine:
+                lane.live[i] = self._live_plan(steps, lane.in_bboxes[i], lane.out_bboxes[i])
         if use_rec and TILE_BATCH > 1:
             # Tiles of one shape go through the sweep TOGETHER (stacked along the batch axis, TILE_BATCH at a time).  Upstream
             # walks them one by one (:578-642); with frozen statistics they are independent, so the result is the same -- but
@@ -654,8 +591,7 @@ class VAEHook:
             def regather(chunk):                 # inputs that were folded into a stacked copy: cut them out of z again
                 for i in chunk:                  # (tiles of the chunk that already FINISHED -- an OOM inside finish() -- are None: left alone)
                     if tiles[i] is not None:
-                        b = run.in_bboxes[i]
-                        tiles[i].x = E.gather_rect(z, b[0], b[2], b[1] - b[0], b[3] - b[2])
+                        tiles[i].x = lane.gather(i)
 
             def run_stack(chunk):
                 T = len(chunk)
@@ -664,17 +600,17 @@ class VAEHook:
                 if T > 1:
                     for i in chunk:
                         tiles[i].x = None          # the stacked copy is the live one
-                w0 = run.live[chunk[0]][0]
-                wins = {k: ([run.live[i][0][k][0] for i in chunk for _ in range(N)], [run.live[i][0][k][1] for i in chunk for _ in range(N)], w[2], w[3])
+                w0 = lane.live[chunk[0]][0]
+                wins = {k: ([lane.live[i][0][k][0] for i in chunk for _ in range(N)], [lane.live[i][0][k][1] for i in chunk for _ in range(N)], w[2], w[3])
                         for k, w in w0.items()} if w0 else None
                 yb = self._run_tile_rec(steps, xb, fz, cf, norm_ord, wins)
                 for t, i in enumerate(chunk):
                     tiles[i].x = yb[t * N:(t + 1) * N]
-                    run.finish(i)
+                    lane.finish(i)
 
             groups: Dict[tuple, List[int]] = {}
-            for i in mine:
-                groups.setdefault(tuple(tiles[i].x.shape[2:]) + tuple((k, w[2], w[3]) for k, w in sorted(run.live[i][0].items())), []).append(i)
+            for i in lane.mine:
+                groups.setdefault(tuple(tiles[i].x.shape[2:]) + tuple((k, w[2], w[3]) for k, w in sorted(lane.live[i][0].items())), []).append(i)
             for key in sorted(groups, key=lambda kk: -len(groups[kk])):
                 ids = groups[key]
                 tb = self._tile_batch_that_fits(N, key[:2], dev)
@@ -683,7 +619,7 @@ class VAEHook:
                 c0 = 0
                 while c0 < len(ids):
                     if state.interrupted:
-                        run.interrupted = True
+                        lane.interrupted = True
                         return
                     chunk = [i for i in ids[c0:c0 + tb] if tiles[i] is not None]      # (after an OOM retry: not the tiles that finished)
                     if not chunk:
@@ -702,99 +638,84 @@ class VAEHook:
                     c0 += tb
                     yield chunk
             return
-        for i in mine:
+        for i in lane.mine:
             if state.interrupted:
-                run.interrupted = True
+                lane.interrupted = True
                 return
-            st, k = tiles[i], 0
-            if use_rec:
-                st.x = self._run_tile_rec(steps, st.x, frozen, coefs, norm_ord, run.live[i][0])
-                run.finish(i)
-                yield [i]
-                continue
-            while True:
-                self._run_until_norm(steps, st)
-                if st.pc >= len(steps):
-                    break
-                self._apply_norm(steps, st, *frozen[k])
-                k += 1
-            run.finish(i)
+            tiles[i].x = self._run_tile_rec(steps, tiles[i].x, frozen, coefs, norm_ord, lane.live[i][0] if use_rec else None)
+            lane.finish(i)
             yield [i]
 
     @staticmethod
-    def _lockstep_order(lanes, forward: bool):
-        """(lane, tile) in the order _sweep_lockstep advances them to the next norm: every slot walks its tiles forward or reversed (the zig-zag);
-        several slots take turns, one tile each, so that no device waits while another's tiles are issued."""
-        orders = [(lane, () if lane[0].interrupted else lane[0].mine if forward else list(reversed(lane[0].mine))) for lane in lanes]
+    def _lockstep_order(lanes: List["VAEHook._Lane"], forward: bool):
+        """(lane, tile) in the order _sweep_lockstep advances them to the next norm: every lane walks its tiles forward or reversed (the
+        zig-zag); several lanes take turns, one tile each, so that no device waits while another's tiles are issued."""
+        orders = [(lane, () if lane.interrupted else lane.mine if forward else lane.mine[::-1]) for lane in lanes]
         for r in range(max((len(o) for _, o in orders), default=0)):
             for lane, o in orders:
                 if r < len(o):
                     yield lane, o[r]
 
-    def _sweep_lockstep(self, lanes) -> None:
+    def _sweep_lockstep(self, lanes: List["VAEHook._Lane"]) -> None:
         """Slow mode: all tiles advance in lockstep from norm to norm, the statistics pooled over the tiles (and ranks) at each one
         (upstream :289-361, :578-642 zig-zag); semi-fast (color_fix): the first len(frozen) norms use the frozen statistics instead.
-        lanes: [(run, steps, frozen, device)], one per device slot (device None: one device, the current one).  With several slots each
-        tile's (var, mean) rows go to slot 0 and are pooled in the order the one-device sweep visits the tiles, and the pooled pair goes
-        back to every slot: the same rows in the same order, the same bits."""
+        Each tile's (var, mean) rows go to lane 0's device and are pooled in the order the one-device sweep visits the tiles, and the pooled
+        pair goes back to every lane: with several lanes (device slots) the same rows in the same order as on one device, the same bits."""
         E, world = self.engine, self.shard[1]
-        dev0 = lanes[0][0].z.device
-        n_frozen = 0 if lanes[0][2] is None else len(lanes[0][2])
+        lane0 = lanes[0]
+        dev0 = lane0.device
+        n_frozen = 0 if lane0.frozen is None else len(lane0.frozen)
         forward, k_norm = True, 0
         while True:
             use_frozen = k_norm < n_frozen
-            gp = GroupNormParam(E)
-            rows = {}                                    # several slots: tile -> its (var, mean, pixels) on its slot's device
-            for (run, steps, _, d), i in self._lockstep_order(lanes, forward):
+            rows = {}                                    # tile -> its (var, mean, pixels) on its lane's device
+            for lane, i in self._lockstep_order(lanes, forward):
                 if state.interrupted:
-                    for lane in lanes:
-                        lane[0].interrupted = True
+                    for ln in lanes:
+                        ln.interrupted = True
                     break
-                st = run.tiles[i]
-                with _on_device(d):
-                    self._run_until_norm(steps, st, want_stats=not use_frozen)
-                    if st.pc < len(steps) and not use_frozen:
-                        if len(lanes) == 1:
-                            gp.add_tile(st.x, st.stats)
-                        else:
-                            rows[i] = (*(st.stats if st.stats is not None else E.gn_stats(st.x, 32)), st.x.shape[2] * st.x.shape[3])
-            if lanes[0][0].interrupted and world == 1:
+                st = lane.tiles[i]
+                with _on_device(lane.device):
+                    self._run_until_norm(lane.steps, st, want_stats=not use_frozen)
+                    if st.pc < len(lane.steps) and not use_frozen:
+                        rows[i] = (*(st.stats if st.stats is not None else E.gn_stats(st.x, 32)), st.x.shape[2] * st.x.shape[3])
+            if lane0.interrupted and world == 1:
                 return
             # several ranks: an interrupted rank runs no more tiles but keeps walking the norms to the next POOLED barrier, where the
             # `head` exchange tells every rank (see _pooled_across_ranks) -- all of them leave this loop at the same barrier
             if use_frozen:
                 # a frozen norm is no barrier upstream (the tile runs straight through it): no pooling, no collective,
                 # no change of the zig-zag direction.  A later pooled norm always exists in this branch.
-                for run, steps, fz, d in lanes:
-                    with _on_device(d):
-                        for i in (() if run.interrupted else run.mine):
-                            self._apply_norm(steps, run.tiles[i], *fz[k_norm])
+                for lane in lanes:
+                    with _on_device(lane.device):
+                        for i in (() if lane.interrupted else lane.mine):
+                            self._apply_norm(lane.steps, lane.tiles[i], *lane.frozen[k_norm])
                 k_norm += 1
                 continue
             # (copied only now: a copy between two devices makes each one's stream wait for the other's, which inside the loop above would
             # tie every slot to the tiles issued before it on slot 0)
-            for i in (sorted(rows) if forward else sorted(rows, reverse=True)):
+            gp = GroupNormParam(E)
+            for i in sorted(rows, reverse=not forward):
                 var, mean, px = rows[i]
                 gp.add_stats(var.to(dev0), mean.to(dev0), px)
-            if world == 1:
-                with _on_device(lanes[0][3]):
+            with _on_device(dev0):
+                if world == 1:
                     pooled = gp.summary()
-            else:
-                run = lanes[0][0]
-                pooled, any_interrupted = self._pooled_across_ranks(gp, lanes[0][1], run.z.device, run.interrupted)
-                if any_interrupted:
-                    run.interrupted = True
-                    return
+                else:
+                    pooled, any_interrupted = self._pooled_across_ranks(gp, dev0, lane0.interrupted)
+                    if any_interrupted:
+                        lane0.interrupted = True
+                        return
             k_norm += 1
-            for run, steps, _, d in lanes:
-                with _on_device(d):
+            for lane in lanes:
+                with _on_device(lane.device):
                     if pooled is None:
-                        for i in run.mine:
-                            run.finish(i)
+                        for i in lane.mine:
+                            lane.finish(i)
                         continue
-                    var, mean = pooled if d is None or d == dev0 else (pooled[0].to(d), pooled[1].to(d))
-                    for i in run.mine:
-                        self._apply_norm(steps, run.tiles[i], var, mean)
+                    var, mean = pooled[0].to(lane.device), pooled[1].to(lane.device)
+                    for i in lane.mine:
+                        self._apply_norm(lane.steps, lane.tiles[i], var, mean)
             if pooled is None:
                 return
             forward = not forward
@@ -829,62 +750,81 @@ class VAEHook:
             else:
                 frozen = self.estimate_group_norm(zs, steps)
         all_frozen = frozen is not None and len(frozen) == sum(1 for s in steps if s.kind == "norm")
-        if slots:
-            return self._multi_slot_forward(z, steps, frozen, all_frozen, in_bboxes, out_bboxes, slots, dtype, t0)
 
-        owner = [0] * len(in_bboxes)
-        if world > 1:
-            from mdtile import sharding as _sh
-            owner = _sh.deal_tiles(in_bboxes, world)      # by tile area (mdtile/sharding.py: deal_tiles), the same list on every rank
-        mine = [i for i in range(len(in_bboxes)) if owner[i] == rank] if world > 1 else list(range(len(in_bboxes)))
-        self.last_tile_slots = [0] * len(in_bboxes) if world == 1 else None
-        run = VAEHook._Run(self, z, in_bboxes, out_bboxes, mine)
+        # one lane for one device or this rank, one per device slot (the slots after the first with their own program and copies of z and
+        # of the frozen statistics); the tiles dealt by area (mdtile/sharding.py: deal_tiles), the same list on every rank
+        from mdtile import sharding
+        devs = [torch.device("cuda", i) for i in slots] if slots else [dev]
+        owner = sharding.deal_tiles(in_bboxes, len(devs) if slots else world)
+        self.last_tile_slots = list(owner) if world == 1 else None
+        lanes = []
+        for k, d in enumerate(devs):
+            with _on_device(d):
+                lane_steps = steps if k == 0 else self._slot_program(d.index)
+                lane_frozen = frozen if k == 0 or frozen is None else [(v.to(d), m.to(d)) for v, m in frozen]
+                mine = [i for i, o in enumerate(owner) if o == (k if slots else rank)]
+                lanes.append(VAEHook._Lane(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, mine, lane_steps, lane_frozen, keep_tiles=bool(slots)))
         if all_frozen:
-            for _ in self._sweep_frozen(run, steps, frozen):
-                pass
+            sweeps = [(lane, self._sweep_frozen(lane)) for lane in lanes]
+            while sweeps:                                # one chunk of every lane per round: no device waits while another's list is issued
+                still = []
+                for lane, sweep in sweeps:
+                    with _on_device(lane.device):
+                        if next(sweep, None) is not None:
+                            still.append((lane, sweep))
+                sweeps = still
         else:
-            self._sweep_lockstep([(run, steps, frozen, None)])
-        return self._assemble(run, owner, dtype, t0)
+            self._sweep_lockstep(lanes)
+        return self._collect(lanes, owner, dtype, t0)
 
-    def _assemble(self, run: "VAEHook._Run", owner, dtype, t0) -> Tensor:
-        """NaN test of the image (upstream :633-634), the gather of the other ranks' rectangles, upstream's interrupt results (:644-650)."""
-        net, z, result, interrupted = self.net, run.z, run.result, run.interrupted
-        dev = z.device
-        N, _, height, width = z.shape
+    def _collect(self, lanes: List["VAEHook._Lane"], owner: List[int], dtype, t0) -> Tensor:
+        """The result on lane 0's device: the tiles kept by several lanes read into one image (mdtile_vae_assemble, peer reads, after lane
+        0's stream has waited for the other devices' -- events, no host synchronize), the NaN test of the image (upstream :633-634), the
+        gather of the other ranks' rectangles, upstream's interrupt results (:644-650); one host synchronize at the end."""
+        from mdtile import sharding
+        z, dev, result = lanes[0].z, lanes[0].device, lanes[0].result
         rank, world = self.shard
-        nan_seen = bool(run.nan_flags) and bool(torch.stack(run.nan_flags).any().item())
-        if world > 1 and self.gather_to is not None:
-            # The gather below is a grouped exchange EVERY rank must enter (or none): a rank that was interrupted, or whose NaN check
-            # raises, would leave the others -- and the root's receives -- waiting for ever.  So the ranks first agree on both flags (one
-            # small all-reduce), then skip the gather together / raise together.  Upstream tests every tile of the image it returns
-            # (tilevae.py:633-634): with the flags summed the root sees a NaN found on any rank.
-            from mdtile import sharding
-            agree = torch.tensor([1.0 if interrupted else 0.0, 1.0 if nan_seen else 0.0], dtype=torch.float32, device=dev)
-            sharding.comm_allreduce_sum(agree)
-            flags = agree.tolist()
-            interrupted, nan_seen = flags[0] > 0.0, flags[1] > 0.0
-        if nan_seen:
-            devices.test_for_nans(torch.full((1,), float("nan")), "vae")     # raises the host's NansException (or not: --disable-nan-check)
-        if world > 1 and self.gather_to is not None and not interrupted:
-            from mdtile import sharding
-            if result is None and rank == self.gather_to:
-                result = torch.zeros((N, 3 if self.is_decoder else 2 * int(getattr(net, "z_channels", 4)),
-                                      *((height * 8, width * 8) if self.is_decoder else (height // 8, width // 8))), device=dev, dtype=torch.float32)
-            if result is not None:
-                sharding.gather_tiles_to_root(result, run.out_bboxes, lambda i: owner[i], rank, self.gather_to)
+        interrupted = any(lane.interrupted for lane in lanes)
+        kept = [t for lane in lanes if lane.kept for t in lane.kept]
+        with _on_device(dev):
+            for lane in lanes[1:]:
+                if lane.device != dev:
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(lane.device))
+                    torch.cuda.current_stream(dev).wait_event(ev)
+            if kept:
+                result = torch.zeros(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
+                self.engine.vae_assemble(kept, result, self.is_decoder)
+            flags = [f.to(dev) for lane in lanes for f in lane.nan_flags]
+            nan_seen = bool(flags) and bool(torch.stack(flags).any().item())
+            if world > 1 and self.gather_to is not None:
+                # The gather below is a grouped exchange EVERY rank must enter (or none): a rank that was interrupted, or whose NaN check
+                # raises, would leave the others -- and the root's receives -- waiting for ever.  So the ranks first agree on both flags (one
+                # small all-reduce), then skip the gather together / raise together.  Upstream tests every tile of the image it returns
+                # (tilevae.py:633-634): with the flags summed the root sees a NaN found on any rank.
+                agree = torch.tensor([1.0 if interrupted else 0.0, 1.0 if nan_seen else 0.0], dtype=torch.float32, device=dev)
+                sharding.comm_allreduce_sum(agree)
+                interrupted, nan_seen = (v > 0.0 for v in agree.tolist())
+            if nan_seen:
+                devices.test_for_nans(torch.full((1,), float("nan")), "vae")     # raises the host's NansException (or not: --disable-nan-check)
+            if world > 1 and self.gather_to is not None and not interrupted:
+                if result is None and rank == self.gather_to:
+                    result = torch.zeros(self._out_shape(z, 3 if self.is_decoder else 2 * int(getattr(self.net, "z_channels", 4))), device=dev,
+                                         dtype=torch.float32)
+                if result is not None:
+                    sharding.gather_tiles_to_root(result, lanes[0].out_bboxes, lambda i: owner[i], rank, self.gather_to)
+            if result is not None and dev.type == "cuda":
+                torch.cuda.synchronize(dev)              # (several lanes: the assembly has read every lane's tiles, which may go now)
         self.last_seconds = time() - t0
-        if interrupted and result is not None:
-            return result.to(dtype)          # upstream hands back what is finished (:644-647)
-        if result is None:
+        if result is None:                               # interrupted before any tile finished (upstream :644-650)
             if not self.is_decoder:
                 raise RuntimeError("[Tiled VAE]: interrupted before any encoder tile finished")
-            from modules.sd_vae_approx import cheap_approximation
-            approx = torch.cat([torch.nn.functional.interpolate(cheap_approximation(x).unsqueeze(0), scale_factor=8,
-                                                                mode="nearest-exact") for x in z], dim=0)
-            return approx.to(dev, dtype=dtype)
+            from modules import sd_vae_approx
+            return torch.cat([torch.nn.functional.interpolate(sd_vae_approx.cheap_approximation(x).unsqueeze(0), scale_factor=8,
+                                                              mode="nearest-exact") for x in z], dim=0).to(dev, dtype=dtype)
         if dev.type == "cuda":
-            torch.cuda.synchronize(dev)
-            print(f"[Tiled VAE]: Done in {time() - t0:.3f}s, max VRAM alloc {torch.cuda.max_memory_allocated(dev) / 2**20:.3f} MB")
+            where = f" on {len(lanes)} device slots" if len(lanes) > 1 else ""
+            print(f"[Tiled VAE]: Done in {self.last_seconds:.3f}s{where}, max VRAM alloc {torch.cuda.max_memory_allocated(dev) / 2**20:.3f} MB")
         return result.to(dtype)
 
 

@@ -183,13 +183,8 @@ class GroupNormParam:
         self.engine = engine or mdtile
         self.var_list, self.mean_list, self.pixel_list = [], [], []
 
-    def add_tile(self, tile: Tensor, stats=None):
-        """stats: (var, mean) of `tile` when its producer has already left them (TileState.stats); else one pass over the tile."""
-        var, mean = stats if stats is not None else self.engine.gn_stats(tile, 32)
-        self.add_stats(var, mean, tile.shape[2] * tile.shape[3])
-
     def add_stats(self, var: Tensor, mean: Tensor, pixels: int):
-        """The (var, mean) rows of a tile of `pixels` px, computed elsewhere (another device slot)."""
+        """The (var, mean) rows of a tile of `pixels` px."""
         self.var_list.append(var)
         self.mean_list.append(mean)
         self.pixel_list.append(pixels)

@@ -245,7 +245,7 @@ def test_pooled_statistics_sites_take_the_record_kernels_where_they_pay(monkeypa
 @pytest.mark.parametrize("rec_convs", [True, False], ids=["record_doubles", "handover_doubles"])
 def test_slow_mode_takes_the_statistics_the_producing_conv_leaves(monkeypatch, rec_convs):
     """Slow mode (scripts/tilevae.py lockstep loop, upstream :289-361): where the conv that produces a pooled norm's input can leave the
-    statistics of its output (PackedConv.leaves_stats -> TileState.stats), GroupNormParam.add_tile takes them instead of a pass over the
+    statistics of its output (PackedConv.leaves_stats -> TileState.stats), the pooling takes them instead of a pass over the
     tile (engine.gn_stats).  Same image as with MDTILE_SLOW_STATS=0, same as the oracle; the passes that remain are the ones whose input
     no 3x3 conv with a fused pre-activation produces (conv_in, the attention block's output)."""
     from hostsim import ldm_decoder as ld

@@ -168,6 +168,17 @@ typedef struct mdtile_blend_args {
 
 int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                  const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
+/* Which kernel mdtile_blend launches for these arguments, and in what shape -- answered by the SAME host function the launcher calls, from
+ * the plan's host tables alone (no device is touched, no GPU is needed): tests pin a geometry to the code path it was written for.
+ *   flags = the MDTILE_BLEND_* of the call; num_batches as for mdtile_blend (0 = no grid); ptrs_aligned16 = every batch pointer (the packed
+ *   buffer's with MDTILE_BLEND_PACKED) is 16-byte aligned; row_lo, row_hi as in mdtile_blend_args.
+ *   info8 = { kernel, planes per thread (k_blend) / per block (k_blend_lds), candidates per chunk G (k_blend) / quads per strip SQ
+ *             (k_blend_lds), LDS bytes per block, most tile columns staged per strip,
+ *             k_blend only: quads (4 px of a row) on the 16-byte vector loads, on the per-element loads, on the generic walk } */
+#define MDTILE_BLEND_KERNEL_PLAIN 0 /* k_blend: tile values global -> registers */
+#define MDTILE_BLEND_KERNEL_LDS 1   /* k_blend_lds: tile row segments staged in LDS by DMA */
+int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, int C, int flags, int num_batches, int ptrs_aligned16, int row_lo,
+                          int row_hi, int* info8);
 /* Epilogue on summed partials (multi-GPU): MD divide + FG composite, identical math to mdtile_blend's tail.
  * d_partial fp32 [N,C,H,W]; FG regions are re-read from `regions`. */
 int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args, const float* d_partial,

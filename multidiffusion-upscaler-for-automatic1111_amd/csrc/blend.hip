@@ -39,7 +39,6 @@ namespace {
 struct BlendParams {
     int W, H, tw, th, cols, tile_bs, N, C;
     int flags, tile_lo, tile_hi, row_lo, nrows, num_regions, num_batches, num_fg;
-    int lds_ncs, lds_pad_[3];      // k_blend_lds: most tile columns that touch one strip (the stage is sized for it)
     const int *xs, *ys, *colrange, *rowrange;
     const int4 *colquad, *rowinfo;
     const float *weights, *tile_w, *rescale;
@@ -426,7 +425,7 @@ __global__ __launch_bounds__(256) void k_blend(const BlendParams P) {
 // ---- the LDS-staged form (see the file header) ------------------------------------------------------------------------
 // Block = `blockDim.x` quads (a strip of 4 * blockDim.x px) of ONE canvas row x LPP planes.  LDS: stage[rr][p][cl] = one tile row each,
 // [16 B of zeros | tw elements | 16 B of zeros], rr = covering tile row (<= 3), p = plane, cl = tile column relative to the first one
-// that touches the strip (P.lds_ncs of them at most; the host sizes the stage for it).  One wave-instruction of LDS-DMA moves one staged
+// that touches the strip (BlendDispatch::ncs of them at most; the host sizes the stage for it).  One wave-instruction of LDS-DMA moves one staged
 // row (tw * sizeof(T) / 16 lanes active: the LDS destination of `global_load_lds` is wave-uniform base + 16 * lane, the global source
 // is per lane).  A 4-element read at tile-relative x in [-3, tw - 1] then never leaves [pad | row | pad].
 template <typename T, int METHOD, int LPP, bool PACKED>
@@ -646,39 +645,97 @@ void launch_blend_lds_cfg(const BlendParams& P, int method, int SQ, size_t lds, 
     }
 }
 
-template <typename T>
-bool launch_blend_lds(BlendParams& P, const mdtile_plan* plan, int method, hipStream_t s) {
-    const int row_bytes = P.tw * (int)sizeof(T);
-    if (P.num_batches <= 0 || row_bytes % 16 != 0 || row_bytes > 1024 || plan->nc_max > 3 || plan->nr_max > 3 || plan->nc_max < 1) return false;
+// ---- dispatch: WHICH kernel takes a launch, and in what shape.  Host integers only (the plan's host tables; no device call, no
+// plan_upload), and the ONLY place where that is decided: launch_blend below and mdtile_blend_dispatch (the query tests use to pin a
+// geometry to the path it was written for) both call it.
+struct BlendDispatch {
+    int kernel;       // MDTILE_BLEND_KERNEL_PLAIN (k_blend) | MDTILE_BLEND_KERNEL_LDS (k_blend_lds)
+    int planes;       // PP (planes per thread) | LPP (planes per block)
+    int shape;        // G (candidates per chunk) | SQ (quads per strip = threads per block)
+    int lds_bytes;    // dynamic LDS per block (k_blend_lds), else 0
+    int ncs;          // k_blend_lds: most tile columns that touch one strip (the stage is sized for it), else 0
+    // k_blend only: how many of the launch's quads (4 px of one row) take the 16-byte vector loads, the per-element loads, the generic walk
+    int vec_quads, elem_quads, walk_quads;
+};
+
+// census: also count k_blend's quads per load path (the query's extra; a launch has no use for it and does not pay for it)
+static BlendDispatch blend_dispatch(const mdtile_plan* plan, int elem_bytes, int N, int C, int flags, int num_batches, bool ptrs_aligned16,
+                                    int row_lo, int nrows, bool census) {
+    BlendDispatch D = {MDTILE_BLEND_KERNEL_PLAIN, 0, 0, 0, 0, 0, 0, 0};
+    (void)flags;      // tile range, partial sums and the packed form are runtime branches of both kernels: today no flag moves a launch to the other one
+    const int planes = N * C, W = plan->w, tw = plan->tw;
+    // k_blend_lds: does it take this launch?  (see the comment above launch_blend_lds_cfg)
+    const int row_bytes = tw * elem_bytes;
+    bool lds_ok = num_batches > 0 && row_bytes % 16 == 0 && row_bytes <= 1024 && plan->nc_max <= 3 && plan->nr_max <= 3 && plan->nc_max >= 1 &&
+                  ptrs_aligned16;
+    if (lds_ok) {
+        int SQ = 256, lpp_forced = 0;
+        bool wanted = false;
+        for (int c = 0; c < plan->cols; ++c) wanted = wanted || (plan->h_xs[c] % 4 != 0);
+        if (const char* e = probe_env("MDTILE_BLEND_LDS")) {
+            int a = 0, b = 0;
+            if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 64 && a <= 256 && a % 64 == 0) { SQ = a; lpp_forced = b; wanted = true; }
+            else wanted = atoi(e) != 0;
+        }
+        if (wanted) {
+            int ncs = 1;      // most tile columns that touch one strip of 4 * SQ px
+            for (int sx = 0; sx < W; sx += 4 * SQ) {
+                int n = 0;
+                for (int c = 0; c < plan->cols; ++c) n += (plan->h_xs[c] < sx + 4 * SQ && plan->h_xs[c] + tw > sx) ? 1 : 0;
+                ncs = n > ncs ? n : ncs;
+            }
+            const size_t per_plane = (size_t)plan->nr_max * ncs * (row_bytes + 32);
+            int lpp = 0;
+            for (int cand : {4, 2, 1})
+                if (planes % cand == 0 && per_plane * cand <= 64 * 1024 && (lpp_forced == 0 || lpp_forced == cand)) { lpp = cand; break; }
+            if (lpp != 0) {
+                D.kernel = MDTILE_BLEND_KERNEL_LDS; D.planes = lpp; D.shape = SQ; D.lds_bytes = (int)(per_plane * lpp); D.ncs = ncs;
+                return D;
+            }
+        }
+    }
+    // k_blend.  Planes per thread: as many as keep >= ~128k threads in the grid (2 per lane of the chip), then G so that a
+    // thread has ~16 16-byte loads in flight (measured on MI355X: (8,2) for the 8K canvas, (4,4)/(2,4) below it)
+    const int W4 = (W + 3) / 4;
+    const long long work = (long long)nrows * W4 * planes;
+    int pp = 8, g = 2;
+    while (pp > 1 && work / pp < 131072) pp >>= 1;
+    if (pp < 8) g = 4;
+    if (const char* e = probe_env("MDTILE_BLEND_CFG")) {  // probes build only; "0,0" keeps the heuristic
+        int epp = 0, eg = 0;
+        if (sscanf(e, "%d,%d", &epp, &eg) == 2 && epp > 0 && eg > 0) { pp = epp; g = eg; }
+    }
+    while (pp > 1 && planes % pp != 0) pp >>= 1;
+    // the instantiations that exist: (8,4) (8,2) (4,4) (4,2) (2,4) (1,4)
+    if (pp >= 8) { pp = 8; g = g >= 4 ? 4 : 2; }
+    else if (pp >= 4) { pp = 4; g = g >= 4 ? 4 : 2; }
+    else { pp = pp >= 2 ? 2 : 1; g = 4; }
+    D.planes = pp; D.shape = g;
+    if (census && num_batches > 0) {
+        // the per-quad choice k_blend makes on the device (`clean` / `small`), counted from the same records it reads
+        const int* cq = plan->h_table + plan->quad_off;
+        const int* ri = cq + 4 * (size_t)W4;
+        long long small_rows = 0;
+        for (int y = row_lo; y < row_lo + nrows; ++y) small_rows += (ri[4 * y] >> 16) <= 3 ? 1 : 0;
+        long long vec = 0, elem = 0;
+        for (int xq = 0; xq < W4; ++xq) {
+            const int nc = cq[4 * xq] >> 16, x0 = 4 * xq;
+            if (nc > 3) continue;
+            bool clean = W - x0 >= 4;
+            for (int k = 0; k < nc && k < 3; ++k) { const int t = x0 - cq[4 * xq + 1 + k]; clean = clean && t >= 0 && t + 3 < tw; }
+            if (nc < 1) { const int t = x0 - cq[4 * xq + 1]; clean = clean && t >= 0 && t + 3 < tw; }
+            (clean ? vec : elem) += 1;
+        }
+        D.vec_quads = (int)(vec * small_rows); D.elem_quads = (int)(elem * small_rows);
+        D.walk_quads = (int)((long long)nrows * W4 - (vec + elem) * small_rows);
+    }
+    return D;
+}
+
+static bool batch_ptrs_aligned16(const BlendParams& P) {
     const int nptr = (P.flags & MDTILE_BLEND_PACKED) ? 1 : P.num_batches;
     for (int b = 0; b < nptr; ++b)
         if (P.batch[b] && ((uintptr_t)P.batch[b] & 15)) return false;
-    int SQ = 256, lpp_forced = 0;
-    bool wanted = false;
-    for (int c = 0; c < plan->cols; ++c) wanted = wanted || (plan->h_xs[c] % 4 != 0);
-    if (const char* e = probe_env("MDTILE_BLEND_LDS")) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 64 && a <= 256 && a % 64 == 0) { SQ = a; lpp_forced = b; wanted = true; }
-        else wanted = atoi(e) != 0;
-    }
-    if (!wanted) return false;
-    int ncs = 1;      // most tile columns that touch one strip of 4 * SQ px
-    for (int sx = 0; sx < P.W; sx += 4 * SQ) {
-        int n = 0;
-        for (int c = 0; c < plan->cols; ++c) n += (plan->h_xs[c] < sx + 4 * SQ && plan->h_xs[c] + P.tw > sx) ? 1 : 0;
-        ncs = n > ncs ? n : ncs;
-    }
-    const int planes = P.N * P.C;
-    const size_t per_plane = (size_t)plan->nr_max * ncs * (row_bytes + 32);
-    int lpp = 0;
-    for (int cand : {4, 2, 1})
-        if (planes % cand == 0 && per_plane * cand <= 64 * 1024 && (lpp_forced == 0 || lpp_forced == cand)) { lpp = cand; break; }
-    if (lpp == 0) return false;
-    P.lds_ncs = ncs;
-    const size_t lds = per_plane * lpp;
-    if (lpp == 4) launch_blend_lds_cfg<T, 4>(P, method, SQ, lds, s);
-    else if (lpp == 2) launch_blend_lds_cfg<T, 2>(P, method, SQ, lds, s);
-    else launch_blend_lds_cfg<T, 1>(P, method, SQ, lds, s);
     return true;
 }
 
@@ -689,27 +746,20 @@ int launch_blend(BlendParams& P, const mdtile_plan* plan, int method, bool final
         dim3 grid(cdiv((long long)P.nrows * P.W, 256), P.N * P.C);
         if (method == MDTILE_METHOD_MD) hipLaunchKernelGGL((k_blend_finalize<T, MDTILE_METHOD_MD>), grid, block, 0, s, P);
         else hipLaunchKernelGGL((k_blend_finalize<T, MDTILE_METHOD_MOD>), grid, block, 0, s, P);
-    } else if (plan && launch_blend_lds<T>(P, plan, method, s)) {
-        // (the LDS-staged kernel took it)
     } else {
-        const int planes = P.N * P.C;
-        // planes per thread: as many as keep >= ~128k threads in the grid (2 per lane of the chip), then G so that a
-        // thread has ~16 16-byte loads in flight (measured on MI355X: (8,2) for the 8K canvas, (4,4)/(2,4) below it)
-        const long long work = (long long)P.nrows * ((P.W + 3) / 4) * planes;
-        int pp = 8, g = 2;
-        while (pp > 1 && work / pp < 131072) pp >>= 1;
-        if (pp < 8) g = 4;
-        if (const char* e = probe_env("MDTILE_BLEND_CFG")) {  // probes build only; "0,0" keeps the heuristic
-            int epp = 0, eg = 0;
-            if (sscanf(e, "%d,%d", &epp, &eg) == 2 && epp > 0 && eg > 0) { pp = epp; g = eg; }
+        const BlendDispatch D = blend_dispatch(plan, (int)sizeof(T), P.N, P.C, P.flags, P.num_batches, batch_ptrs_aligned16(P), P.row_lo, P.nrows, false);
+        if (D.kernel == MDTILE_BLEND_KERNEL_LDS) {
+            if (D.planes == 4) launch_blend_lds_cfg<T, 4>(P, method, D.shape, (size_t)D.lds_bytes, s);
+            else if (D.planes == 2) launch_blend_lds_cfg<T, 2>(P, method, D.shape, (size_t)D.lds_bytes, s);
+            else launch_blend_lds_cfg<T, 1>(P, method, D.shape, (size_t)D.lds_bytes, s);
+        } else {
+            if (D.planes == 8 && D.shape == 4) launch_blend_cfg<T, 8, 4>(P, method, s);
+            else if (D.planes == 8) launch_blend_cfg<T, 8, 2>(P, method, s);
+            else if (D.planes == 4 && D.shape == 4) launch_blend_cfg<T, 4, 4>(P, method, s);
+            else if (D.planes == 4) launch_blend_cfg<T, 4, 2>(P, method, s);
+            else if (D.planes == 2) launch_blend_cfg<T, 2, 4>(P, method, s);
+            else launch_blend_cfg<T, 1, 4>(P, method, s);
         }
-        while (pp > 1 && planes % pp != 0) pp >>= 1;
-        if (pp >= 8 && g >= 4) launch_blend_cfg<T, 8, 4>(P, method, s);
-        else if (pp >= 8) launch_blend_cfg<T, 8, 2>(P, method, s);
-        else if (pp >= 4 && g >= 4) launch_blend_cfg<T, 4, 4>(P, method, s);
-        else if (pp >= 4) launch_blend_cfg<T, 4, 2>(P, method, s);
-        else if (pp >= 2) launch_blend_cfg<T, 2, 4>(P, method, s);
-        else launch_blend_cfg<T, 1, 4>(P, method, s);
     }
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
@@ -787,6 +837,30 @@ extern "C" int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* ar
         case MDTILE_DT_F16: return launch_blend<__half>(P, plan, args->method, false, s);
         default: return launch_blend<__hip_bfloat16>(P, plan, args->method, false, s);
     }
+}
+
+extern "C" int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, int C, int flags, int num_batches, int ptrs_aligned16,
+                                     int row_lo, int row_hi, int* info8) {
+    MDT_CHECK_ARG(plan && info8, "mdtile_blend_dispatch: null argument");
+    MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_blend_dispatch: bad N=%d C=%d", N, C);
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_blend_dispatch: bad dtype %d", dtype);
+    MDT_CHECK_ARG(num_batches >= 0, "mdtile_blend_dispatch: bad num_batches %d", num_batches);
+    if (num_batches > 0 && !(flags & MDTILE_BLEND_PACKED)) {   // what fill_params asks of an unpacked launch
+        MDT_CHECK_ARG(num_batches == plan->num_batches, "mdtile_blend_dispatch: %d batches given, plan has %d", num_batches, plan->num_batches);
+        if (num_batches > MDTILE_MAX_BATCHES) {
+            set_error("mdtile_blend_dispatch: %d batches > MDTILE_MAX_BATCHES=%d (use MDTILE_BLEND_PACKED)", num_batches, MDTILE_MAX_BATCHES);
+            return MDTILE_E_LIMIT;
+        }
+    }
+    int lo = 0, nrows = plan->h;
+    if (!(row_lo == 0 && row_hi == 0)) {
+        MDT_CHECK_ARG(row_lo >= 0 && row_hi > row_lo && row_hi <= plan->h, "mdtile_blend_dispatch: bad row range [%d,%d)", row_lo, row_hi);
+        lo = row_lo; nrows = row_hi - row_lo;
+    }
+    const BlendDispatch D = blend_dispatch(plan, dtype == MDTILE_DT_F32 ? 4 : 2, N, C, flags, num_batches, ptrs_aligned16 != 0, lo, nrows, true);
+    info8[0] = D.kernel; info8[1] = D.planes; info8[2] = D.shape; info8[3] = D.lds_bytes; info8[4] = D.ncs;
+    info8[5] = D.vec_quads; info8[6] = D.elem_quads; info8[7] = D.walk_quads;
+    return MDTILE_OK;
 }
 
 extern "C" int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args, const float* d_partial,

@@ -11,7 +11,7 @@ import contextlib
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -23,6 +23,7 @@ DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 METHOD_MD, METHOD_MOD = 0, 1
 REGION_BG, REGION_FG = 0, 1
 BLEND_PARTIAL, BLEND_TILE_RANGE, BLEND_PACKED = 1, 2, 4
+BLEND_KERNEL_PLAIN, BLEND_KERNEL_LDS = 0, 1
 CONV_UPSAMPLE2X = 1
 CONV_REC_ONE_BLOCK, CONV_REC_TWO_BLOCKS = 4, 8      # call_rec(family=...): name the record-conv kernel family (tests / probes); 0 = per launch
 CONV_EXACT_F32 = 2
@@ -80,6 +81,7 @@ _SIGNATURES = {
     "mdtile_gather_rect": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mdtile_stream_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mdtile_blend": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_Region), c_int, c_void_p]),
+    "mdtile_blend_dispatch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _IP]),
     "mdtile_blend_finalize": (c_int, [c_void_p, POINTER(_BlendArgs), c_void_p, POINTER(_Region), c_int, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
@@ -484,7 +486,7 @@ class BlendCall:
     blend itself runs 20 us on an 8K canvas).  Valid while the tensors it was built from stay alive at the same addresses (sampler
     loops that write the model outputs into fixed buffers; bench.py)."""
 
-    __slots__ = ("plan", "out", "_a", "_ptrs", "_n", "_rarr", "_nreg", "_keep", "_fn")
+    __slots__ = ("plan", "out", "_a", "_ptrs", "_n", "_rarr", "_nreg", "_keep", "_fn", "_aligned")
 
     def __init__(self, plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, weights=None, tile_w=None, rescale=None,
                  regions: Sequence[RegionSpec] = (), out: Optional[torch.Tensor] = None, dtype=None, device=None, partial: bool = False,
@@ -513,6 +515,7 @@ class BlendCall:
                              _p(weights).value, _p(tile_w).value, _p(rescale).value, out.data_ptr())
         self._ptrs = (c_void_p * max(1, len(batch_out)))(*[t.data_ptr() for t in batch_out])
         self._n = len(batch_out)
+        self._aligned = all(t.data_ptr() % 16 == 0 for t in batch_out)
         self._rarr, keep = _regions_array(regions, dtype)
         self._nreg = len(regions)
         self._keep = (list(batch_out), weights, tile_w, rescale, keep)
@@ -523,6 +526,50 @@ class BlendCall:
         if rc != OK:
             _check(rc, "mdtile_blend")
         return self.out
+
+    def dispatch(self) -> "BlendDispatch":
+        """The kernel and launch shape this call gets (mdtile_blend_dispatch on exactly these arguments and pointers)."""
+        a = self._a
+        return _blend_dispatch(self.plan, a.dtype, a.N, a.C, a.flags, self._n, self._aligned, (a.row_lo, a.row_hi))
+
+
+class BlendDispatch(NamedTuple):
+    """Answer of mdtile_blend_dispatch: kernel = BLEND_KERNEL_PLAIN (k_blend: planes = planes per thread, shape = candidates per chunk;
+    vec / elem / walk_quads = quads on its 16-byte loads, per-element loads, generic walk) or BLEND_KERNEL_LDS (k_blend_lds: planes = planes
+    per block, shape = quads per strip, lds_bytes / ncs = the stage)."""
+    kernel: int
+    planes: int
+    shape: int
+    lds_bytes: int
+    ncs: int
+    vec_quads: int
+    elem_quads: int
+    walk_quads: int
+
+    @property
+    def lds(self) -> bool:
+        return self.kernel == BLEND_KERNEL_LDS
+
+
+def _blend_dispatch(plan: Plan, dtype_c: int, N: int, C: int, flags: int, num_batches: int, aligned: bool, rows) -> BlendDispatch:
+    info = (c_int * 8)()
+    _check(lib().mdtile_blend_dispatch(plan.handle, dtype_c, int(N), int(C), int(flags), int(num_batches), int(bool(aligned)),
+                                       int(rows[0]), int(rows[1]), info), "mdtile_blend_dispatch")
+    return BlendDispatch(*list(info))
+
+
+def blend_dispatch(plan: Plan, dtype, N: int, C: int, *, partial: bool = False, tile_range=None, row_range=None, packed: bool = False,
+                   num_batches: Optional[int] = None, aligned: bool = True) -> BlendDispatch:
+    """Which kernel blend() launches for these arguments (no tensors, no device: the library answers from the plan's host tables with the
+    function its launcher calls).  num_batches: tile-batch tensors handed over (default: the plan's; more than MAX_BATCHES are packed into
+    one buffer, as BlendCall does); aligned: every batch tensor starts on a 16-byte boundary."""
+    n = plan.num_batches if num_batches is None else int(num_batches)
+    if not packed and n > MAX_BATCHES:
+        n, packed = 1, True
+    if packed and n > 0:
+        n = 1
+    flags = (BLEND_PARTIAL if partial else 0) | (BLEND_PACKED if packed else 0) | (BLEND_TILE_RANGE if tile_range is not None else 0)
+    return _blend_dispatch(plan, dtype_code(dtype), N, C, flags, n, aligned, row_range or (0, 0))
 
 
 def blend(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, weights=None, tile_w=None,

@@ -84,6 +84,60 @@ def test_sharded_blend_matches_single_device(plugin, cuda, world, method, with_r
             assert torch.equal(outs[r][:, :, solo], ref[:, :, solo])
 
 
+def _tile_fn_f32_inside(t):
+    """_tile_fn evaluated in fp32 and rounded once to the I/O dtype (for fp32 tensors: _tile_fn itself)."""
+    return _tile_fn(t.float()).to(t.dtype)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("method", ["md", "mod"])
+@pytest.mark.parametrize("dt", ["f32", "f16"])
+@pytest.mark.parametrize("geom", ["odd200", "odd3rows"])
+def test_sharded_blend_odd_origins_matches_single_device(plugin, cuda, world, method, dt, geom):
+    """test_sharded_blend_matches_single_device on grids with odd tile origins (tile 96 / overlap 48: origins 0, 34, 69, 104), where every
+    band's launch -- tile range + partial sums + row band over the packed buffer -- is a k_blend_lds launch (asserted through the dispatch
+    query), in fp32 and fp16; two tile rows (the third of 3 ranks stays empty) and three.
+    Rows owned by one band: bitwise the one-rank result.  Rows shared by bands are summed across ranks in another order than the one-rank
+    list order: fp32 keeps that test's rtol = 1e-5, atol = 1e-6.  fp16 stores each of the two fp32 values with one rounding to nearest,
+    an error of at most half an fp16 ulp each, ulp(v) <= 2^-10 |v| for normal v and 2^-24 below: rtol = 1e-5 + 2^-10, atol = 1e-6 + 2^-24."""
+    import blend_matrix_cases as bm
+    E = plugin.engine
+    from mdtile import sharding
+    W, H, tw, th, ov, bs = bm.GEOMETRIES[geom]
+    N, C = 2, 4
+    dtype = torch.float32 if dt == "f32" else torch.float16
+    rtol, atol = (1e-5, 1e-6) if dt == "f32" else (1e-5 + 2.0 ** -10, 1e-6 + 2.0 ** -24)
+    M = E.METHOD_MD if method == "md" else E.METHOD_MOD
+    label = next(c for c in bm.SHARD_CASES if (c.geom, c.dtype, c.method) == (geom, dt, method))
+    torch.manual_seed(5)
+    x = torch.randn(N, C, H, W).to(dtype).to(cuda)
+    one = sharding.ShardedBlend(E.Shard(dev_ids=[0]), W, H, tw, th, ov, bs, M)
+    ref = one.step([x], _tile_fn_f32_inside)[0].clone()
+    o = bo.BlendOracle(method, W, H, tw, th, ov, bs)
+    want = o.evaluate(x.cpu().float(), lambda t: _tile_fn_f32_inside(t.to(dtype)).float()).to(dtype)
+    assert torch.allclose(ref.cpu().float(), want.float(), rtol=rtol, atol=atol), "one-rank ShardedBlend vs the oracle"
+    sb = sharding.ShardedBlend(E.Shard(dev_ids=[0] * world), W, H, tw, th, ov, bs, M)
+    live = [b for b in sb.bands if not b.empty]
+    assert len(live) == min(world, sb.local[0]["plan"].rows)
+    for b in live:       # the launch ShardedBlend.step makes for this band
+        d = E.blend_dispatch(sb.local[0]["plan"], dtype, N, C, packed=True, partial=True, tile_range=(b.tile_lo, b.tile_hi), row_range=(b.row_lo, b.row_hi))
+        assert label.kernel == "lds" and d.lds and d.planes == label.lpp, f"band of rank {b.rank}: {d}"
+    outs = sb.allgather_rows(sb.step([x.clone() for _ in range(world)], _tile_fn_f32_inside))
+    for r, out in enumerate(outs):
+        assert out.dtype == dtype
+        assert torch.allclose(out.float(), ref.float(), rtol=rtol, atol=atol), f"rank {r} of {world}: max diff {(out.float() - ref.float()).abs().max().item()}"
+    checked = 0
+    for r, b in enumerate(sb.bands):
+        if b.empty:
+            continue
+        solo = [y for y in range(b.row_lo, b.row_hi) if sum(1 for q in sb.bands if not q.empty and q.row_lo <= y < q.row_hi) == 1]
+        if solo:
+            assert torch.equal(outs[r][:, :, solo].view(torch.int32 if dt == "f32" else torch.int16),
+                               ref[:, :, solo].view(torch.int32 if dt == "f32" else torch.int16)), f"rank {r}: solo rows differ bitwise"
+            checked += len(solo)
+    assert checked > 0
+
+
 def test_vae_multi_device_sweep_matches_single_device(plugin, cuda):
     """VAEHook.devices: single-process multi-device decode (tiles dealt round-robin, per-device packed weights and streams, output
     rectangles copied to the first device).  Listing cuda:0 twice runs the whole flow on one GPU; the result must equal the ordinary

@@ -57,10 +57,28 @@ const char* mdtile_last_error(void);
  * already produce), fp32 accumulation; everything outside the matrix-core products stays fp32 (residual stream, GroupNorm statistics,
  * softmax, conv_in).  Error class of bf16 operands: ~2^-9 relative per product, ~1e-3 of the output range end to end -- the arithmetic of a
  * half-precision VAE (dtype_vae = bfloat16), at up to a third of the MFMAs.  Process-wide; env MDTILE_CONV_MODE=f32 / MDTILE_ATTN_MODE=f32
- * preset it (and win over MDTILE_PRECISION_BF16 for the kernels they cover). */
+ * preset it (and win over MDTILE_PRECISION_BF16 / MDTILE_PRECISION_F16 for the kernels they cover).
+ *
+ * MDTILE_PRECISION_F16 (= 5; 3 and 4 stay unknown): the fast mode for an fp16 VAE (11 significand bits, the webui's default half VAE).
+ *   - A 3x3 conv whose operand the library itself produces as silu(a x + s) runs as ONE fp16 MFMA per product, fp16_rn(act) x fp16_rn(w),
+ *     fp32 accumulation (v_mfma_f32_32x32x16_f16).  Three cases: the input is an ACTIVATED record image in its fp16 form (below,
+ *     MDTILE_CONV_REC_X_F16); the fp32 hand-over conv mdtile_conv2d_gn(_stats) is called with MDTILE_CONV_W_F16; conv_out behind norm_out
+ *     (the narrow record kernel, the same flag as the first case).
+ *   - Conversion: v_cvt_pk_f16_f32, round to nearest even, of the value clamped to +-65504 first: no Inf is ever written or multiplied.
+ *     fp16 subnormals are operands like any other: v_mfma_f32_32x32x16_f16 multiplies subnormal A / B values as they are, it does not flush
+ *     them (measured on an MI355X: a conv whose weights all lie below 2^-14 gives max |y| 8.3e-4 where flushing would give 0, 4.9e-7 of the
+ *     range from the fp64 reference on the unflushed fp16 weights; tests/test_gpu_precision_f16.py), so nothing is scaled.
+ *   - A conv whose operand is the raw residual stream, or one the library cannot prove normalised, runs the existing THREE-TERM bf16 kernels:
+ *     the upsample convs, nin_shortcut and every other 1x1 conv outside the attention, Downsample, mdtile_conv2d, mdtile_conv2d_gn without
+ *     MDTILE_CONV_W_F16, and a record conv given a bf16-split record.  (The GroupNorm behind the stream is scale-free, the stream is not:
+ *     it may pass 65504.)
+ *   - The attention and its q / k / v / proj_out 1x1 convs (mdtile_conv2d with MDTILE_CONV_ATTN_PROJ): exactly as in MDTILE_PRECISION_BF16.
+ *   - Everything outside the matrix products stays fp32: residual stream, statistics, softmax, conv_in.
+ *   The route predicates (mdtile_conv2d_rec_supported, mdtile_conv2d_gn_supported, mdtile_vae_attn_takes_channel_major) answer as in the default mode. */
 #define MDTILE_PRECISION_BF16X3 0
 #define MDTILE_PRECISION_F32 1
 #define MDTILE_PRECISION_BF16 2
+#define MDTILE_PRECISION_F16 5
 int mdtile_set_precision(int mode);
 int mdtile_get_precision(void);
 
@@ -271,8 +289,18 @@ int mdtile_add(const float* d_a, const float* d_b, float* d_y, size_t n, mdtile_
 #define MDTILE_CONV_UPSAMPLE2X 1
 #define MDTILE_CONV_EXACT_F32 2   /* force the exact-fp32 MFMA kernel (default: split-bf16 "bf16x3" MFMA where the shape allows,
                                      fp32 accumulate, ~1e-5 relative vs fp32; env MDTILE_CONV_MODE=f32 forces it globally) */
+#define MDTILE_CONV_W_F16 128     /* mdtile_conv2d_gn / _gn_stats in MDTILE_PRECISION_F16: d_w_packed is the fp16 plane of mdtile_conv_pack_f16 -> the fp16
+                                     one-term kernel (without the flag the call keeps its three terms; with it outside that mode, or together with
+                                     MDTILE_CONV_EXACT_F32: an error) */
+#define MDTILE_CONV_ATTN_PROJ 256 /* mdtile_conv2d, ksize 1: the conv is q / k / v / proj_out of the attention -- one-term bf16 in MDTILE_PRECISION_F16
+                                     (any other 1x1 conv reads the raw stream and keeps three terms there); no effect in the other modes */
 size_t mdtile_conv_packed_size(int cout, int cin, int ksize); /* floats */
 int mdtile_conv_pack(const float* d_w_oihw, float* d_w_packed, int cout, int cin, int ksize, mdtile_stream_t stream);
+/* fp16 weight plane of MDTILE_PRECISION_F16: fp16_rn(w) (clamped to +-65504) in the layout and K order of the hi plane of the split-bf16 image,
+ * built from the packed buffer of mdtile_conv_pack (its fp32 image holds the exact weights) into a buffer of its own of
+ * mdtile_conv_pack_f16_size floats (0: no fp16 kernel takes the shape; 3x3 only).  The packed buffer and mdtile_conv_packed_size are unchanged. */
+size_t mdtile_conv_pack_f16_size(int cout, int cin, int ksize); /* floats */
+int mdtile_conv_pack_f16(const float* d_w_packed, float* d_w_f16, int cout, int cin, int ksize, mdtile_stream_t stream);
 int mdtile_conv2d(const float* d_x, const float* d_w_packed, const float* d_bias, const float* d_residual, float* d_y,
                   int B, int cin, int cout, int H, int W, int ksize, int flags, int out_layout, mdtile_stream_t stream);
 
@@ -325,12 +353,26 @@ int mdtile_conv2d_gn_stats(const float* d_x, const float* d_coef, const float* d
  *   mdtile_conv2d_rec          : y = conv3x3(x_rec) + bias (+ residual), written as fp32 NCHW (d_y, may be NULL) and / or as the
  *                                record image d_y_rec = split(silu(a y + s)) (d_y_coef [B][2][cout]) or split(y) (d_y_coef NULL);
  *                                MDTILE_CONV_UPSAMPLE2X: x_rec is the HALF-size input of the fused nearest-2x upsample conv
- *                                (ldm Upsample, tilevae.py:139-153).  H, W = output size.  d_w_packed: mdtile_conv_pack(ksize 3). */
+ *                                (ldm Upsample, tilevae.py:139-153).  H, W = output size.  d_w_packed: mdtile_conv_pack(ksize 3).
+ * Second form (MDTILE_PRECISION_F16): an ACTIVATED record image (d_coef / d_y_coef given) written in that mode holds fp16_rn(clamp(x, +-65504)) in
+ * the hi half -- the same 16-byte records, plane order and mdtile_rec_size; its lo half is NOT written (and its border is zeroed in the hi half
+ * only).  A raw record image (coefficients NULL) is a bf16 (hi, lo) split in every mode.  The caller carries the form with the buffer:
+ *   MDTILE_REC_BF16X2 / MDTILE_REC_F16        the format tag of mdtile_rec_from_f32_fmt / mdtile_rec_to_f32_fmt (the calls without _fmt: BF16X2)
+ *   MDTILE_CONV_REC_X_F16                      mdtile_conv2d_rec(_stats): d_x_rec is the fp16 form AND d_w_packed is the plane of mdtile_conv_pack_f16
+ *   MDTILE_CONV_REC_Y_F16                      mdtile_conv2d_rec / mdtile_upconv2d_rec_window: d_y_rec is to be the fp16 form
+ * A tag that disagrees with what the mode writes (fp16 asked outside MDTILE_PRECISION_F16 or for a raw record; an activated record output in that
+ * mode without _Y_F16; _X_F16 on an upsample conv) is MDTILE_E_ARG with "record format mismatch" in the error text -- never a reinterpretation. */
+#define MDTILE_REC_BF16X2 0
+#define MDTILE_REC_F16 1
+#define MDTILE_CONV_REC_X_F16 32
+#define MDTILE_CONV_REC_Y_F16 64
 #define MDTILE_CONV_REC_ONE_BLOCK 4   /* mdtile_conv2d_rec / mdtile_upconv2d_rec_window flags: name the kernel family instead of letting the */
 #define MDTILE_CONV_REC_TWO_BLOCKS 8  /* launcher choose per launch (one 8-wave block per CU / two 4-wave blocks per CU; identical results) */
 size_t mdtile_rec_size(int B, int C, int H, int W);
 int mdtile_rec_from_f32(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, mdtile_stream_t stream);
 int mdtile_rec_to_f32(const void* d_rec, float* d_x, int B, int C, int H, int W, mdtile_stream_t stream);
+int mdtile_rec_from_f32_fmt(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, int fmt, mdtile_stream_t stream);
+int mdtile_rec_to_f32_fmt(const void* d_rec, float* d_x, int B, int C, int H, int W, int fmt, mdtile_stream_t stream);
 int mdtile_conv2d_rec_supported(int cout, int cin, int ksize, int flags);
 int mdtile_conv2d_rec(const void* d_x_rec, const float* d_w_packed, const float* d_bias, const float* d_residual, float* d_y,
                       void* d_y_rec, const float* d_y_coef, int B, int cin, int cout, int H, int W, int flags,

@@ -29,6 +29,7 @@ void set_error(const char* fmt, ...);
 bool conv_strict_f32();   // mdtile_set_precision / MDTILE_CONV_MODE=f32: every conv on the exact-fp32 MFMA kernels
 bool attn_strict_f32();   // ... / MDTILE_ATTN_MODE=f32: attention on the exact-fp32 kernel
 bool mfma_single_term();  // mdtile_set_precision(MDTILE_PRECISION_BF16): one bf16 MFMA (w_hi x x_hi) per product where no strict bit applies
+bool mode_f16();          // mdtile_set_precision(MDTILE_PRECISION_F16): fp16 MFMAs behind a norm, three terms on the raw stream, attention as in MDTILE_PRECISION_BF16
 int plan_upload(const struct ::mdtile_plan* plan);  // mirror the plan's lookup tables to the current device (idempotent)
 
 #define MDT_CHECK_ARG(cond, ...)           \

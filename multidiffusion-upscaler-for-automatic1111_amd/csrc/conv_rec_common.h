@@ -3,6 +3,7 @@
 // See vae_conv_rec.hip for the record-image format and the upstream call sites (scripts/tilevae.py:115-195, 218-245, 614-616).
 #pragma once
 #include "common.h"
+#include "f16_convert.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -152,6 +153,13 @@ __device__ __forceinline__ void split8p(const f32x16& v, int o, u32x4& hi, u32x4
     }
 }
 
+// 8 of the 16 accumulator values of one pixel -> ONE fp16 record (MDTILE_PRECISION_F16, include/mdtile.h: the activated record image's second form;
+// f16_convert.h holds the conversion): 1.5 VALU per value, no lo half.
+__device__ __forceinline__ void cvt8h_acc(const f32x16& v, int o, u32x4& hi) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hi[j] = cvt2h(v[o + 2 * j], v[o + 2 * j + 1]);
+}
+
 // A wave-uniform pointer the optimiser cannot see through: what is added to it afterwards stays a 32-bit lane offset next to an SGPR
 // base (LLVM otherwise re-associates base + plane + lane into (base + lane) + plane: a 64-bit VALU multiply-add per access).
 // volatile: not merged across pixel rows either (16 live SGPR pairs per tensor would spill to VGPR lanes).
@@ -219,7 +227,10 @@ __device__ __forceinline__ void residual_into_acc(const float* res, int Cout, si
 // include/mdtile.h "Slow mode (round 5)"): a lane adds its NROW x NPX x 4 values of every 4-cout quad in fp32, the half-wave's 32 pixels
 // are combined in fp64 and lane 0 of each half writes (sum, sum of squares) to E.st[(m * 8 + 2 g + kg) * 2 ..] -- combined over waves,
 // items and cout quads in a fixed order by k_conv_stats_partial (vae_norm.hip).  Separate kernel symbols: the ST = false code is untouched.
-template <int NPX, int NROW, int MW, int ECS = 64, bool ST = false>
+// R16 (MDTILE_PRECISION_F16): the record output is the fp16 form of an ACTIVATED record image -- fp16_rn(clamp(silu(a y + s))) in the hi half,
+// one 16-byte store per record where the split form has two, zero border in the hi half only; the lo half is not written.  The launcher
+// picks an R16 kernel only for a record output with coefficients (a raw record stays a bf16 split in every mode).  Separate kernel symbols again.
+template <int NPX, int NROW, int MW, int ECS = 64, bool ST = false, bool R16 = false>
 __device__ __forceinline__ void epilogue_item(const EpiCtx& E, const u32x4* ec, f32x16 (&acc)[MW][NROW][NPX], int mt_local0, int mt_global0,
                                               const int (&ys)[NROW], int x, bool x_ok, const ResRows<NROW>& next) {
     constexpr bool ACC_RES = NPX == 1;     // the residual is already in the accumulators (see ResRows); the sub-pixel kernel keeps the plain form
@@ -359,15 +370,26 @@ __device__ __forceinline__ void epilogue_item(const EpiCtx& E, const u32x4* ec, 
 #pragma unroll
                         for (int e = 0; e < NPX; ++e) act8(acc[m][n][e], 8 * R, aq, sq);
                     }
-                    gchar* const yp = uniform_ptr(yr + (size_t)(2 * R) * pl16), *const ypl = uniform_ptr(yp + lo_half);
+                    if constexpr (R16) {
+                        gchar* const yp = uniform_ptr(yr + (size_t)(2 * R) * pl16);
 #pragma unroll
-                    for (int e = 0; e < NPX; ++e) {
-                        u32x4 hi, lo;
-                        split8p(acc[m][n][e], 8 * R, hi, lo);
-                        const size_t at = (size_t)(rrow + (unsigned)(e + 1) * 16u);
-                        if (!(E.dbg & 32)) {
-                            *(MDT_GLOBAL u32x4*)(yp + at) = hi;
-                            *(MDT_GLOBAL u32x4*)(ypl + at) = lo;
+                        for (int e = 0; e < NPX; ++e) {
+                            u32x4 hi;
+                            cvt8h_acc(acc[m][n][e], 8 * R, hi);
+                            const size_t at = (size_t)(rrow + (unsigned)(e + 1) * 16u);
+                            if (!(E.dbg & 32)) *(MDT_GLOBAL u32x4*)(yp + at) = hi;
+                        }
+                    } else {
+                        gchar* const yp = uniform_ptr(yr + (size_t)(2 * R) * pl16), *const ypl = uniform_ptr(yp + lo_half);
+#pragma unroll
+                        for (int e = 0; e < NPX; ++e) {
+                            u32x4 hi, lo;
+                            split8p(acc[m][n][e], 8 * R, hi, lo);
+                            const size_t at = (size_t)(rrow + (unsigned)(e + 1) * 16u);
+                            if (!(E.dbg & 32)) {
+                                *(MDT_GLOBAL u32x4*)(yp + at) = hi;
+                                *(MDT_GLOBAL u32x4*)(ypl + at) = lo;
+                            }
                         }
                     }
                 }
@@ -382,7 +404,7 @@ __device__ __forceinline__ void epilogue_item(const EpiCtx& E, const u32x4* ec, 
                         auto zrec = [&](int py, int px) {      // (px: padded column, 0 = left border)
                             const size_t at = (size_t)(p0 + (unsigned)(py * E.WpO + px) * 16u);
                             *reinterpret_cast<u32x4*>(yp + at) = z;
-                            *reinterpret_cast<u32x4*>(yp + lo_half + at) = z;
+                            if constexpr (!R16) *reinterpret_cast<u32x4*>(yp + lo_half + at) = z;
                         };
                         if (left) zrec(y + 1, 0);
                         if (right) zrec(y + 1, E.W + 1);

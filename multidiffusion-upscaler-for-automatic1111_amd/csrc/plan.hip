@@ -20,7 +20,7 @@ extern "C" int mdtile_version(void) { return MDTILE_VERSION; }
 
 // ---- arithmetic of the matrix-core kernels: split-bf16 ("bf16x3") by default, exact fp32 MFMA or single bf16 on request ----
 // g_precision bits: 1 = convs on exact fp32, 2 = attention on exact fp32 (MDTILE_CONV_MODE / MDTILE_ATTN_MODE presets, either or both),
-// 4 = single-term bf16 MFMAs (MDTILE_PRECISION_BF16).  A strict bit wins over bit 4 for the kernels it covers.
+// 4 = single-term bf16 MFMAs (MDTILE_PRECISION_BF16), 8 = MDTILE_PRECISION_F16.  A strict bit wins over bits 4 / 8 for the kernels it covers.
 namespace mdt {
 static int g_precision = [] {
     const char* c = getenv("MDTILE_CONV_MODE");
@@ -30,17 +30,18 @@ static int g_precision = [] {
 bool conv_strict_f32() { return (g_precision & 1) != 0; }
 bool attn_strict_f32() { return (g_precision & 2) != 0; }
 bool mfma_single_term() { return (g_precision & 4) != 0; }
+bool mode_f16() { return (g_precision & 8) != 0; }
 }  // namespace mdt
 extern "C" int mdtile_set_precision(int mode) {
-    if (mode != MDTILE_PRECISION_BF16X3 && mode != MDTILE_PRECISION_F32 && mode != MDTILE_PRECISION_BF16) {
+    if (mode != MDTILE_PRECISION_BF16X3 && mode != MDTILE_PRECISION_F32 && mode != MDTILE_PRECISION_BF16 && mode != MDTILE_PRECISION_F16) {
         mdt::set_error("mdtile_set_precision: unknown mode %d", mode);
         return MDTILE_E_ARG;
     }
-    mdt::g_precision = mode == MDTILE_PRECISION_F32 ? 3 : mode == MDTILE_PRECISION_BF16 ? 4 : 0;
+    mdt::g_precision = mode == MDTILE_PRECISION_F32 ? 3 : mode == MDTILE_PRECISION_BF16 ? 4 : mode == MDTILE_PRECISION_F16 ? 8 : 0;
     return MDTILE_OK;
 }
 extern "C" int mdtile_get_precision(void) {
-    return mdt::g_precision == 3 ? MDTILE_PRECISION_F32 : (mdt::g_precision & 4) ? MDTILE_PRECISION_BF16 : MDTILE_PRECISION_BF16X3;
+    return mdt::g_precision == 3 ? MDTILE_PRECISION_F32 : (mdt::g_precision & 4) ? MDTILE_PRECISION_BF16 : (mdt::g_precision & 8) ? MDTILE_PRECISION_F16 : MDTILE_PRECISION_BF16X3;
 }
 extern "C" const char* mdtile_last_error(void) { return mdt::g_err; }
 

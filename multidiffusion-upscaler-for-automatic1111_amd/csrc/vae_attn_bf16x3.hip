@@ -265,7 +265,7 @@ int attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok,
     const int nq8 = (Tq128 / BQ + 7) / 8 * 8;
     dim3 grid(nq8 * ns, B), block(512);
 #define MDT_ATTN_LAUNCH(KN, CC) hipLaunchKernelGGL((KN<CC>), grid, block, 0, s, Qr, Kr, Vr, d_out, Tq, Tq128, Tk, Tk128, scale, ns, part, pstat)
-    if (mfma_single_term()) {      // MDTILE_PRECISION_BF16: one MFMA per product
+    if (mfma_single_term() || mode_f16()) {      // MDTILE_PRECISION_BF16, and the attention of MDTILE_PRECISION_F16: one bf16 MFMA per product
         if (C == 512) MDT_ATTN_LAUNCH(k_attn_bf16x1, 512);
         else if (C == 256) MDT_ATTN_LAUNCH(k_attn_bf16x1, 256);
         else MDT_ATTN_LAUNCH(k_attn_bf16x1, 128);

@@ -334,7 +334,9 @@ bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up);
 int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
                              hipStream_t s);
 int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part = nullptr);
+                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part = nullptr, int w16 = 0);
+size_t conv_f16_plane_floats(int cout, int cin);
+int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s);
 bool conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up);
 size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W);
 // vae_norm.hip
@@ -347,11 +349,11 @@ int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, 
 bool conv_rec_supported(int cout, int cin, int ksize);
 size_t rec_image_bytes(int B, int C, int H, int W);
 size_t rec_plane_records(int H, int W);
-int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s);
-int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s);
+int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
+int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
 int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y32, void* d_yrec,
                     const float* d_ycoef, int B, int cin, int cout, int H, int W, int up, hipStream_t s, const int* win = nullptr, int family = 0,
-                    double* d_part = nullptr);
+                    double* d_part = nullptr, int x16 = 0, int y16 = 0);
 bool conv_rec_stats_in_epilogue(int B, int cin, int cout, int H, int W, int up);
 int conv_rec_stats_units(int H, int W, int up);
 // vae_conv1x1_bf16x3.hip
@@ -359,7 +361,7 @@ bool conv1x1_bf16x3_eligible(int cout, int cin);
 size_t conv1x1_bf16x3_packed_floats(int cout, int cin);
 int conv1x1_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
 int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                          int cout, size_t HW, hipStream_t s);
+                          int cout, size_t HW, hipStream_t s, bool attn_proj = false);
 }  // namespace mdt
 
 // packed buffer = [ fp32 image (tap, cin, coutP) | split-bf16 record image (only for shapes the bf16x3 kernels take) ]
@@ -387,6 +389,18 @@ extern "C" int mdtile_conv_pack(const float* d_w_oihw, float* d_w_packed, int co
     return MDTILE_OK;
 }
 
+// fp16 weight plane of MDTILE_PRECISION_F16 (a buffer of its own: the packed buffer and its size are what they were)
+extern "C" size_t mdtile_conv_pack_f16_size(int cout, int cin, int ksize) {
+    if (cout <= 0 || cin <= 0 || ksize != 3) return 0;
+    return conv_f16_plane_floats(cout, cin);
+}
+
+extern "C" int mdtile_conv_pack_f16(const float* d_w_packed, float* d_w_f16, int cout, int cin, int ksize, mdtile_stream_t stream) {
+    MDT_CHECK_ARG(d_w_packed && d_w_f16, "mdtile_conv_pack_f16: null argument");
+    MDT_CHECK_ARG(mdtile_conv_pack_f16_size(cout, cin, ksize) != 0, "mdtile_conv_pack_f16: no fp16 kernel takes cout=%d cin=%d ksize=%d", cout, cin, ksize);
+    return conv_f16_pack(d_w_packed, d_w_f16, cout, cin, as_stream(stream));
+}
+
 extern "C" int mdtile_conv2d(const float* d_x, const float* d_w_packed, const float* d_bias, const float* d_residual, float* d_y,
                              int B, int cin, int cout, int H, int W, int ksize, int flags, int out_layout, mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x && d_w_packed && d_y, "mdtile_conv2d: null argument");
@@ -408,7 +422,7 @@ extern "C" int mdtile_conv2d(const float* d_x, const float* d_w_packed, const fl
     // 1x1 convs (nin_shortcut, q / k / proj_out): split-bf16 kernel over the flat pixel run
     if (ksize == 1 && !up && !force_f32 && !(flags & MDTILE_CONV_EXACT_F32) && out_layout == 0 && conv1x1_bf16x3_eligible(cout, cin))
         return conv1x1_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout,
-                                     (size_t)H * W, s);
+                                     (size_t)H * W, s, (flags & MDTILE_CONV_ATTN_PROJ) != 0);
     if (conv_fewcin_eligible(cin, ksize, up, out_layout)) {      // conv_in: exact fp32 FMAs, bound by its output stream (every precision mode)
         const int ncb = (cout + 127) / 128;
         MDT_CHECK_ARG((size_t)B * ncb <= 65535 && (H + 3) / 4 <= 65535, "mdtile_conv2d: conv_in grid too large (B=%d cout=%d H=%d)", B, cout, H);
@@ -458,9 +472,15 @@ extern "C" int mdtile_conv2d_gn(const float* d_x, const float* d_coef, const flo
                                 float* d_y, int B, int cin, int cout, int H, int W, int ksize, int flags, mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x && d_coef && d_w_packed && d_y, "mdtile_conv2d_gn: null argument");
     MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && H > 0 && W > 0, "mdtile_conv2d_gn: bad shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
+    MDT_CHECK_ARG(!((flags & MDTILE_CONV_W_F16) && (flags & MDTILE_CONV_EXACT_F32)),
+                  "mdtile_conv2d_gn: MDTILE_CONV_W_F16 (fp16 weight plane, one fp16 MFMA per product) contradicts MDTILE_CONV_EXACT_F32 (flags=%d)", flags);
     MDT_CHECK_ARG(mdtile_conv2d_gn_supported(cout, cin, ksize, flags, 0),
                   "mdtile_conv2d_gn: no fused pre-activation kernel for cout=%d cin=%d ksize=%d flags=%d (use mdtile_gn_apply + mdtile_conv2d)", cout, cin, ksize, flags);
     MDT_CHECK_ARG((size_t)H * W < (1u << 31), "mdtile_conv2d_gn: input plane of 2^31 or more pixels");
+    if (flags & MDTILE_CONV_W_F16) {      // d_w_packed is the fp16 plane: the fp16 one-term kernel (the operand is silu(a x + s) by construction)
+        MDT_CHECK_ARG(mode_f16(), "mdtile_conv2d_gn: MDTILE_CONV_W_F16 (fp16 weight plane) outside MDTILE_PRECISION_F16 (mode %d)", mdtile_get_precision());
+        return conv_bf16x3_launch(d_x, d_w_packed, d_bias, d_residual, d_y, B, cin, cout, H, W, 0, d_coef, as_stream(stream), nullptr, 1);
+    }
     return conv_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, 0, d_coef,
                               as_stream(stream));
 }
@@ -491,12 +511,17 @@ extern "C" int mdtile_conv2d_gn_stats(const float* d_x, const float* d_coef, con
                                       float* d_var, void* d_ws, mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x && d_coef && d_w_packed && d_y && d_mean && d_var && d_ws, "mdtile_conv2d_gn_stats: null argument");
     MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && H > 0 && W > 0, "mdtile_conv2d_gn_stats: bad shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
+    MDT_CHECK_ARG(!((flags & MDTILE_CONV_W_F16) && (flags & MDTILE_CONV_EXACT_F32)),
+                  "mdtile_conv2d_gn_stats: MDTILE_CONV_W_F16 (fp16 weight plane, one fp16 MFMA per product) contradicts MDTILE_CONV_EXACT_F32 (flags=%d)", flags);
     MDT_CHECK_ARG(mdtile_conv2d_gn_stats_supported(cout, cin, ksize, flags, groups),
                   "mdtile_conv2d_gn_stats: no statistics kernel for cout=%d cin=%d ksize=%d flags=%d groups=%d (use mdtile_conv2d_gn + mdtile_gn_stats)", cout, cin, ksize, flags, groups);
     MDT_CHECK_ARG((size_t)H * W < (1u << 31), "mdtile_conv2d_gn_stats: input plane of 2^31 or more pixels");
     double* d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
     hipStream_t s = as_stream(stream);
-    const int rc = conv_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, 0, d_coef, s, d_part);
+    const int w16 = (flags & MDTILE_CONV_W_F16) ? 1 : 0;
+    MDT_CHECK_ARG(!w16 || mode_f16(), "mdtile_conv2d_gn_stats: MDTILE_CONV_W_F16 (fp16 weight plane) outside MDTILE_PRECISION_F16 (mode %d)", mdtile_get_precision());
+    const int rc = conv_bf16x3_launch(d_x, w16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, 0,
+                                      d_coef, s, d_part, w16);
     if (rc != MDTILE_OK) return rc;
     const int units = ((W + 31) / 32) * ((H + 7) / 8);
     return conv_stats_finish_launch(d_part, B, cout, (size_t)H * W, units, cout / 128, 32, groups, d_mean, d_var, d_ws, s);
@@ -527,6 +552,39 @@ extern "C" int mdtile_rec_to_f32(const void* d_rec, float* d_x, int B, int C, in
     return rec_to_f32_launch(d_rec, d_x, B, C, H, W, as_stream(stream));
 }
 
+// the two forms of a record image (include/mdtile.h): which one a producer writes is decided by the mode and by whether it activates; the caller
+// names the form it expects / holds and a disagreement is an error, never a silent reinterpretation of the bytes
+static bool rec_writes_f16(const void* coef) { return mode_f16() && coef != nullptr; }
+
+extern "C" int mdtile_rec_from_f32_fmt(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, int fmt, mdtile_stream_t stream) {
+    MDT_CHECK_ARG(d_x && d_rec, "mdtile_rec_from_f32_fmt: null argument");
+    MDT_CHECK_ARG(fmt == MDTILE_REC_BF16X2 || fmt == MDTILE_REC_F16, "mdtile_rec_from_f32_fmt: unknown record format %d", fmt);
+    MDT_CHECK_ARG(rec_image_ok(B, C, H, W), "mdtile_rec_from_f32_fmt: unsupported shape B=%d C=%d H=%d W=%d (C %% 32 == 0 required)", B, C, H, W);
+    MDT_CHECK_ARG(fmt != MDTILE_REC_F16 || rec_writes_f16(d_coef),
+                  "mdtile_rec_from_f32_fmt: record format mismatch: the fp16 form is written for an activated record (d_coef) in MDTILE_PRECISION_F16 only (mode %d, d_coef %s)",
+                  mdtile_get_precision(), d_coef ? "given" : "NULL");
+    return rec_from_f32_launch(d_x, d_coef, d_rec, B, C, H, W, as_stream(stream), fmt == MDTILE_REC_F16);
+}
+
+extern "C" int mdtile_rec_to_f32_fmt(const void* d_rec, float* d_x, int B, int C, int H, int W, int fmt, mdtile_stream_t stream) {
+    MDT_CHECK_ARG(d_x && d_rec, "mdtile_rec_to_f32_fmt: null argument");
+    MDT_CHECK_ARG(fmt == MDTILE_REC_BF16X2 || fmt == MDTILE_REC_F16, "mdtile_rec_to_f32_fmt: unknown record format %d", fmt);
+    MDT_CHECK_ARG(rec_image_ok(B, C, H, W), "mdtile_rec_to_f32_fmt: unsupported shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    return rec_to_f32_launch(d_rec, d_x, B, C, H, W, as_stream(stream), fmt == MDTILE_REC_F16);
+}
+
+// MDTILE_CONV_REC_X_F16 / _Y_F16 of a record conv call against the mode: x16 needs the mode (its kernels exist for nothing else) and a direct conv;
+// y16 must be set exactly when the call writes an activated record in MDTILE_PRECISION_F16
+static int rec_formats_ok(const char* who, int flags, int up, const void* d_y_rec, const void* d_y_coef) {
+    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0, y16 = (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0;
+    MDT_CHECK_ARG(!x16 || (mode_f16() && !up), "%s: record format mismatch: MDTILE_CONV_REC_X_F16 (fp16 input record, fp16 weight plane) needs MDTILE_PRECISION_F16 and a "
+                  "direct conv (mode %d, upsample %d)", who, mdtile_get_precision(), up);
+    const int want = (d_y_rec && rec_writes_f16(d_y_coef)) ? 1 : 0;
+    MDT_CHECK_ARG(y16 == want, "%s: record format mismatch: the call %s MDTILE_CONV_REC_Y_F16 but its record output is %s (mode %d, d_y_coef %s)", who,
+                  y16 ? "sets" : "does not set", want ? "the fp16 form" : "a bf16 split or absent", mdtile_get_precision(), d_y_coef ? "given" : "NULL");
+    return MDTILE_OK;
+}
+
 extern "C" int mdtile_conv2d_rec_supported(int cout, int cin, int ksize, int flags) {
     if (conv_force_f32() || (flags & MDTILE_CONV_EXACT_F32)) return 0;
     return conv_rec_supported(cout, cin, ksize) ? 1 : 0;
@@ -547,8 +605,10 @@ extern "C" int mdtile_conv2d_rec(const void* d_x_rec, const float* d_w_packed, c
                   "mdtile_conv2d_rec: unsupported shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
     MDT_CHECK_ARG(cout % 128 == 0 || (!up && !d_y_rec && !d_residual),
                   "mdtile_conv2d_rec: the narrow (cout < 32) kernel writes fp32 only, no residual, no upsample (cout=%d)", cout);
-    return conv_rec_launch(d_x_rec, d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, d_residual, d_y, d_y_rec, d_y_coef, B, cin, cout,
-                           H, W, up, as_stream(stream), nullptr, rec_family(flags));
+    if (const int rc = rec_formats_ok("mdtile_conv2d_rec", flags, up, d_y_rec, d_y_coef)) return rc;
+    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0;      // (then d_w_packed IS the fp16 plane)
+    return conv_rec_launch(d_x_rec, x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, d_residual, d_y, d_y_rec, d_y_coef, B, cin, cout,
+                           H, W, up, as_stream(stream), nullptr, rec_family(flags), nullptr, x16, (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0);
 }
 
 extern "C" int mdtile_conv2d_rec_stats_supported(int cout, int cin, int ksize, int flags, int groups) {
@@ -566,15 +626,17 @@ extern "C" int mdtile_conv2d_rec_stats(const void* d_x_rec, const float* d_w_pac
     MDT_CHECK_ARG(rec_image_ok(B, cin, up ? H / 2 : H, up ? W / 2 : W) && rec_image_ok(B, cout, H, W),
                   "mdtile_conv2d_rec_stats: unsupported shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
     hipStream_t s = as_stream(stream);
-    const float* w = d_w_packed + f32_packed_floats(cout, cin, 3);
+    if (const int rc = rec_formats_ok("mdtile_conv2d_rec_stats", flags, up, nullptr, nullptr)) return rc;
+    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0;
+    const float* w = x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3);
     if (rec_family(flags) == 0 && !conv_rec_stats_in_epilogue(B, cin, cout, H, W, up)) {
         // a launch of a few item rounds: the two-blocks-per-CU family gains more than the statistics pass costs (conv_rec_stats_in_epilogue)
-        const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s);
+        const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s, nullptr, 0, nullptr, x16, 0);
         return rc != MDTILE_OK ? rc : mdtile_gn_stats(d_y, B, cout, H * W, groups, d_mean, d_var, d_ws, stream);
     }
     MDT_CHECK_ARG(rec_family(flags) <= 1, "mdtile_conv2d_rec_stats: only the one-block-per-CU family leaves statistics (flags=%d)", flags);
     double* d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
-    const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s, nullptr, 1, d_part);
+    const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s, nullptr, 1, d_part, x16, 0);
     if (rc != MDTILE_OK) return rc;
     return conv_stats_finish_launch(d_part, B, cout, (size_t)H * W, conv_rec_stats_units(H, W, up), cout / 128, 32, groups, d_mean, d_var, d_ws, s);
 }
@@ -600,8 +662,9 @@ extern "C" int mdtile_upconv2d_rec_window(const void* d_x_rec, const float* d_w_
     }
     MDT_CHECK_ARG(rec_image_ok(B, cin, Hin, Win) && rec_image_ok(B, cout, 2 * h, 2 * w),
                   "mdtile_upconv2d_rec_window: unsupported shape B=%d cin=%d cout=%d Hin=%d Win=%d", B, cin, cout, Hin, Win);
+    if (const int rc = rec_formats_ok("mdtile_upconv2d_rec_window", flags, 1, d_y_rec, d_y_coef)) return rc;
     return conv_rec_launch(d_x_rec, d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, nullptr, d_y, d_y_rec, d_y_coef, B, cin, cout,
-                           2 * h, 2 * w, 1, as_stream(stream), win, rec_family(flags));
+                           2 * h, 2 * w, 1, as_stream(stream), win, rec_family(flags), nullptr, 0, (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0);
 }
 
 // ldm Downsample: y = conv3x3_stride2(pad(x, right 1, bottom 1)); output (Hin - 2) / 2 + 1 rows (likewise columns).

@@ -164,7 +164,10 @@ int conv1x1_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, h
 }
 
 int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                          int cout, size_t HW, hipStream_t s) {
+                          int cout, size_t HW, hipStream_t s, bool attn_proj) {
+    // MDTILE_PRECISION_F16: q / k / v / proj_out of the attention (the caller says so: MDTILE_CONV_ATTN_PROJ) run one-term bf16 like the attention
+    // itself; every other 1x1 conv (nin_shortcut) reads the raw stream and keeps its three terms
+    const bool one = mfma_single_term() || (attn_proj && mode_f16());
     Conv1Params P;
     P.x = d_x; P.w = (const u32x4*)d_w_rec; P.bias = d_bias; P.res = d_res; P.y = d_y;
     P.B = B; P.Cin = cin; P.Cout = cout; P.HW = HW;
@@ -175,7 +178,7 @@ int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_
         P.NCB = cout / (MT * 32);
         P.NP = cin / 32;
         dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-        if (mfma_single_term()) {      // MDTILE_PRECISION_BF16
+        if (one) {      // MDTILE_PRECISION_BF16
             if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream1t<2>, grid, block, 0, s, P);
             else hipLaunchKernelGGL(k_conv1x1_stream1t<4>, grid, block, 0, s, P);
         } else if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream<2>, grid, block, 0, s, P);
@@ -188,7 +191,7 @@ int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_
     P.NCB = round_up1(cout, MT * 32) / (MT * 32);
     P.NP = cin / 32;
     dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-    if (mfma_single_term()) {
+    if (one) {
         if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x1<8, 256>), grid, block, 0, s, P);
         else if (MT == 4) hipLaunchKernelGGL((k_conv1x1_bf16x1<4, 128>), grid, block, 0, s, P);
         else hipLaunchKernelGGL((k_conv1x1_bf16x1<2, 256>), grid, block, 0, s, P);

@@ -22,6 +22,7 @@
 // the next phase's weights (24 KB, L2-resident) and the next K-step's input slab are fetched into registers at the start
 // of a phase and written to the other LDS stage at its end (fp32 -> hi/lo split happens on that write).
 #include "common.h"
+#include "f16_convert.h"
 
 using namespace mdt;
 
@@ -85,6 +86,7 @@ __device__ __host__ __forceinline__ int kstep_cj(int j, int perm) { return perm 
 // scripts/tilevae.py:207-215, 300-307) also leaves the statistics of that output: every block writes (sum, sum of squares) of its
 // BM couts x 8 x 32 px in 4-cout quads -- gn_part[(b * ptiles + ptile) * NCB + cb][BM / 4][2] fp64, combined in a fixed order by
 // k_conv_stats_partial / k_gn_final (vae_norm.hip): the separate pass that re-read the whole activation is gone.  y is bit-identical.
+#define MDT_OPERAND_F16 0      // mfma_operand.h: bf16 fragments
 #define MDT_B3_TERMS 3
 #define MDT_B3_KERNEL k_conv3x3_bf16x3
 #include "vae_conv_bf16x3_direct_body.h"
@@ -95,6 +97,17 @@ __device__ __host__ __forceinline__ int kstep_cj(int j, int perm) { return perm 
 #include "vae_conv_bf16x3_direct_body.h"
 #undef MDT_B3_KERNEL
 #undef MDT_B3_TERMS
+
+// fp16 form (MDTILE_PRECISION_F16): launched only with the fused pre-activation (GNS) -- the one operand this family can prove normalised
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 1
+#define MDT_B3_TERMS 1
+#define MDT_B3_KERNEL k_conv3x3_f16
+#include "vae_conv_bf16x3_direct_body.h"
+#undef MDT_B3_KERNEL
+#undef MDT_B3_TERMS
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 0
 
 // OIHW fp32 -> records [cb][k][dy][hl][dx][mt][lane] of 8 bf16:  cout = cb*BM + mt*32 + (lane & 31),
 // cin = k*16 + (lane >> 5)*8 + j,  tap = (dy, dx);  hl = 0: bf16(w), hl = 1: bf16(w - hi).  Zero outside [Cout) x [Cin).
@@ -122,6 +135,33 @@ __global__ void k_conv_pack_bf16x3(const float* __restrict__ w, u32x4* __restric
     out[i] = __builtin_bit_cast(u32x4, o);
 }
 
+// fp16 weight plane (MDTILE_PRECISION_F16): fp16_rn(w) in the layout and K order of k_conv_pack_bf16x3's hi plane -- the same record array
+// [cb][k][dy][hl][dx][mt][lane], hl = 0: 8 fp16, hl = 1: zeros (the one-term kernels DMA both halves of a chunk and read the first), so the
+// fp16 kernels address it exactly as their bf16 twins address the split image.  Source: the fp32 image [tap][cin][CoutP] at the head of the
+// packed buffer of mdtile_conv_pack (the exact weights), so the plane can be built long after the OIHW tensor is gone.
+__global__ void k_conv_pack_f16(const float* __restrict__ wp, u32x4* __restrict__ out, int Cout, int Cin, int CoutP, int MT, int NCB, int NK, int perm) {
+    const size_t n = (size_t)NCB * NK * 3 * 2 * 3 * MT * 64;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    size_t r = i;
+    const int lane = (int)(r % 64); r /= 64;
+    const int mt = (int)(r % MT); r /= MT;
+    const int dx = (int)(r % 3); r /= 3;
+    const int hl = (int)(r % 2); r /= 2;
+    const int dy = (int)(r % 3); r /= 3;
+    const int k = (int)(r % NK); r /= NK;
+    const int cb = (int)r;
+    const int co = cb * MT * 32 + mt * 32 + (lane & 31);
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ci = kstep_c0(k, lane >> 5, perm) + kstep_cj(j, perm);
+        v[j] = (hl == 0 && co < Cout && ci < Cin) ? wp[((size_t)(dy * 3 + dx) * Cin + ci) * CoutP + co] : 0.0f;
+    }
+    u32x4 o;
+    cvt8h(v, o);
+    out[i] = o;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Fused nearest-2x upsample + 3x3 conv as FOUR 2x2 convs on the un-upsampled input ("sub-pixel" form): 2.25x fewer MACs.
@@ -234,6 +274,22 @@ int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, 
     return MDTILE_OK;
 }
 
+// fp16 weight plane of a 3x3 conv the record / hand-over kernels take: the size and geometry of the direct records of the split image
+size_t conv_f16_plane_floats(int cout, int cin) {
+    if (conv_rec_narrow_eligible(cout, cin, 3)) return conv_rec_narrow_packed_floats(cin);
+    return conv_bf16x3_eligible(cout, cin, 3) ? conv_bf16x3_direct_records(cout, cin) * 4 : 0;
+}
+int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s) {
+    const bool narrow = conv_rec_narrow_eligible(cout, cin, 3);
+    const int MT = narrow ? 1 : conv_bf16x3_mt(cout), NCB = narrow ? 1 : round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
+    const int perm = narrow ? 1 : conv_bf16x3_perm(cin);
+    const size_t n = (size_t)NCB * NK * 3 * 2 * 3 * MT * 64;
+    hipLaunchKernelGGL(k_conv_pack_f16, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_f32img, (u32x4*)d_out, cout, cin, round_up_i(cout, 32), MT, NCB, NK,
+                       perm);
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
 bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up) {
     return conv_bf16x3_eligible(cout, cin, ksize) && !up && cin <= MAX_GN_CIN;
 }
@@ -248,7 +304,9 @@ size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W) {
 }
 
 int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part) {
+                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part, int w16) {
+    // w16 (MDTILE_PRECISION_F16, fused pre-activation only): d_w_rec is the fp16 weight plane -> k_conv3x3_f16
+    MDT_CHECK_ARG(!w16 || (d_coef && !up), "conv_bf16x3_launch: the fp16 form exists for the fused pre-activation conv only");
     ConvBParams P;
     P.perm = conv_bf16x3_perm(cin);
     P.coef = d_coef;
@@ -277,7 +335,11 @@ int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bia
     P.ptiles = P.PX * ((H + TH - 1) / TH);
     dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B);
     MDT_CHECK_ARG(!d_part || (MT == 4 && d_coef && cout % 128 == 0), "conv_bf16x3_launch: no statistics kernel for cout=%d", cout);
-    if (mfma_single_term()) {      // MDTILE_PRECISION_BF16: the one-term forms of the same instantiations
+    if (w16) {
+        if (MT == 4 && d_part) hipLaunchKernelGGL((k_conv3x3_f16<4, true, 1, true>), grid, block, 0, s, P);
+        else if (MT == 4) hipLaunchKernelGGL((k_conv3x3_f16<4, true>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_conv3x3_f16<2, true>), grid, block, 0, s, P);
+    } else if (mfma_single_term()) {      // MDTILE_PRECISION_BF16: the one-term forms of the same instantiations
         if (MT == 4) {
             if (d_coef && d_part) hipLaunchKernelGGL((k_conv3x3_bf16x1<4, true, 1, true>), grid, block, 0, s, P);
             else if (d_coef) hipLaunchKernelGGL((k_conv3x3_bf16x1<4, true>), grid, block, 0, s, P);

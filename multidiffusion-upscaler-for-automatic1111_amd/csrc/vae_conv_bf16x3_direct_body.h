@@ -1,6 +1,9 @@
 // Body of k_conv3x3_bf16x3 / k_conv3x3_bf16x1 (csrc/vae_conv_bf16x3.hip includes this file twice, the way vae_conv_rec.hip shares its bodies):
 //   MDT_B3_TERMS = 3: the three-term kernel; = 1: MDTILE_PRECISION_BF16, w_hi x x_hi only.  The one-term form still splits and stages both
 //   planes of its input (the LDS images and the load / store schedule are the three-term kernel's); it reads only the hi fragments.
+//   MDT_OPERAND_F16 = 1 (with MDT_B3_TERMS = 1; k_conv3x3_f16, MDTILE_PRECISION_F16, GNS forms only): the activated input is rounded to fp16 while it is
+//   staged (clamp to +-65504, v_cvt_pk_f16_f32; only the hi image is written) and the weights are the fp16 plane of mdtile_conv_pack_f16
+#include "mfma_operand.h"
 template <int MT, bool GNS, int S = 1, bool ST = false>
 __global__ __launch_bounds__(512, (MT == 4 && S == 1) ? 4 : 2) void MDT_B3_KERNEL(const ConvBParams P) {
     constexpr int NT = MDT_B3_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), weight planes read
@@ -102,12 +105,18 @@ __global__ __launch_bounds__(512, (MT == 4 && S == 1) ? 4 : 2) void MDT_B3_KERNE
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = rin[i][j] * smask[i];
                 }
+#if MDT_OPERAND_F16
+                u32x4 hi;
+                cvt8h(v, hi);
+                if (tid + 512 * i < IN_REC_) dst[tid + 512 * i] = hi;
+#else
                 u32x4 hi, lo;
                 split8(v, hi, lo);
                 if (tid + 512 * i < IN_REC_) {
                     dst[tid + 512 * i] = hi;
                     dst[IN_REC_ + tid + 512 * i] = lo;
                 }
+#endif
             }
         }
     };
@@ -159,21 +168,21 @@ __global__ __launch_bounds__(512, (MT == 4 && S == 1) ? 4 : 2) void MDT_B3_KERNE
         const u32x4* ist = in_l + (IB1 ? 0 : (k & 1)) * IN_STAGE;
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
-            bf16x8 a[2][2];   // [m][hl]
+            MDT_FRAG a[2][2];   // [m][hl]
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int hl = 0; hl < NHL; ++hl) {
-                    a[m][hl] = __builtin_bit_cast(bf16x8, wst[((hl * 3 + dx) * MT + wm * 2 + m) * 64 + lane]);
+                    a[m][hl] = __builtin_bit_cast(MDT_FRAG, wst[((hl * 3 + dx) * MT + wm * 2 + m) * 64 + lane]);
                 }
             if (TERM_MAJOR) {
-                bf16x8 bh[NROW], bl[NROW];
+                MDT_FRAG bh[NROW], bl[NROW];
 #pragma unroll
                 for (int n = 0; n < NROW; ++n) {
                     const int rec = S == 1 ? (kg * ROWS_ + wr * NROW + n + dy) * COLS + l31 + dx
                                            : (kg * ROWS_ + 2 * (wr * NROW + n) + dy) * COLSL + (dx & 1) * HCOL + l31 + (dx >> 1);
-                    bh[n] = __builtin_bit_cast(bf16x8, ist[rec]);
-                    bl[n] = NT == 3 ? __builtin_bit_cast(bf16x8, ist[IN_REC_ + rec]) : bh[n];
+                    bh[n] = __builtin_bit_cast(MDT_FRAG, ist[rec]);
+                    bl[n] = NT == 3 ? __builtin_bit_cast(MDT_FRAG, ist[IN_REC_ + rec]) : bh[n];
                 }
 #pragma unroll
                 for (int t = 3 - NT; t < 3; ++t) {
@@ -181,7 +190,7 @@ __global__ __launch_bounds__(512, (MT == 4 && S == 1) ? 4 : 2) void MDT_B3_KERNE
                     for (int n = 0; n < NROW; ++n)
 #pragma unroll
                         for (int m = 0; m < 2; ++m)
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][t == 0 ? 1 : 0], t == 1 ? bl[n] : bh[n], acc[m][n], 0, 0, 0);
+                            acc[m][n] = MDT_MFMA(a[m][t == 0 ? 1 : 0], t == 1 ? bl[n] : bh[n], acc[m][n], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0x07F7);   // everything but MFMAs may cross: keeps the term-major order
                 }
             } else {
@@ -189,14 +198,14 @@ __global__ __launch_bounds__(512, (MT == 4 && S == 1) ? 4 : 2) void MDT_B3_KERNE
                 for (int n = 0; n < NROW; ++n) {
                     const int rec = S == 1 ? (kg * ROWS_ + wr * NROW + n + dy) * COLS + l31 + dx
                                            : (kg * ROWS_ + 2 * (wr * NROW + n) + dy) * COLSL + (dx & 1) * HCOL + l31 + (dx >> 1);
-                    const bf16x8 bh = __builtin_bit_cast(bf16x8, ist[rec]), bl = NT == 3 ? __builtin_bit_cast(bf16x8, ist[IN_REC_ + rec]) : bh;
+                    const MDT_FRAG bh = __builtin_bit_cast(MDT_FRAG, ist[rec]), bl = NT == 3 ? __builtin_bit_cast(MDT_FRAG, ist[IN_REC_ + rec]) : bh;
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
                         if constexpr (NT == 3) {
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], bh, acc[m][n], 0, 0, 0);   // w_lo * x_hi
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bl, acc[m][n], 0, 0, 0);   // w_hi * x_lo
+                            acc[m][n] = MDT_MFMA(a[m][1], bh, acc[m][n], 0, 0, 0);   // w_lo * x_hi
+                            acc[m][n] = MDT_MFMA(a[m][0], bl, acc[m][n], 0, 0, 0);   // w_hi * x_lo
                         }
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bh, acc[m][n], 0, 0, 0);   // w_hi * x_hi
+                        acc[m][n] = MDT_MFMA(a[m][0], bh, acc[m][n], 0, 0, 0);   // w_hi * x_hi
                     }
                 }
             }

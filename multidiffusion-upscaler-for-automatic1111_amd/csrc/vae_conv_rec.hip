@@ -64,6 +64,8 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
     while (__builtin_amdgcn_s_memrealtime() - t0 < d) __builtin_amdgcn_s_sleep(32);
 }
 
+#define MDT_OPERAND_F16 0      // mfma_operand.h: bf16 fragments
+#define MDT_REC_OUT16 0        // epilogue_item<.., R16>: the record output is a bf16 (hi, lo) split
 #define MDT_REC_TERMS 3
 #define MDT_REC_KERNEL k_conv3x3_rec
 #define MDT_REC_ST 0
@@ -89,6 +91,35 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
 #undef MDT_REC_KERNEL
 #undef MDT_REC_ST
 #undef MDT_REC_TERMS
+
+// fp16 forms (MDTILE_PRECISION_F16): the one-term text on v_mfma_f32_32x32x16_f16.  The input is an ACTIVATED record image in its fp16 form
+// (fp16(x) in the hi half, include/mdtile.h), the weights the fp16 plane of mdtile_conv_pack_f16 (the hi-plane layout of the bf16 image).
+//   k_conv3x3_rec_f16      record output in the fp16 form (the next norm's (a, s) + SiLU applied: P.coef != null)
+//   k_conv3x3_rec_f16s     record output, if any, a bf16 split (a raw record for an upsample conv) -- also the fp32-only launches and conv_out
+//   k_conv3x3_rec_f16_st   + statistics (fp32 output only)
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 1
+#define MDT_REC_TERMS 1
+#define MDT_REC_ST 0
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 1
+#define MDT_REC_KERNEL k_conv3x3_rec_f16
+#include "vae_conv_rec_direct_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 0
+#define MDT_REC_KERNEL k_conv3x3_rec_f16s
+#include "vae_conv_rec_direct_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#define MDT_REC_KERNEL k_conv3x3_rec_f16_st
+#define MDT_REC_ST 1
+#include "vae_conv_rec_direct_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#undef MDT_REC_TERMS
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 0
 
 // =====================================================================================================================
 // nearest-2x upsample + 3x3 conv in sub-pixel form (four 2x2 convs on the un-upsampled grid, see vae_conv_bf16x3.hip
@@ -124,6 +155,20 @@ __device__ __forceinline__ void stagger_start(const ConvRParams& P, int wave) {
 #undef MDT_REC_ST
 #undef MDT_REC_TERMS
 
+// MDTILE_PRECISION_F16: an upsample conv reads the raw residual stream, so it stays on the three-term bf16 MFMAs; its record output, when
+// activated, is written in the fp16 form (the whole-image and the window entry share this kernel)
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 1
+#define MDT_REC_TERMS 3
+#define MDT_REC_KERNEL k_upconv_rec_o16
+#define MDT_REC_ST 0
+#include "vae_conv_rec_upconv_body.h"
+#undef MDT_REC_KERNEL
+#undef MDT_REC_ST
+#undef MDT_REC_TERMS
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 0
+
 // =====================================================================================================================
 // fp32 NCHW -> record image (+ optional fixed-statistics GroupNorm + SiLU): entry points of the record path (conv_in /
 // attention outputs, the fast-mode estimator and slow mode, where the statistics only exist after the producer ran).
@@ -154,6 +199,46 @@ __global__ __launch_bounds__(256) void k_rec_from_f32(const float* __restrict__ 
     }
     *hi_p = hi;
     *lo_p = lo;
+}
+
+// the fp16 form of an activated record image (MDTILE_PRECISION_F16): fp16_rn(clamp(silu(a x + s), +-65504)) in the hi half, zero border in
+// the hi half only, the lo half is not written
+__global__ __launch_bounds__(256) void k_rec_from_f32_f16(const float* __restrict__ x, const float* __restrict__ coef, u32x4* __restrict__ rec,
+                                                          int C, int H, int W) {
+    const int Wp = rec_pitch(W), Hp = H + 2, Pn = C >> 3;
+    const int px = blockIdx.x * 256 + threadIdx.x, py = blockIdx.y;
+    const int bp = blockIdx.z, b = bp / Pn, p = bp - b * Pn;
+    if (px >= W + 2) return;
+    const size_t planeO = (size_t)Hp * Wp;
+    u32x4 hi = {0u, 0u, 0u, 0u};
+    if (px >= 1 && px <= W && py >= 1 && py <= H) {
+        const int ks = p >> 1, g = p & 1;
+        const int c0 = 32 * (ks >> 1) + 16 * (ks & 1) + 4 * g;
+        const float* src = x + ((size_t)b * C + c0) * H * W + (size_t)(py - 1) * W + (px - 1);
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int cc = (j & 3) + 8 * (j >> 2);
+            v[j] = silu_f(fmaf(src[(size_t)cc * H * W], coef[(size_t)b * 2 * C + c0 + cc], coef[(size_t)b * 2 * C + C + c0 + cc]));
+        }
+        cvt8h(v, hi);
+    }
+    rec[((size_t)b * 2 * Pn + p) * planeO + (size_t)py * Wp + px + REC_COL0] = hi;
+}
+
+// fp16 record image -> fp32 NCHW (exact: every fp16 is an fp32)
+__global__ __launch_bounds__(256) void k_rec_to_f32_f16(const u32x4* __restrict__ rec, float* __restrict__ x, int C, int H, int W) {
+    const int Wp = rec_pitch(W), Hp = H + 2, Pn = C >> 3;
+    const int px = blockIdx.x * 256 + threadIdx.x, py = blockIdx.y;
+    const int bp = blockIdx.z, b = bp / Pn, p = bp - b * Pn;
+    if (px >= W) return;
+    const size_t planeO = (size_t)Hp * Wp;
+    const f16x8 h = __builtin_bit_cast(f16x8, rec[((size_t)b * 2 * Pn + p) * planeO + (size_t)(py + 1) * Wp + (px + 1 + REC_COL0)]);
+    const int ks = p >> 1, g = p & 1;
+    const int c0 = 32 * (ks >> 1) + 16 * (ks & 1) + 4 * g;
+    float* dst = x + ((size_t)b * C + c0) * H * W + (size_t)py * W + px;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[(size_t)((j & 3) + 8 * (j >> 2)) * H * W] = (float)h[j];
 }
 
 // record image -> fp32 NCHW (hi + lo): inspection / tests
@@ -203,7 +288,7 @@ static int num_cus() {
 }
 
 // vae_conv_rec2.hip: the two-blocks-per-CU form of the cout % 128 == 0 kernels
-int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus);
+int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, int x16 = 0, int y16 = 0);
 // probes/csrc/vae_conv_recd.hip (PROBES twin of the library only -- a measured, rejected form: DESIGN.md / docs/history/r5.md): 64-cout items with
 // the epilogue dripped into the next item's K loop (direct 3x3, cin % 32 == 0, cin >= 128).  Declared here, defined only in that build: the one
 // call sits in a discarded `if constexpr (kProbes)` statement, so the shipping library neither references nor carries the kernel.
@@ -238,16 +323,18 @@ size_t rec_image_bytes(int B, int C, int H, int W) { return (size_t)B * C * (H +
 
 size_t rec_plane_records(int H, int W) { return (size_t)(H + 2) * rec_pitch(W); }
 
-int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s) {
+int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16) {
     dim3 grid(cdiv(W + 2, 256), H + 2, B * (C / 8));
-    hipLaunchKernelGGL(k_rec_from_f32, grid, dim3(256), 0, s, d_x, d_coef, (u32x4*)d_rec, C, H, W);
+    if (f16) hipLaunchKernelGGL(k_rec_from_f32_f16, grid, dim3(256), 0, s, d_x, d_coef, (u32x4*)d_rec, C, H, W);
+    else hipLaunchKernelGGL(k_rec_from_f32, grid, dim3(256), 0, s, d_x, d_coef, (u32x4*)d_rec, C, H, W);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
 
-int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s) {
+int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16) {
     dim3 grid(cdiv(W, 256), H, B * (C / 8));
-    hipLaunchKernelGGL(k_rec_to_f32, grid, dim3(256), 0, s, (const u32x4*)d_rec, d_x, C, H, W);
+    if (f16) hipLaunchKernelGGL(k_rec_to_f32_f16, grid, dim3(256), 0, s, (const u32x4*)d_rec, d_x, C, H, W);
+    else hipLaunchKernelGGL(k_rec_to_f32, grid, dim3(256), 0, s, (const u32x4*)d_rec, d_x, C, H, W);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -273,7 +360,10 @@ int conv_rec_stats_units(int H, int W, int up) {
 
 int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y32, void* d_yrec,
                     const float* d_ycoef, int B, int cin, int cout, int H, int W, int up, hipStream_t s, const int* win, int family,
-                    double* d_part) {
+                    double* d_part, int x16, int y16) {
+    // x16 (MDTILE_PRECISION_F16): d_xrec is an activated record image in its fp16 form and d_w_rec the fp16 weight plane -> the fp16 kernels;
+    // y16: the (activated) record output is written in the fp16 form.  The C entry points have checked both against the mode.
+    MDT_CHECK_ARG(!(x16 && up) && !(y16 && !(d_yrec && d_ycoef)) && !(y16 && d_part), "conv_rec_launch: fp16 record forms: x16=%d up=%d y16=%d", x16, up, y16);
     ConvRParams P;
     P.gn_part = d_part;
     if (d_part) {
@@ -298,7 +388,7 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
         if (const char* e = probe_env("MDTILE_REC_STAMPS")) P.census = reinterpret_cast<unsigned*>((uintptr_t)strtoull(e, nullptr, 16));
     if (up) P.w = (const u32x4*)d_w_rec + conv_bf16x3_direct_records(cout, cin);
     if constexpr (kProbes) {
-        if (family == 3) {      // a NAMED family is honoured or refused, never silently replaced by the cost model
+        if (family == 3 && !x16 && !y16) {      // a NAMED family is honoured or refused, never silently replaced by the cost model
             MDT_CHECK_ARG(!up && !win && !d_part && conv_recd_supported(cout, cin), "conv_rec_launch: the dripped-epilogue kernel takes direct 3x3 convs with cin %% 32 == 0, "
                           "cin >= 128, cout %% 128 == 0, no window, no statistics (cout=%d cin=%d up=%d)", cout, cin, up);
             return conv_recd_launch(P, B, s, num_cus());
@@ -310,7 +400,7 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
         const long long px = (win + 31) / 32;
         const long long items16 = (px * ((hin + (up ? 7 : 15)) / (up ? 8 : 16)) + 7) / 8 * 8 * per * B;
         const long long items8 = (px * ((hin + (up ? 3 : 7)) / (up ? 4 : 8)) + 7) / 8 * 8 * per * B;
-        if (rec_two_blocks(items16, items8, cus, up, family)) return conv_rec2_launch(P, B, up, s, num_cus());
+        if (rec_two_blocks(items16, items8, cus, up, family)) return conv_rec2_launch(P, B, up, s, num_cus(), x16, y16);
     }
     // start-up stagger (stagger_start): spread = MDTILE_REC_STAGGER_PCT percent of an estimated item period, launches of >= 6 rounds only
     // default: a quarter period for launches that write records ONLY (a conv1: -2 ... -5 % per launch, profiles/r4u, r4v; launches with an fp32
@@ -327,7 +417,8 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
         const int cus = num_cus();
         stagger(items, cus, (unsigned)P.NK * 400u + 2000u);
         dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-        if (mfma_single_term()) {
+        if (y16) hipLaunchKernelGGL(k_upconv_rec_o16, grid, block, 0, s, P);
+        else if (mfma_single_term()) {
             if (d_part) hipLaunchKernelGGL(k_upconv_rec1t_st, grid, block, 0, s, P);
             else hipLaunchKernelGGL(k_upconv_rec1t, grid, block, 0, s, P);
         } else {
@@ -343,7 +434,12 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
     const int cus = num_cus();                    // one block per CU (155 KB LDS, 2 waves per SIMD)
     if (cout % 128 == 0) stagger(items, cus, (unsigned)P.NK * 900u + 1500u);
     dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-    if (mfma_single_term()) {
+    if (x16) {
+        if (d_part) hipLaunchKernelGGL((k_conv3x3_rec_f16_st<2, 2, 4>), grid, block, 0, s, P);
+        else if (cout % 128 != 0) hipLaunchKernelGGL((k_conv3x3_rec_f16s<1, 1, 2>), grid, block, 0, s, P);
+        else if (y16) hipLaunchKernelGGL((k_conv3x3_rec_f16<2, 2, 4>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_conv3x3_rec_f16s<2, 2, 4>), grid, block, 0, s, P);
+    } else if (mfma_single_term()) {
         if (d_part) hipLaunchKernelGGL((k_conv3x3_rec1t_st<2, 2, 4>), grid, block, 0, s, P);
         else if (cout % 128 == 0) hipLaunchKernelGGL((k_conv3x3_rec1t<2, 2, 4>), grid, block, 0, s, P);
         else hipLaunchKernelGGL((k_conv3x3_rec1t<1, 1, 2>), grid, block, 0, s, P);

@@ -90,6 +90,8 @@ __device__ __forceinline__ void startup_skew(const ConvRParams& P, int wave, int
 // runs on across items: r0' = (r0 + 9 NK) & 3); K-step k uses input stage k & 1 (NK is even: every item starts in stage 0).
 // One step of a wave:   fx(t, h=1) <- LDS | 12 MFMAs (rows 0-1) | vmcnt(N) + barrier | DMA requests |
 //                       fw(t+1), fx(t+1, h=0) <- LDS | 12 MFMAs (rows 2-3)
+#define MDT_OPERAND_F16 0      // mfma_operand.h: bf16 fragments
+#define MDT_REC_OUT16 0        // epilogue_item<.., R16>: the record output is a bf16 (hi, lo) split
 #define MDT_REC2_TERMS 3
 #define MDT_REC2_KERNEL k_conv3x3_rec2
 #include "vae_conv_rec2_direct_body.h"
@@ -100,6 +102,23 @@ __device__ __forceinline__ void startup_skew(const ConvRParams& P, int wave, int
 #include "vae_conv_rec2_direct_body.h"
 #undef MDT_REC2_KERNEL
 #undef MDT_REC2_TERMS
+// fp16 forms (MDTILE_PRECISION_F16, see vae_conv_rec.hip): fp16 input record + fp16 weight plane; record output fp16 (_f16) or a bf16 split / none (_f16s)
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 1
+#define MDT_REC2_TERMS 1
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 1
+#define MDT_REC2_KERNEL k_conv3x3_rec2_f16
+#include "vae_conv_rec2_direct_body.h"
+#undef MDT_REC2_KERNEL
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 0
+#define MDT_REC2_KERNEL k_conv3x3_rec2_f16s
+#include "vae_conv_rec2_direct_body.h"
+#undef MDT_REC2_KERNEL
+#undef MDT_REC2_TERMS
+#undef MDT_OPERAND_F16
+#define MDT_OPERAND_F16 0
 
 // =====================================================================================================================
 // nearest-2x upsample + 3x3 conv in sub-pixel form (vae_conv_rec.hip: k_upconv_rec; derivation in vae_conv_bf16x3.hip), two blocks
@@ -124,6 +143,16 @@ __device__ __forceinline__ int wrap6(int x) { return x >= 6 ? x - 6 : x; }
 #include "vae_conv_rec2_upconv_body.h"
 #undef MDT_REC2_KERNEL
 #undef MDT_REC2_TERMS
+// MDTILE_PRECISION_F16: the three-term upsample conv (raw-stream operand) with its activated record output in the fp16 form
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 1
+#define MDT_REC2_TERMS 3
+#define MDT_REC2_KERNEL k_upconv_rec2_o16
+#include "vae_conv_rec2_upconv_body.h"
+#undef MDT_REC2_KERNEL
+#undef MDT_REC2_TERMS
+#undef MDT_REC_OUT16
+#define MDT_REC_OUT16 0
 
 }  // namespace
 
@@ -160,7 +189,7 @@ static unsigned* cu_counters(unsigned* epoch) {
 //   MDTILE_REC2_SKEW    0 = no start-up delay, 1 = by block index (>= grid / 2), 2 = by the per-CU arrival counter (default)
 //   MDTILE_REC2_SKEW_PCT  the delay as a percentage of an item's K loop at one block per CU-half (default 100)
 //   MDTILE_REC2_CENSUS  device address (hex) of a [grid] unsigned buffer that receives every block's hardware CU id
-int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus) {
+int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, int x16, int y16) {
     int skew = 2, pct = 100;
     if (const char* e = probe_env("MDTILE_REC2_SKEW")) skew = atoi(e);
     if (const char* e = probe_env("MDTILE_REC2_SKEW_PCT")) pct = atoi(e);
@@ -171,7 +200,8 @@ int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus) {
     int per_cu = 2;                                   // two blocks per CU
     if (const char* e = probe_env("MDTILE_REC2_PER_CU")) per_cu = atoi(e) == 1 ? 1 : 2;      // probing: a 4-wave block alone on its CU
     const int grid_max = per_cu * (cus / 8 * 8);
-    const bool one = mfma_single_term();             // MDTILE_PRECISION_BF16: the one-term kernels, a third of the MFMAs per step
+    // MDTILE_PRECISION_BF16: the one-term kernels, a third of the MFMAs per step; x16: the fp16 kernels (one term as well), never the upsample conv
+    const bool one = up ? (mfma_single_term() && !y16) : (mfma_single_term() || x16);
     if (up) {
         // K loop of one item with the SIMDs to itself: NK x 8 steps x 12 MFMAs x 32 clk at ~2 GHz = NK x 1.5 us; in 10 ns ticks
         P.skew_ticks = skew ? (unsigned)((long long)P.NK * 154 * pct / (one ? 300 : 100)) : 0u;
@@ -179,7 +209,8 @@ int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus) {
         P.ptiles = P.PX * ((P.Hin + 3) / 4);
         const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * 2 * B;
         dim3 grid((unsigned)(items < grid_max ? items : grid_max)), block(256);
-        if (one) hipLaunchKernelGGL(k_upconv_rec2_1t, grid, block, 0, s, P);
+        if (y16) hipLaunchKernelGGL(k_upconv_rec2_o16, grid, block, 0, s, P);
+        else if (one) hipLaunchKernelGGL(k_upconv_rec2_1t, grid, block, 0, s, P);
         else hipLaunchKernelGGL(k_upconv_rec2, grid, block, 0, s, P);
         MDT_LAUNCH_CHECK();
         return MDTILE_OK;
@@ -190,7 +221,9 @@ int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus) {
     P.ptiles = P.PX * ((P.H + 7) / 8);
     const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * B;
     dim3 grid((unsigned)(items < grid_max ? items : grid_max)), block(256);
-    if (one) hipLaunchKernelGGL((k_conv3x3_rec2_1t<2, 2, 4>), grid, block, 0, s, P);
+    if (x16 && y16) hipLaunchKernelGGL((k_conv3x3_rec2_f16<2, 2, 4>), grid, block, 0, s, P);
+    else if (x16) hipLaunchKernelGGL((k_conv3x3_rec2_f16s<2, 2, 4>), grid, block, 0, s, P);
+    else if (one) hipLaunchKernelGGL((k_conv3x3_rec2_1t<2, 2, 4>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((k_conv3x3_rec2<2, 2, 4>), grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;

@@ -1,6 +1,8 @@
 // Body of k_conv3x3_rec2 / k_conv3x3_rec2_1t (csrc/vae_conv_rec2.hip includes this file twice, the way vae_conv_rec.hip shares its bodies):
 //   MDT_REC2_TERMS = 3: the three-term kernel (w_lo x_hi, w_hi x_lo, w_hi x_hi per product); = 1: MDTILE_PRECISION_BF16, w_hi x x_hi only and
 //   only the hi fragments read -- the DMA pieces (lo planes included), ring slots and counted waits of every step are the three-term kernel's.
+//   MDT_OPERAND_F16 = 1 (one-term only; k_conv3x3_rec2_f16 / _f16s, MDTILE_PRECISION_F16): fp16 fragments and MFMA; MDT_REC_OUT16 = 1: fp16 record-out epilogue
+#include "mfma_operand.h"
 template <int MW, int WM, int NROW>
 __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
     constexpr int NT = MDT_REC2_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), planes read
@@ -86,8 +88,8 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
         }
     };
 
-    bf16x8 fw[2][MW][2];   // [set][m][hl]
-    bf16x8 fx[2][HN][2];   // [set = half-step][row][hl]
+    MDT_FRAG fw[2][MW][2];   // [set][m][hl]
+    MDT_FRAG fx[2][HN][2];   // [set = half-step][row][hl]
     const int wfrag = wm * MW * 64 + lane;                       // + slot*W_STEP + (hl*MT + m)*64
     const int xfrag = (kg * ROWS + wr * NROW) * COLS + l31;      // + stage*PAD + hl*HALF_PAD + (n + dy)*COLS + dx
     auto load_fw = [&](int set, int slot) {
@@ -95,14 +97,14 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[(hl * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(MDT_FRAG, wst[(hl * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int stage, int dy, int dx, int h) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + (dy + h * HN) * COLS + dx;
 #pragma unroll
         for (int n = 0; n < HN; ++n)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(MDT_FRAG, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     Item2 cur, nxt;
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
                     for (int n = 0; n < HN; ++n)
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
-                            acc[m][n][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][term == 0 ? 1 : 0], fx[0][n][term == 1 ? 1 : 0],
+                            acc[m][n][0] = MDT_MFMA(fw[ws][m][term == 0 ? 1 : 0], fx[0][n][term == 1 ? 1 : 0],
                                                                                    acc[m][n][0], 0, 0, 0);   // w_lo x_hi, w_hi x_lo, w_hi x_hi
                 MDT_PIN();
                 // ---- the barrier of step t publishes chunk t+1 (and, at s = 8, the input stage of the next K-step).  Requested by
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
                     for (int n = 0; n < HN; ++n)
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
-                            acc[m][HN + n][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][term == 0 ? 1 : 0], fx[1][n][term == 1 ? 1 : 0],
+                            acc[m][HN + n][0] = MDT_MFMA(fw[ws][m][term == 0 ? 1 : 0], fx[1][n][term == 1 ? 1 : 0],
                                                                                         acc[m][HN + n][0], 0, 0, 0);
                 MDT_PIN();
             }
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int n = 0; n < NROW; ++n) ys[n] = cur.y0 + wr * NROW + n;
         if (!(pdbg(P.dbg) & 1)) {
-            epilogue_item<1, NROW, MW, 32>(E, ec_l + par * EC2, acc, wm * MW, cur.cb * MT + wm * MW, ys, x, x < P.W, res_rows(nxt, has_next));
+            epilogue_item<1, NROW, MW, 32, false, MDT_REC_OUT16 != 0>(E, ec_l + par * EC2, acc, wm * MW, cur.cb * MT + wm * MW, ys, x, x < P.W, res_rows(nxt, has_next));
         }
         if (!has_next) break;
         work = work_n;

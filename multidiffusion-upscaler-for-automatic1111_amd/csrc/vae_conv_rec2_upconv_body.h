@@ -1,6 +1,8 @@
 // Body of k_upconv_rec2 / k_upconv_rec2_1t (csrc/vae_conv_rec2.hip includes this file twice, the way vae_conv_rec.hip shares its bodies):
 //   MDT_REC2_TERMS = 3: the three-term kernel (w_lo x_hi, w_hi x_lo, w_hi x_hi per product); = 1: MDTILE_PRECISION_BF16, w_hi x x_hi only and
 //   only the hi fragments read -- the DMA pieces (lo planes included), ring slots and counted waits of every step are the three-term kernel's.
+// MDT_REC_OUT16 = 1 (k_upconv_rec_o16 / k_upconv_rec2_o16, MDTILE_PRECISION_F16): the three-term kernel with the fp16 record-out epilogue (R16)
+#include "mfma_operand.h"
 __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
     constexpr int NT = MDT_REC2_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), planes read
     constexpr int MT = 4, MW = 2, WM = 2, NROW = 2, TH = 4, R = 6;
@@ -84,22 +86,22 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
         }
     };
 
-    bf16x8 fw[2][MW][2];     // [set][m][hl]   weight tiles of one combo-step
-    bf16x8 fx[2][NROW][2];   // [set][n][hl]   input rows of one column shift
+    MDT_FRAG fw[2][MW][2];     // [set][m][hl]   weight tiles of one combo-step
+    MDT_FRAG fx[2][NROW][2];   // [set][n][hl]   input rows of one column shift
     const int wfrag = wm * MW * 64 + lane;
     auto load_fw = [&](int set, int slot) {
         const u32x4* wst = w_l + slot * W_STEP + wfrag;
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[(hl * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(MDT_FRAG, wst[(hl * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int xfrag, int stage, int u, int s) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + u * COLS + s;
 #pragma unroll
         for (int n = 0; n < NROW; ++n)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(MDT_FRAG, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     Item cur, nxt;
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
                     for (int n = 0; n < NROW; ++n)
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
-                            acc[m][n][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][1], fx[xs][n][0], acc[m][n][bb], 0, 0, 0);   // w_lo x_hi
+                            acc[m][n][bb] = MDT_MFMA(fw[ws][m][1], fx[xs][n][0], acc[m][n][bb], 0, 0, 0);   // w_lo x_hi
                 }
                 MDT_PIN();
                 // ---- the barrier of step t publishes chunk t+1 (and, at e8 = 7, the input stage of the next K-step).  Requested by
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
                     for (int n = 0; n < NROW; ++n)
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
-                            acc[m][n][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][0], fx[xs][n][term == 1 ? 1 : 0], acc[m][n][bb], 0, 0, 0);   // w_hi x_lo, w_hi x_hi
+                            acc[m][n][bb] = MDT_MFMA(fw[ws][m][0], fx[xs][n][term == 1 ? 1 : 0], acc[m][n][bb], 0, 0, 0);   // w_hi x_lo, w_hi x_hi
                 MDT_PIN();
             }
             rb = wrap6(rb + 16 % 6);
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void MDT_REC2_KERNEL(const ConvRParams P) {
             ys[n] = yi < P.Hin ? 2 * yi + cur.a : P.H;      // rows past the input's last row: marked invalid
         }
         if (!(pdbg(P.dbg) & 1)) {
-            epilogue_item<2, NROW, MW, 32>(E, ec_l + par * EC2, acc, wm * MW, cur.cb * MT + wm * MW, ys, 2 * xi, xi < P.Win, ResRows<NROW>{});
+            epilogue_item<2, NROW, MW, 32, false, MDT_REC_OUT16 != 0>(E, ec_l + par * EC2, acc, wm * MW, cur.cb * MT + wm * MW, ys, 2 * xi, xi < P.Win, ResRows<NROW>{});
         }
         if (!has_next) break;
         work = work_n;

@@ -4,6 +4,9 @@
 //   MDT_REC_KERNEL = k_conv3x3_rec_st, MDT_REC_ST = 1 : + the GroupNorm statistics of the output (epilogue_item<.., ST = true>): slow mode's pooled sites
 //   MDT_REC_TERMS = 3 (the kernels above) or 1 (k_conv3x3_rec1t / k_conv3x3_rec1t_st, MDTILE_PRECISION_BF16): the one-term form issues only
 //   w_hi x x_hi and reads only the hi fragments; its DMA pieces, ring slots and counted waits are the three-term kernel's, lo planes included
+//   MDT_OPERAND_F16 = 1 (with MDT_REC_TERMS = 1; k_conv3x3_rec_f16 / _f16s / _f16_st, MDTILE_PRECISION_F16): the same one-term text on fp16 fragments and
+//   v_mfma_f32_32x32x16_f16 (mfma_operand.h); MDT_REC_OUT16 = 1 selects the fp16 record-out form of the epilogue (conv_rec_common.h: R16)
+#include "mfma_operand.h"
 template <int MW, int WM, int NROW>
 __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
     constexpr bool ST = MDT_REC_ST != 0;
@@ -93,8 +96,8 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                   ec_l + par * EC_REC + wave * 64);
     };
 
-    bf16x8 fw[2][MW][2];   // [set][m][hl]
-    bf16x8 fx[2][HN][2];   // [set][row of the half-step][hl]
+    MDT_FRAG fw[2][MW][2];   // [set][m][hl]
+    MDT_FRAG fx[2][HN][2];   // [set][row of the half-step][hl]
     const int wfrag = wm * MW * 64 + lane;                       // + ((hl*3 + dx)*MT + m)*64
     const int xfrag = (kg * ROWS + wr * NROW) * COLS + l31;      // + hl*HALF_PAD + (n + dy)*COLS + dx
     auto load_fw = [&](int set, int ring, int dx) {
@@ -102,14 +105,14 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[((hl * 3 + dx) * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(MDT_FRAG, wst[((hl * 3 + dx) * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int stage, int dy, int dx, int h) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + (dy + h * HN) * COLS + dx;
 #pragma unroll
         for (int n = 0; n < HN; ++n)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(MDT_FRAG, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     WorkItem cur, nxt;
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                     for (int n = 0; n < HN; ++n)
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
-                            acc[m][h * HN + n][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][term == 0 ? 1 : 0], fx[xs][n][term == 1 ? 1 : 0],
+                            acc[m][h * HN + n][0] = MDT_MFMA(fw[ws][m][term == 0 ? 1 : 0], fx[xs][n][term == 1 ? 1 : 0],
                                                                                             acc[m][h * HN + n][0], 0, 0, 0);   // w_lo x_hi, w_hi x_lo, w_hi x_hi
                 MDT_PIN();
                 if (dx == 0 && h == 1) {
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
             E.st = P.gn_part + (((((size_t)cur.b * P.ptiles + ptile) * WR + wr) * P.NCB + cur.cb) * (MT * 8) + wm * MW * 8) * 2;
         }
         if (!(pdbg(P.dbg) & 1)) {
-            epilogue_item<1, NROW, MW, 64, ST>(E, ec_l + par * EC_REC, acc, wm * MW, cur.cb * MT + wm * MW, ys, x, x < P.W, res_rows(nxt, work_n < total));
+            epilogue_item<1, NROW, MW, 64, ST, MDT_REC_OUT16 != 0>(E, ec_l + par * EC_REC, acc, wm * MW, cur.cb * MT + wm * MW, ys, x, x < P.W, res_rows(nxt, work_n < total));
         }
         stamp(2);
         ++item_no;

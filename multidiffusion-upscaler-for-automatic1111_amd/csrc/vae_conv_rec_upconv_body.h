@@ -1,6 +1,8 @@
 // Body of k_upconv_rec / k_upconv_rec_st (csrc/vae_conv_rec.hip includes this file twice; see vae_conv_rec_direct_body.h for why the text is
 // shared by inclusion and not through a body template): MDT_REC_ST = 1 adds the GroupNorm statistics of the output, MDT_REC_TERMS = 1 is the
 // one-term form (k_upconv_rec1t / _st: w_hi x x_hi only, hi fragments only, the DMA / wait protocol of the three-term kernel unchanged).
+// MDT_REC_OUT16 = 1 (k_upconv_rec_o16 / k_upconv_rec2_o16, MDTILE_PRECISION_F16): the three-term kernel with the fp16 record-out epilogue (R16)
+#include "mfma_operand.h"
 __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
     constexpr bool ST = MDT_REC_ST != 0;
     constexpr int NT = MDT_REC_TERMS, NHL = NT == 3 ? 2 : 1;   // products per MFMA site (3: w_lo x_hi, w_hi x_lo, w_hi x_hi; 1: w_hi x_hi), planes read
@@ -81,8 +83,8 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                   ec_l + par * EC_REC + wave * 64);
     };
 
-    bf16x8 fw[2][MW][2];     // [set][m][hl]   weight tiles of one combo-step
-    bf16x8 fx[2][NROW][2];   // [set][n][hl]   input rows of one column shift
+    MDT_FRAG fw[2][MW][2];     // [set][m][hl]   weight tiles of one combo-step
+    MDT_FRAG fx[2][NROW][2];   // [set][n][hl]   input rows of one column shift
     const int wfrag = wm * MW * 64 + lane;
     auto load_fw = [&](int set, int ring, int c) {
         const int bb = c >> 1, v = ((c + 1) >> 1) - bb;           // c: 0 -> (0, 0), 1 -> (0, 1), 2 -> (1, 0), 3 -> (1, 1)
@@ -90,14 +92,14 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
 #pragma unroll
         for (int m = 0; m < MW; ++m)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(bf16x8, wst[(((hl * 2 + bb) * 2 + v) * MT + m) * 64]);
+            for (int hl = 0; hl < NHL; ++hl) fw[set][m][hl] = __builtin_bit_cast(MDT_FRAG, wst[(((hl * 2 + bb) * 2 + v) * MT + m) * 64]);
     };
     auto load_fx = [&](int set, int xfrag, int stage, int u, int s) {
         const u32x4* ist = in_l + stage * IS::PAD + xfrag + u * COLS + s;
 #pragma unroll
         for (int n = 0; n < NROW; ++n)
 #pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(bf16x8, ist[hl * IS::HALF_PAD + n * COLS]);
+            for (int hl = 0; hl < NHL; ++hl) fx[set][n][hl] = __builtin_bit_cast(MDT_FRAG, ist[hl * IS::HALF_PAD + n * COLS]);
     };
 
     Item cur, nxt;
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
                         for (int n = 0; n < NROW; ++n)
 #pragma unroll
                             for (int m = 0; m < MW; ++m)
-                                acc[m][n][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ws][m][term == 0 ? 1 : 0], fx[xs][n][term == 1 ? 1 : 0],
+                                acc[m][n][bb] = MDT_MFMA(fw[ws][m][term == 0 ? 1 : 0], fx[xs][n][term == 1 ? 1 : 0],
                                                                                         acc[m][n][bb], 0, 0, 0);
                     MDT_PIN();
                     if (c == 1) {
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void MDT_REC_KERNEL(const ConvRParams P) {
             E.st = P.gn_part + ((((((size_t)cur.b * P.ptiles + ptile) * 2 + cur.a) * (8 / WM) + wr) * P.NCB + cur.cb) * (MT * 8) + wm * MW * 8) * 2;
         }
         if (!(pdbg(P.dbg) & 1)) {
-            epilogue_item<2, NROW, MW, 64, ST>(E, ec_l + par * EC_REC, acc, wm * MW, cur.cb * MT + wm * MW, ys, 2 * xi, xi < P.Win, ResRows<NROW>{});
+            epilogue_item<2, NROW, MW, 64, ST, MDT_REC_OUT16 != 0>(E, ec_l + par * EC_REC, acc, wm * MW, cur.cb * MT + wm * MW, ys, 2 * xi, xi < P.Win, ResRows<NROW>{});
         }
         if (work_n >= total) break;
         work = work_n;

@@ -27,6 +27,9 @@ BLEND_KERNEL_PLAIN, BLEND_KERNEL_LDS = 0, 1
 CONV_UPSAMPLE2X = 1
 CONV_REC_ONE_BLOCK, CONV_REC_TWO_BLOCKS = 4, 8      # call_rec(family=...): name the record-conv kernel family (tests / probes); 0 = per launch
 CONV_EXACT_F32 = 2
+CONV_REC_X_F16, CONV_REC_Y_F16 = 32, 64      # PRECISION_F16: the input record / the record output of a record conv is the fp16 form (RecImage.fmt)
+CONV_W_F16, CONV_ATTN_PROJ = 128, 256        # PRECISION_F16: the hand-over conv gets the fp16 weight plane; a 1x1 conv is q / k / v / proj_out of the attention
+REC_BF16X2, REC_F16 = 0, 1                   # RecImage.fmt: bf16 (hi, lo) split | fp16 in the hi half (activated records written in PRECISION_F16)
 ATTN_EXACT_F32 = 1
 ATTN_V_CHANNEL_MAJOR = 2
 MAX_BATCHES, MAX_REGIONS = 320, 16
@@ -118,6 +121,8 @@ _SIGNATURES = {
     "mdtile_add": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mdtile_conv_packed_size": (c_size_t, [c_int, c_int, c_int]),
     "mdtile_conv_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdtile_conv_pack_f16_size": (c_size_t, [c_int, c_int, c_int]),
+    "mdtile_conv_pack_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdtile_conv2d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_void_p]),
     "mdtile_conv2d_down2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
@@ -139,6 +144,8 @@ _SIGNATURES = {
     "mdtile_rec_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mdtile_rec_from_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdtile_rec_to_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mdtile_rec_from_f32_fmt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mdtile_rec_to_f32_fmt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mdtile_conv2d_rec_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "mdtile_conv2d_rec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_int, c_int, c_void_p]),
@@ -177,6 +184,7 @@ def lib() -> ctypes.CDLL:
 
 
 PRECISION_BF16X3, PRECISION_F32, PRECISION_BF16 = 0, 1, 2
+PRECISION_F16 = 5
 
 
 def set_precision(mode: int) -> None:
@@ -184,7 +192,9 @@ def set_precision(mode: int) -> None:
     PRECISION_BF16X3 (default): split-bf16 operands, three bf16 MFMAs per product, fp32 accumulation (~1e-5 relative to fp32);
     PRECISION_F32: exact-fp32 MFMA kernels everywhere (~4x slower);
     PRECISION_BF16: one bf16 MFMA per product, bf16_rn(a) x bf16_rn(b) with fp32 accumulation -- the arithmetic of a half-precision
-    (bfloat16) VAE; tensors in and out, the residual stream, GroupNorm statistics and softmax stay fp32.
+    (bfloat16) VAE; tensors in and out, the residual stream, GroupNorm statistics and softmax stay fp32;
+    PRECISION_F16: one fp16 MFMA per product for the 3x3 convs behind a norm + SiLU (the arithmetic class of an fp16 VAE), three bf16 terms for
+    every conv that reads the raw residual stream (it may pass fp16's range), the attention as in PRECISION_BF16 (include/mdtile.h).
     Raises MdtileError on any other value."""
     _check(lib().mdtile_set_precision(int(mode)), "mdtile_set_precision")
 
@@ -750,14 +760,15 @@ class RecImage:
     """Split-bf16 record image of an activation [B, C, H, W] (include/mdtile.h "Record-image conv path"): the form the record
     conv kernels read by DMA.  `data` is an opaque int32 buffer of mdtile_rec_size bytes."""
 
-    __slots__ = ("data", "shape")
+    __slots__ = ("data", "shape", "fmt")
 
-    def __init__(self, shape, device):
+    def __init__(self, shape, device, fmt: int = REC_BF16X2):
         B, C, H, W = (int(v) for v in shape)
         n = lib().mdtile_rec_size(B, C, H, W)
         if n == 0:
             raise MdtileError(f"no record image for shape {tuple(shape)} (C % 32 == 0 required)")
         self.shape = (B, C, H, W)
+        self.fmt = int(fmt)      # REC_BF16X2 | REC_F16: the form the producer wrote; the wrappers hand it to every call that reads the image
         self.data = torch.empty(n // 4, dtype=torch.int32, device=device)
 
     REC_COL0 = 7          # csrc/conv_rec_common.h: column of the left border record; pixel x sits at column x + 8
@@ -777,20 +788,26 @@ class RecImage:
     def to_f32(self) -> torch.Tensor:
         B, C, H, W = self.shape
         out = torch.empty(self.shape, dtype=torch.float32, device=self.data.device)
-        _check(lib().mdtile_rec_to_f32(_p(self.data), _p(out), B, C, H, W, _stream()), "mdtile_rec_to_f32")
+        _check(lib().mdtile_rec_to_f32_fmt(_p(self.data), _p(out), B, C, H, W, self.fmt, _stream()), "mdtile_rec_to_f32_fmt")
         return out
 
 
 def rec_from_f32(x: torch.Tensor, coef: Optional[torch.Tensor] = None) -> RecImage:
-    """split(silu(a x + s)) with coef = gn_coeffs(...) [B, 2, C], or split(x) when coef is None."""
+    """split(silu(a x + s)) with coef = gn_coeffs(...) [B, 2, C], or split(x) when coef is None.  In PRECISION_F16 an activated record is
+    written in its fp16 form (RecImage.fmt == REC_F16)."""
     _dev_tensor(x, "x", torch.float32)
     B, C, H, W = x.shape
-    rec = RecImage(x.shape, x.device)
+    rec = RecImage(x.shape, x.device, _act_rec_fmt(coef))
     if coef is not None:
         _dev_tensor(coef, "coef", torch.float32)
         assert tuple(coef.shape) == (B, 2, C)
-    _check(lib().mdtile_rec_from_f32(_p(x), _p(coef), _p(rec.data), B, C, H, W, _stream()), "mdtile_rec_from_f32")
+    _check(lib().mdtile_rec_from_f32_fmt(_p(x), _p(coef), _p(rec.data), B, C, H, W, rec.fmt, _stream()), "mdtile_rec_from_f32_fmt")
     return rec
+
+
+def _act_rec_fmt(coef) -> int:
+    """The form a producer writes now: an activated record (coef given) is fp16 in PRECISION_F16, everything else a bf16 split."""
+    return REC_F16 if coef is not None and get_precision() == PRECISION_F16 else REC_BF16X2
 
 
 def silu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -820,8 +837,12 @@ def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) ->
 class PackedConv:
     """Weights of one nn.Conv2d (1x1 or 3x3, stride 1, 'same' padding) re-laid out once for the MFMA conv kernel."""
 
-    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor]):
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], attn_proj: bool = False):
+        """attn_proj: the conv is q / k / v / proj_out of the attention (a 1x1 conv): in PRECISION_F16 it follows the attention's one-term bf16
+        arithmetic (CONV_ATTN_PROJ); every other 1x1 conv reads the raw stream and keeps three terms.  No effect in the other modes."""
         _dev_tensor(weight, "weight", torch.float32)
+        self.attn_proj = bool(attn_proj)
+        self._packed_f16 = None      # fp16 weight plane of PRECISION_F16, built by packed_f16() the first time a call needs it
         self.cout, self.cin, kh, kw = weight.shape
         assert kh == kw and kh in (1, 3)
         self.ksize = kh
@@ -834,6 +855,24 @@ class PackedConv:
         if self.bias is not None and self.cout % 32:
             self.bias_rec = torch.zeros((self.cout + 31) // 32 * 32, dtype=torch.float32, device=weight.device)
             self.bias_rec[:self.cout] = self.bias
+
+    def packed_f16(self) -> torch.Tensor:
+        """fp16 weight plane of PRECISION_F16 (mdtile_conv_pack_f16), built from the packed buffer the first time a call needs it."""
+        w = self._packed_f16
+        if w is None:
+            n = lib().mdtile_conv_pack_f16_size(self.cout, self.cin, self.ksize)
+            if n == 0:
+                raise MdtileError(f"no fp16 kernel takes a {self.ksize}x{self.ksize} conv {self.cin} -> {self.cout}")
+            w = torch.empty(n, dtype=torch.float32, device=self.packed.device)
+            _check(lib().mdtile_conv_pack_f16(_p(self.packed), _p(w), self.cout, self.cin, self.ksize, _stream()), "mdtile_conv_pack_f16")
+            self._packed_f16 = w
+        return w
+
+    def _rec_operands(self, x: "RecImage", yrec: Optional["RecImage"]):
+        """(weights, flag bits) of a record conv call reading x and writing yrec: the forms travel with the images."""
+        x16 = getattr(x, "fmt", REC_BF16X2) == REC_F16
+        flags = (CONV_REC_X_F16 if x16 else 0) | (CONV_REC_Y_F16 if yrec is not None and yrec.fmt == REC_F16 else 0)
+        return (self.packed_f16() if x16 else self.packed), flags
 
     def down2(self, x: torch.Tensor) -> torch.Tensor:
         """ldm Downsample: conv3x3 stride 2 over pad(x, right 1, bottom 1) (encoder 'downsample' task)."""
@@ -872,26 +911,28 @@ class PackedConv:
             assert len(y0) == len(x0) == B, f"{B} images but {len(y0)} / {len(x0)} window origins"
             h, w = int(h), int(w)
             y = torch.empty((B, self.cout, 2 * h, 2 * w), dtype=torch.float32, device=x.data.device) if want_f32 else None
-            yr = RecImage((B, self.cout, 2 * h, 2 * w), x.data.device) if want_rec else None
+            yr = RecImage((B, self.cout, 2 * h, 2 * w), x.data.device, _act_rec_fmt(rec_coef)) if want_rec else None
             if rec_coef is not None:
                 _dev_tensor(rec_coef, "rec_coef", torch.float32)
                 assert want_rec and tuple(rec_coef.shape) == (B, 2, self.cout)
-            _check(lib().mdtile_upconv2d_rec_window(_p(x.data), _p(self.packed), _p(self.bias_rec), _p(y), None if yr is None else _p(yr.data),
-                                                    _p(rec_coef), B, self.cin, self.cout, H, W, (c_int * B)(*y0), (c_int * B)(*x0), h, w, int(family), _stream()),
+            wts, fmt_flags = self._rec_operands(x, yr)
+            _check(lib().mdtile_upconv2d_rec_window(_p(x.data), _p(wts), _p(self.bias_rec), _p(y), None if yr is None else _p(yr.data),
+                                                    _p(rec_coef), B, self.cin, self.cout, H, W, (c_int * B)(*y0), (c_int * B)(*x0), h, w, int(family) | fmt_flags, _stream()),
                    "mdtile_upconv2d_rec_window")
             return y, yr
         if upsample2x:
             H, W = 2 * H, 2 * W
         y = torch.empty((B, self.cout, H, W), dtype=torch.float32, device=x.data.device) if want_f32 else None
-        yr = RecImage((B, self.cout, H, W), x.data.device) if want_rec else None
+        yr = RecImage((B, self.cout, H, W), x.data.device, _act_rec_fmt(rec_coef)) if want_rec else None
         if residual is not None:
             _dev_tensor(residual, "residual", torch.float32)
             assert tuple(residual.shape) == (B, self.cout, H, W)
         if rec_coef is not None:
             _dev_tensor(rec_coef, "rec_coef", torch.float32)
             assert want_rec and tuple(rec_coef.shape) == (B, 2, self.cout)
-        _check(lib().mdtile_conv2d_rec(_p(x.data), _p(self.packed), _p(self.bias_rec), _p(residual), _p(y), None if yr is None else _p(yr.data),
-                                       _p(rec_coef), B, self.cin, self.cout, H, W, (CONV_UPSAMPLE2X if upsample2x else 0) | int(family), _stream()),
+        wts, fmt_flags = self._rec_operands(x, yr)
+        _check(lib().mdtile_conv2d_rec(_p(x.data), _p(wts), _p(self.bias_rec), _p(residual), _p(y), None if yr is None else _p(yr.data),
+                                       _p(rec_coef), B, self.cin, self.cout, H, W, (CONV_UPSAMPLE2X if upsample2x else 0) | int(family) | fmt_flags, _stream()),
                "mdtile_conv2d_rec")
         return y, yr
 
@@ -907,8 +948,9 @@ class PackedConv:
             _dev_tensor(residual, "residual", torch.float32)
             assert tuple(residual.shape) == (B, self.cout, H, W)
         mean, var, ws = self._stats_buffers(B, H, W, int(groups), x.data.device)
-        _check(lib().mdtile_conv2d_rec_stats(_p(x.data), _p(self.packed), _p(self.bias_rec), _p(residual), _p(y), B, self.cin, self.cout, H, W,
-                                             (CONV_UPSAMPLE2X if upsample2x else 0) | int(family), int(groups), _p(mean), _p(var), _p(ws),
+        wts, fmt_flags = self._rec_operands(x, None)
+        _check(lib().mdtile_conv2d_rec_stats(_p(x.data), _p(wts), _p(self.bias_rec), _p(residual), _p(y), B, self.cin, self.cout, H, W,
+                                             (CONV_UPSAMPLE2X if upsample2x else 0) | int(family) | fmt_flags, int(groups), _p(mean), _p(var), _p(ws),
                                              _stream()), "mdtile_conv2d_rec_stats")
         return y, (var, mean)
 
@@ -924,8 +966,9 @@ class PackedConv:
             _dev_tensor(residual, "residual", torch.float32)
             assert residual.shape == y.shape
         mean, var, ws = self._stats_buffers(B, H, W, int(groups), x.device)
-        _check(lib().mdtile_conv2d_gn_stats(_p(x), _p(pre_gn), _p(self.packed), _p(self.bias), _p(residual), _p(y), B, self.cin, self.cout,
-                                            H, W, self.ksize, 0, int(groups), _p(mean), _p(var), _p(ws), _stream()), "mdtile_conv2d_gn_stats")
+        w16 = get_precision() == PRECISION_F16      # the operand is silu(a x + s) by construction: the fp16 one-term kernel
+        _check(lib().mdtile_conv2d_gn_stats(_p(x), _p(pre_gn), _p(self.packed_f16() if w16 else self.packed), _p(self.bias), _p(residual), _p(y), B, self.cin, self.cout,
+                                            H, W, self.ksize, CONV_W_F16 if w16 else 0, int(groups), _p(mean), _p(var), _p(ws), _stream()), "mdtile_conv2d_gn_stats")
         return y, (var, mean)
 
     def leaves_stats(self, groups: int = 32, upsample2x: bool = False, rec: bool = False) -> bool:
@@ -966,12 +1009,13 @@ class PackedConv:
         if pre_gn is not None:
             _dev_tensor(pre_gn, "pre_gn", torch.float32)
             assert tuple(pre_gn.shape) == (B, 2, self.cin) and not token_major and not upsample2x
-            _check(lib().mdtile_conv2d_gn(_p(x), _p(pre_gn), _p(self.packed), _p(self.bias), _p(residual), _p(y), B, self.cin, self.cout,
-                                          H, W, self.ksize, CONV_EXACT_F32 if exact else 0, _stream()), "mdtile_conv2d_gn")
+            w16 = not exact and get_precision() == PRECISION_F16      # the operand is silu(a x + s) by construction: the fp16 one-term kernel
+            _check(lib().mdtile_conv2d_gn(_p(x), _p(pre_gn), _p(self.packed_f16() if w16 else self.packed), _p(self.bias), _p(residual), _p(y), B, self.cin,
+                                          self.cout, H, W, self.ksize, (CONV_EXACT_F32 if exact else 0) | (CONV_W_F16 if w16 else 0), _stream()), "mdtile_conv2d_gn")
             return y
         _check(lib().mdtile_conv2d(_p(x), _p(self.packed), _p(self.bias), _p(residual), _p(y), B, self.cin, self.cout, H, W,
-                                   self.ksize, (CONV_UPSAMPLE2X if upsample2x else 0) | (CONV_EXACT_F32 if exact else 0),
-                                   int(token_major), _stream()), "mdtile_conv2d")
+                                   self.ksize, (CONV_UPSAMPLE2X if upsample2x else 0) | (CONV_EXACT_F32 if exact else 0) |
+                                   (CONV_ATTN_PROJ if self.attn_proj else 0), int(token_major), _stream()), "mdtile_conv2d")
         return y
 
 

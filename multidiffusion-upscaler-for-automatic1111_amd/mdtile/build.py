@@ -89,10 +89,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
         raise RuntimeError(f"link failed:\n{r.stdout}")
     # build-time guard of the hand-counted LDS-DMA protocol (M0 save / set / restore around every global_load_lds, the counted vmcnt
     # waits in front of the barriers): checked on the emitted device assembly, so a compiler upgrade cannot break it silently; --one-term
-    # adds the one-term kernels of MDTILE_PRECISION_BF16
+    # adds the one-term kernels of MDTILE_PRECISION_BF16, --f16 the fp16 kernels of MDTILE_PRECISION_F16 (each against its bf16 twin)
     guard = os.path.join(os.path.dirname(EXT_ROOT), "tools", "asm_guard.py")
     if os.path.exists(guard) and os.environ.get("MDTILE_SKIP_ASM_GUARD", "") != "1":
-        g = subprocess.run([sys.executable, guard, "--one-term"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        g = subprocess.run([sys.executable, guard, "--one-term", "--f16"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if g.returncode != 0:
             raise RuntimeError("tools/asm_guard.py rejected the device code of the record conv / attention kernels (it checks hipcc's assembly for the "
                                "hand-counted LDS-DMA protocol; after a compiler upgrade a mismatch of its patterns looks the same as a real violation -- "

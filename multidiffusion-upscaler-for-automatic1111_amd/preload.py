@@ -6,3 +6,8 @@ def preload(parser):
         "--mdtile-devices", type=str, default=None,
         help="Tiled VAE on several GPUs of this process: comma-separated CUDA indices (a device may be listed more than once), or 'all'. "
              "The VAE's own device is always the first; the others need peer access to it. Default: the VAE's device only.")
+    parser.add_argument(
+        "--mdtile-precision", type=str, default=None, choices=["bf16x3", "f32", "bf16", "f16", "auto"],
+        help="Matrix-core arithmetic of Tiled VAE while it is enabled: bf16x3 (split-bf16, fp32 class), f32 (exact), bf16 / f16 (one MFMA per product, "
+             "the arithmetic class of a bfloat16 / float16 VAE), auto (from the VAE's dtype: float16 -> f16, bfloat16 -> bf16, else bf16x3). "
+             "Default: not set, the engine's mode is left alone (bf16x3 unless the process set another).")

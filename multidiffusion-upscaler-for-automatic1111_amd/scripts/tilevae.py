@@ -125,6 +125,33 @@ def parse_devices(value: Optional[str], vae_device: int, device_count: int, can_
     return slots if len(slots) > 1 else None
 
 
+PRECISION_NAMES = {"bf16x3": mdtile.PRECISION_BF16X3, "f32": mdtile.PRECISION_F32, "bf16": mdtile.PRECISION_BF16, "f16": mdtile.PRECISION_F16}
+
+
+def resolve_precision(value, param_dtype) -> Optional[int]:
+    """The value of --mdtile-precision -> a mdtile.PRECISION_* mode, or None (option absent: the mode is never touched).  "auto" follows the dtype
+    of the decoder's parameters: float16 -> F16, bfloat16 -> BF16, anything else (float32, no parameters) -> BF16X3.  Pure."""
+    if value is None or not str(value).strip():
+        return None
+    value = str(value).strip().lower()
+    if value == "auto":
+        return {torch.float16: mdtile.PRECISION_F16, torch.bfloat16: mdtile.PRECISION_BF16}.get(param_dtype, mdtile.PRECISION_BF16X3)
+    if value not in PRECISION_NAMES:
+        print(f"[Tiled VAE]: --mdtile-precision {value!r} is none of {', '.join(PRECISION_NAMES)}, auto; the option is ignored")
+        return None
+    return PRECISION_NAMES[value]
+
+
+def _cmd_line_precision(net) -> Optional[int]:
+    """--mdtile-precision (preload.py) for the VAE whose decoder is `net`; None when the option is not set."""
+    import modules.shared as shared
+    value = getattr(shared.cmd_opts, "mdtile_precision", None)
+    if not value:
+        return None
+    p = next(net.parameters(), None)
+    return resolve_precision(value, None if p is None else p.dtype)
+
+
 def _cmd_line_devices(net) -> Optional[List[int]]:
     """--mdtile-devices (preload.py) for the hooks of `net` (the VAE's decoder); None when the option is not set."""
     import modules.shared as shared
@@ -832,6 +859,12 @@ class Script(scripts.Script):
 
     def __init__(self):
         self.hooked = False
+        self._prev_precision = None      # the engine's mode before --mdtile-precision replaced it (None: not replaced); postprocess puts it back
+
+    def _restore_precision(self):
+        if self._prev_precision is not None:
+            mdtile.set_precision(self._prev_precision)
+            self._prev_precision = None
 
     def title(self):
         return "Tiled VAE"
@@ -869,7 +902,18 @@ class Script(scripts.Script):
                         net.forward.net = None
                         net.forward = net.original_forward
             self.hooked = False
+            self._restore_precision()
             return
+        mode = _cmd_line_precision(decoder)
+        if mode is None:
+            self._restore_precision()      # (the option went away between two jobs; without it the mode is never touched)
+        else:
+            prev = mdtile.get_precision()
+            if self._prev_precision is None:
+                self._prev_precision = prev      # (a job that never reached postprocess: keep what was there before IT)
+            mdtile.set_precision(mode)
+            names = {v: k for k, v in PRECISION_NAMES.items()}
+            print(f"[Tiled VAE]: --mdtile-precision: matrix-core arithmetic {names.get(mode, mode)} for this job (was {names.get(prev, prev)})")
         if not hasattr(decoder, "original_forward"):
             decoder.original_forward = decoder.forward
         self.hooked = True
@@ -885,6 +929,7 @@ class Script(scripts.Script):
         encoder.forward.devices = None if slots is None else list(slots)
 
     def postprocess(self, p, processed, enabled: bool, *args):
+        self._restore_precision()
         if not enabled:
             return
         vae = p.sd_model.first_stage_model

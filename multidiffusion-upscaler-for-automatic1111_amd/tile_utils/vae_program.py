@@ -31,7 +31,9 @@ class AttnPack:
     """q/k/v/proj_out of one AttnBlock, packed for the engine; v is produced token-major for the PV contraction."""
 
     def __init__(self, attn, pack=None, engine=None):
-        pack = pack or _pack
+        # the engine's own packer marks these 1x1 convs as the attention's (PRECISION_F16: they follow its arithmetic, nin_shortcut does not);
+        # an injected packer (the CPU tests' torch doubles) is called as it always was
+        pack = pack or (lambda conv: _pack(conv, attn_proj=True))
         self.engine = engine or mdtile
         self.q, self.k, self.v, self.proj = (pack(attn.q), pack(attn.k), pack(attn.v), pack(attn.proj_out))
         self.channels = attn.q.weight.shape[0]
@@ -49,7 +51,7 @@ class AttnPack:
         return self.proj(o.view(B, C, H, W), residual=residual)        # proj_out + the queue's add_res
 
 
-def _pack(conv) -> mdtile.PackedConv:
+def _pack(conv, attn_proj: bool = False) -> mdtile.PackedConv:
     if conv.stride == (2, 2):
         # ldm Downsample.conv: 3x3, stride 2, no padding (the module pads right/bottom by one itself) -> PackedConv.down2
         assert conv.kernel_size == (3, 3) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1, f"unsupported conv {conv}"
@@ -58,7 +60,7 @@ def _pack(conv) -> mdtile.PackedConv:
     k = conv.kernel_size[0]
     assert conv.kernel_size == (k, k) and conv.padding == (k // 2, k // 2), f"unsupported conv {conv}"
     return mdtile.PackedConv(conv.weight.detach().float().contiguous(),
-                             None if conv.bias is None else conv.bias.detach().float())
+                             None if conv.bias is None else conv.bias.detach().float(), attn_proj=attn_proj)
 
 
 def _norm_params(gn):
@@ -85,13 +87,14 @@ def build_task_queue(net, is_decoder: bool = True, pack=None, engine=None) -> Li
     with num_res_blocks+1 resblocks (+ upsample except on level 0), norm_out, silu, conv_out.  30 norms for SD/SDXL.
     `pack` turns an nn.Conv2d into the callable a step carries and `engine` is the module the attention step calls
     (defaults: mdtile.PackedConv / mdtile; the CPU tests of the host logic inject torch doubles, tests/torch_engine.py)."""
+    attn_pack = pack          # None: AttnPack uses the engine's packer with attn_proj set
     pack = pack or _pack
     steps = [Step("conv", conv=pack(net.conv_in))]
 
     def _mid():
         _resblock(steps, net.mid.block_1, pack)
         steps.extend([Step("store_res"), Step("norm", norm=_norm_params(net.mid.attn_1.norm), channels=net.mid.attn_1.norm.num_channels),
-                      Step("attn", attn=AttnPack(net.mid.attn_1, pack, engine))])
+                      Step("attn", attn=AttnPack(net.mid.attn_1, attn_pack, engine))])
         _resblock(steps, net.mid.block_2, pack)
 
     if is_decoder:

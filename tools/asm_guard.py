@@ -15,8 +15,16 @@ device assembly and checks the emitted instruction stream instead:
     * MFMA counts per unrolled trip match the source (conv: 36 half-steps x 12; upconv: 24 combo-steps x 12; attention: 24 / slab)
     * with --one-term: the one-term forms of MDTILE_PRECISION_BF16 (k_conv3x3_rec1t, k_upconv_rec1t, their _st forms, k_conv3x3_rec2_1t, k_upconv_rec2_1t,
       k_conv1x1_stream1t, k_attn_bf16x1) keep their three-term twins' DMA count and barrier waits exactly; their MFMA multiples are a third
+    * with --f16: the fp16 kernels of MDTILE_PRECISION_F16, each against its bf16 twin (the one-term kernel for a consumer, the three-term kernel for the
+      upsample convs, which only gain the fp16 record output): present; a consumer's MFMAs are all v_mfma_f32_32x32x16_f16 and as many as the twin's
+      (an upsample conv keeps the twin's bf16 MFMAs); the same DMA quintuples and the same counted waits in front of the barriers as the twin; a
+      PRODUCER of fp16 records (k_conv3x3_rec_f16, k_conv3x3_rec2_f16, k_upconv_rec_o16, k_upconv_rec2_o16, k_rec_from_f32_f16) has exactly half the
+      twin's 16-byte stores -- one store per record where the split form has two (hi, lo), border records included; the fp32 streams of these kernels
+      are 4- / 8-byte stores.  The wait values in front of the barriers are compared with the TWIN's own list, not only with the table.  The three
+      hand-over kernels (k_conv3x3_f16) issue no inline-asm LDS-DMA of their own protocol (their weights come through the compiler's
+      global_load_lds builtin or through registers, behind __syncthreads): for them the MFMA, DMA, barrier and store counts are compared
     * k_vae_assemble (csrc/vae_assemble.hip): no packed-fp32 instruction with op_sel, 16-byte loads and stores present
-usage: python tools/asm_guard.py [--one-term] [--probes]   (exit code 0 = ok; prints one line per kernel)      -- also run by tests/test_host_abi.py
+usage: python tools/asm_guard.py [--one-term] [--f16] [--probes]   (exit code 0 = ok; prints one line per kernel)      -- also run by tests/test_host_abi.py
        (--one-term adds the one-term kernels; mdtile/build.py runs the guard with it, tests/test_precision_bf16_host.py checks them)
 """
 from __future__ import annotations
@@ -74,7 +82,7 @@ def kernels(lines: list) -> dict:
 SREG = r"(?:s\d+|vcc_lo|vcc_hi|ttmp\d+)"
 
 
-def check_kernel(name: str, ins: list, expect: dict) -> list:
+def check_kernel(name: str, ins: list, expect: dict, mfma: str = "bf16") -> list:
     errs = []
     dma = [k for k, l in enumerate(ins) if l.startswith("global_load_lds_dwordx4")]
     for k in dma:
@@ -106,7 +114,7 @@ def check_kernel(name: str, ins: list, expect: dict) -> list:
             m = re.search(r"vmcnt\((\d+)\)", w)
             bar_waits.append(int(m.group(1)) if m else None)      # None: an lgkmcnt-only wait (LDS hand-over, no DMA consumed behind it)
     counted = {w for w in bar_waits if w is not None}
-    n_mfma = sum(1 for l in ins if l.startswith("v_mfma_f32_32x32x16_bf16"))
+    n_mfma = sum(1 for l in ins if l.startswith("v_mfma_f32_32x32x16_" + mfma))
     for key, val in expect.items():
         if key == "dma_min" and len(dma) < val:
             errs.append(f"{len(dma)} DMA instructions < {val}")
@@ -117,6 +125,51 @@ def check_kernel(name: str, ins: list, expect: dict) -> list:
     print(f"{name[:70]:70s} {len(ins):6d} instr  {len(dma):3d} DMA  {len(bars):3d} barriers (vmcnt in front: {sorted(counted)}, lgkm-only: {bar_waits.count(None)})  "
           f"{n_mfma:4d} MFMA  {'ok' if not errs else 'FAIL'}")
     return [f"{name}: {e}" for e in errs]
+
+
+def barrier_waits(ins: list) -> list:
+    """vmcnt value (None: lgkmcnt only, -1: no wait) of the nearest s_waitcnt in front of every s_barrier, in program order"""
+    out = []
+    for k, l in enumerate(ins):
+        if l.startswith("s_barrier"):
+            j = k - 1
+            while j >= 0 and not ins[j].startswith("s_waitcnt") and not ins[j].startswith("s_barrier") and k - j < 64:
+                j -= 1
+            if j < 0 or not ins[j].startswith("s_waitcnt"):
+                out.append(-1)
+            else:
+                m = re.search(r"vmcnt\((\d+)\)", ins[j])
+                out.append(int(m.group(1)) if m else None)
+    return out
+
+
+def count(ins: list, prefix: str) -> int:
+    return sum(1 for l in ins if l.startswith(prefix))
+
+
+def check_f16(table: dict, sub: str, twin_sub: str, expect: dict, consumer: bool, producer: bool) -> list:
+    """One fp16 kernel of MDTILE_PRECISION_F16 against its bf16 twin (see the module text, --f16)."""
+    hit, twin = [n for n in table if sub in n], [n for n in table if twin_sub in n]
+    if not hit or not twin:
+        return [f"kernel {sub if not hit else twin_sub} not found in the device assembly"]
+    ins, tw = table[hit[0]], table[twin[0]]
+    errs = check_kernel(hit[0], ins, expect, "f16" if consumer else "bf16") if expect else []
+    n16, nb, tb = count(ins, "v_mfma_f32_32x32x16_f16"), count(ins, "v_mfma_f32_32x32x16_bf16"), count(tw, "v_mfma_f32_32x32x16_bf16")
+    if consumer and (nb != 0 or n16 != tb):
+        errs.append(f"{hit[0]}: {n16} fp16 + {nb} bf16 MFMAs, the one-term twin has {tb} (expected {tb} + 0)")
+    if not consumer and (n16 != 0 or nb != tb):
+        errs.append(f"{hit[0]}: {nb} bf16 + {n16} fp16 MFMAs, the twin has {tb} (expected {tb} + 0)")
+    if barrier_waits(ins) != barrier_waits(tw):
+        errs.append(f"{hit[0]}: waits in front of the barriers {barrier_waits(ins)}, the twin's {barrier_waits(tw)}")
+    for what in ("global_load_lds_dwordx4", "s_barrier"):
+        if count(ins, what) != count(tw, what):
+            errs.append(f"{hit[0]}: {count(ins, what)} {what}, the twin has {count(tw, what)}")
+    st, stw = count(ins, "global_store_dwordx4"), count(tw, "global_store_dwordx4")
+    if (producer and 2 * st != stw) or (not producer and st != stw):
+        errs.append(f"{hit[0]}: {st} 16-byte stores, the twin has {stw} (expected {'half: one store per record' if producer else 'as many'})")
+    if not expect:      # (kernels outside the hand-counted DMA protocol: no check_kernel line)
+        print(f"{hit[0][:70]:70s} {len(ins):6d} instr  {n16:4d} fp16 MFMA  {st} / {stw} 16-byte stores (twin)  {'ok' if not errs else 'FAIL'}")
+    return errs
 
 
 def main() -> int:
@@ -170,6 +223,25 @@ def main() -> int:
             errs.append(f"kernel {sub} not found in the device assembly")
             continue
         errs += check_kernel(hit[0], table[hit[0]], expect)
+    # --f16: the fp16 kernels of MDTILE_PRECISION_F16 (mdtile/build.py passes it): (table, kernel, bf16 twin, DMA protocol of the twin, consumer, producer)
+    if "--f16" in sys.argv:
+        b3 = kernels(device_asm(os.path.join(CSRC, "vae_conv_bf16x3.hip")))
+        r5, r2 = dict(dma_min=8, barrier_vmcnt=[0, 5], mfma_multiple=4), dict(dma_min=8, barrier_vmcnt=[0, 2, 3, 4], mfma_multiple=4)
+        for table, sub, twin, expect, consumer, producer in [
+            (rec, "k_conv3x3_rec_f16ILi2ELi2ELi4", "k_conv3x3_rec1tILi2ELi2ELi4", r5, True, True),
+            (rec, "k_conv3x3_rec_f16sILi2ELi2ELi4", "k_conv3x3_rec1tILi2ELi2ELi4", r5, True, False),
+            (rec, "k_conv3x3_rec_f16sILi1ELi1ELi2", "k_conv3x3_rec1tILi1ELi1ELi2", dict(dma_min=4, barrier_vmcnt=[0, 5], mfma_multiple=1), True, False),
+            (rec, "k_conv3x3_rec_f16_stILi2ELi2ELi4", "k_conv3x3_rec1t_stILi2ELi2ELi4", r5, True, False),
+            (rec2, "k_conv3x3_rec2_f16ILi2ELi2ELi4", "k_conv3x3_rec2_1tILi2ELi2ELi4", r2, True, True),
+            (rec2, "k_conv3x3_rec2_f16sILi2ELi2ELi4", "k_conv3x3_rec2_1tILi2ELi2ELi4", r2, True, False),
+            (rec, "k_upconv_rec_o16E", "k_upconv_recE", dict(dma_min=8, barrier_vmcnt=[0], mfma_multiple=12), False, True),
+            (rec2, "k_upconv_rec2_o16E", "k_upconv_rec2E", dict(dma_min=8, barrier_vmcnt=[0, 6, 7, 8, 9], mfma_multiple=12), False, True),
+            (rec, "k_rec_from_f32_f16E", "k_rec_from_f32E", None, True, True),
+            (b3, "k_conv3x3_f16ILi4ELb1ELi1ELb0", "k_conv3x3_bf16x1ILi4ELb1ELi1ELb0", None, True, False),
+            (b3, "k_conv3x3_f16ILi4ELb1ELi1ELb1", "k_conv3x3_bf16x1ILi4ELb1ELi1ELb1", None, True, False),
+            (b3, "k_conv3x3_f16ILi2ELb1ELi1ELb0", "k_conv3x3_bf16x1ILi2ELb1ELi1ELb0", None, True, False),
+        ]:
+            errs += check_f16(table, sub, twin, expect, consumer, producer)
     # conv_in (csrc/vae_conv.hip: k_conv3x3_fewcin): no packed-fp32 instruction of the shipping form may read the HIGH register of a pair for
     # the LOW half of its result (`op_sel:[..1..]`) -- the encoding that dropped single products when the kernel shared a CU with another
     # kernel's MFMA waves (round 6, profiles/r6j).  The shipping form keeps every weight in LDS as a ready-made pair and needs none.

@@ -5,7 +5,9 @@ events (ms per decode, min and median), and the max-abs / rel-L2 error of the mo
     python tools/precision_ab.py [--modes bf16x3,bf16] [--latent 1024] [--tile 256] [--reps 2] [--out file.json]
 For per-kernel times run one mode per process under a kernel trace, e.g.
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/precision_ab.py --modes bf16 --reps 1
-(--modes bf16 alone skips the error column: it needs the BF16X3 image of the same process)."""
+(--modes bf16 alone skips the error column: it needs the BF16X3 image of the same process).  A mode may be listed twice
+(--modes bf16x3,bf16,f16,bf16x3): the repeat is reported as "bf16x3#2", and the difference between the two BF16X3 rows is printed as the
+run-to-run spread a speed-up has to exceed."""
 from __future__ import annotations
 
 import argparse
@@ -18,7 +20,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-MODES = {"bf16x3": 0, "f32": 1, "bf16": 2}
+MODES = {"bf16x3": 0, "f32": 1, "bf16": 2, "f16": 5}
 
 
 def main() -> int:
@@ -47,7 +49,10 @@ def main() -> int:
     _print = builtins.print
     rows, images = [], {}
     for name in a.modes.split(","):
-        with torch.no_grad(), E.precision(MODES[name]):
+        mode = MODES[name]
+        n_seen = sum(1 for r in rows if r["mode"].split("#")[0] == name)
+        name = name if n_seen == 0 else f"{name}#{n_seen + 1}"
+        with torch.no_grad(), E.precision(mode):
             builtins.print = lambda *x, **k: None        # the plugin's progress chatter
             try:
                 img = hook(z)                            # warm-up (and the image compared below)
@@ -79,6 +84,15 @@ def main() -> int:
         t3 = next(r for r in rows if r["mode"] == "bf16x3")["ms_min"]
         t1 = next(r for r in rows if r["mode"] == "bf16")["ms_min"]
         print(json.dumps({"latent": a.latent, "tile": a.tile, "speedup_bf16_over_bf16x3": t3 / t1}))
+    tmin = {r["mode"]: r["ms_min"] for r in rows}
+    if "bf16x3" in tmin and "f16" in tmin:
+        line = {"latent": a.latent, "tile": a.tile, "speedup_f16_over_bf16x3": tmin["bf16x3"] / tmin["f16"]}
+        if "bf16" in tmin:
+            line["f16_over_bf16"] = tmin["f16"] / tmin["bf16"]
+        if "bf16x3#2" in tmin:
+            line["bf16x3_run_to_run_ms"] = abs(tmin["bf16x3"] - tmin["bf16x3#2"])
+            line["f16_gain_ms"] = min(tmin["bf16x3"], tmin["bf16x3#2"]) - tmin["f16"]
+        print(json.dumps(line))
     if a.out:
         with open(a.out, "w") as f:
             json.dump({"latent": a.latent, "tile": a.tile, "rows": rows}, f, indent=1)

@@ -219,6 +219,32 @@ int mdtile_region_noise(float* d_noise, int N, int C, int H, int W, const mdtile
 int mdtile_noise_inverse_blend(const float* d_noise, const float* d_inverse_noise, const float* d_renoise_mask, float* d_out, int N, int C,
                                int H, int W, const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
 
+/* Noise Inversion renoise mask (tile_utils/utils.py:216-247, get_retouch_mask; tile_methods/abstractdiffusion.py:607-621): where the init image
+ * carries detail -- the residue of a self-guided box filter (guide = input, eps 0.01), quantised to uint8 levels.  Upstream computes it with
+ * OpenCV on the CPU; here the result is DEFINED, so that it can be checked bit for bit (DESIGN.md 3.9 lists the two differences from OpenCV).
+ *   d_img     [H, W] grey bytes (channels = 1) or [H, W, 3] interleaved RGB bytes (channels = 3): L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16,
+ *             PIL's convert("L")
+ *   window    of pixel (y, x): rows y - k/2 .. y - k/2 + k - 1 and the same in x (k/2 = floor, OpenCV's default anchor); indices outside the
+ *             image are mapped by BORDER_REFLECT_101, i.e. the triangle wave of period 2 (n - 1), applied as often as needed (k/2 >= n is
+ *             legal; n == 1 -> 0)
+ *   sums      S1 = sum of L, S2 = sum of L^2 over the window as exact integers (S2 in 64 bits): no dependence on order or block shape
+ *   then, every operation ONE correctly rounded fp32 operation (no FMA), n = k^2:
+ *             img  = float(L) / 255.0f
+ *             mean = (float)((double)S1 / (255.0 * n))          msq = (float)((double)S2 / (65025.0 * n))
+ *             var  = msq - mean * mean                          a = var / (var + 0.01f)            b = mean - a * mean
+ *             gf   = ((a * img + b) - img) * 255.0f
+ *             q    = ((int32)trunc(gf)) & 255                   upstream's astype(uint8): toward zero, negatives wrap
+ *             mask = float(q) / 255.0f                          d_mask [H, W] fp32
+ *   1 <= kernel_size <= 512, channels 1 or 3, H * W < 2^31 (anything else: MDTILE_E_ARG).  Work per pixel does not grow with the window area:
+ *   horizontal window sums per row (block scan), then vertical sliding sums with a k-row start-up per chunk of rows.
+ *   d_ws: mdtile_retouch_mask_ws_size(H, W, kernel_size) bytes (8 per pixel: the row sums; 0 for arguments the call would refuse), 8-byte aligned.
+ * mdtile_renoise_resize: the tail of upstream :619-621, d_out [h, w] = clamp((1 - bilinear(d_mask [H, W] -> h x w)) * strength, 0, 1) with torch's
+ *   align_corners = False rule in fp32, per axis:  scale = float(H) / h;  src = max(scale * (dst + 0.5) - 0.5, 0);  i0 = (int)src;
+ *   i1 = min(i0 + 1, H - 1);  l1 = src - i0;  l0 = 1 - l1;    value = l0y * (l0x * p00 + l1x * p01) + l1y * (l0x * p10 + l1x * p11). */
+size_t mdtile_retouch_mask_ws_size(int H, int W, int kernel_size);
+int mdtile_retouch_mask(const uint8_t* d_img, int H, int W, int channels, int kernel_size, float* d_mask, void* d_ws, mdtile_stream_t stream);
+int mdtile_renoise_resize(const float* d_mask, int H, int W, float strength, float* d_out, int h, int w, mdtile_stream_t stream);
+
 /* ControlNet / StableSR tile slicing (tile_methods/abstractdiffusion.py:475-544, 548-588): num_rects (<= 16) rectangles of size w x h
  * at rects_xy[2 i], rects_xy[2 i + 1] of d_x_in [N,C,H,W] are cut out, concatenated (tile-major, then the N samples: torch.cat over
  * the bboxes) and repeated `repeat` times for the sampler's cond / uncond copies:

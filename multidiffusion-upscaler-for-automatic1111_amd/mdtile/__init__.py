@@ -88,6 +88,9 @@ _SIGNATURES = {
     "mdtile_blend_finalize": (c_int, [c_void_p, POINTER(_BlendArgs), c_void_p, POINTER(_Region), c_int, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
+    "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
+    "mdtile_retouch_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mdtile_renoise_resize": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_gather_rects": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, _IP, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mdtile_shard_init": (c_void_p, [c_int, _IP]),
     "mdtile_shard_unique_id": (c_int, [c_void_p]),
@@ -365,6 +368,33 @@ def noise_inverse_blend(noise: torch.Tensor, inverse_noise: torch.Tensor, renois
     out = torch.empty_like(noise)
     _check(lib().mdtile_noise_inverse_blend(_p(noise), _p(inverse_noise), _p(renoise_mask), _p(out), N, C, H, W, arr, len(regions), _stream()),
            "mdtile_noise_inverse_blend")
+    return out
+
+
+def retouch_mask(img_u8: torch.Tensor, kernel_size: int) -> torch.Tensor:
+    """Renoise mask of Noise Inversion before the resize (get_retouch_mask, tile_utils/utils.py:216-247): img_u8 [H, W] grey or [H, W, 3] RGB
+    bytes on the GPU -> [H, W] fp32 levels q / 255, defined exactly in include/mdtile.h.  1 <= kernel_size <= 512."""
+    _dev_tensor(img_u8, "img_u8", torch.uint8)
+    if not (img_u8.dim() == 2 or (img_u8.dim() == 3 and img_u8.shape[2] == 3)):
+        raise MdtileError(f"img_u8 has shape {tuple(img_u8.shape)}, expected [H, W] or [H, W, 3]")
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    L = lib()
+    ws = torch.empty(max(8, L.mdtile_retouch_mask_ws_size(H, W, int(kernel_size))), dtype=torch.uint8, device=img_u8.device)
+    out = torch.empty((H, W), dtype=torch.float32, device=img_u8.device)
+    _check(L.mdtile_retouch_mask(_p(img_u8), H, W, 1 if img_u8.dim() == 2 else 3, int(kernel_size), _p(out), _p(ws), _stream()),
+           "mdtile_retouch_mask")
+    return out
+
+
+def renoise_resize(mask: torch.Tensor, size: Tuple[int, int], strength: float) -> torch.Tensor:
+    """clamp((1 - bilinear(mask [H, W] -> size = (h, w))) * strength, 0, 1): the weight of fresh noise on the latent grid
+    (abstractdiffusion.py:619-621), torch's align_corners=False rule in fp32."""
+    _dev_tensor(mask, "mask", torch.float32)
+    assert mask.dim() == 2, f"mask has shape {tuple(mask.shape)}, expected [H, W]"
+    H, W = mask.shape
+    h, w = int(size[0]), int(size[1])
+    out = torch.empty((h, w), dtype=torch.float32, device=mask.device)
+    _check(lib().mdtile_renoise_resize(_p(mask), H, W, float(strength), _p(out), h, w, _stream()), "mdtile_renoise_resize")
     return out
 
 

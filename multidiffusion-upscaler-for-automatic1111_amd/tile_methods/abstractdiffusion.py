@@ -443,16 +443,16 @@ class AbstractDiffusion:
 
     def renoise_mask(self, p, size) -> Optional[Tensor]:
         """[H, W] weight of fresh noise: where the guided filter says the input image has detail, scaled by the renoise strength
-        (upstream :607-616)."""
+        (upstream :607-621).  An RGB init image goes up as its interleaved bytes and is made grey on the GPU; any other mode is converted
+        on the host first.  Filter and resize both run on the engine (mdtile_retouch_mask, mdtile_renoise_resize)."""
         if self.noise_inverse_renoise_strength <= 0:
             return None
         import numpy as np
-        import torch.nn.functional as F
-        gray = np.asarray(p.init_images[0].convert("L"))
-        m = torch.from_numpy(get_retouch_mask(gray, self.noise_inverse_renoise_kernel)).to(devices.device)
-        m = 1 - F.interpolate(m.unsqueeze(0).unsqueeze(0), size=size, mode="bilinear").squeeze(0).squeeze(0)
-        m *= self.noise_inverse_renoise_strength
-        return torch.clamp(m, 0, 1)
+        img = p.init_images[0]
+        pixels = np.asarray(img if img.mode == "RGB" else img.convert("L"))
+        m = get_retouch_mask(pixels, self.noise_inverse_renoise_kernel)     # module attribute, looked up per call (tests replace it)
+        m = torch.as_tensor(m).to(devices.device, torch.float32).contiguous()
+        return mdtile.renoise_resize(m, size, self.noise_inverse_renoise_strength)
 
     def _cached_inversion(self, p, prompts) -> Optional[Tensor]:
         c = self.noise_inverse_get_cache()

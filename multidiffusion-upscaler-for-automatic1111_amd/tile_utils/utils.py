@@ -5,9 +5,9 @@ computation routed through the mdtile engine (libmdtile.so, include/mdtile.h):
     split_bboxes      upstream utils.py:160-177  -> mdtile_plan_create + mdtile_weight_map_add_grid
     gaussian_weights  upstream utils.py:180-194  -> mdtile_gaussian_weights
     feather_mask      upstream utils.py:196-214  -> mdtile_feather_mask
+    get_retouch_mask  upstream utils.py:216-247  -> mdtile_retouch_mask (upstream: OpenCV box filters on the CPU; no OpenCV here)
 
 Prompt / cond helpers stay thin host-side Python (they only forward to `modules.prompt_parser`).
-`get_retouch_mask` (cv2 guided filter, once per Noise Inversion job on the CPU) is host glue as upstream.
 """
 from __future__ import annotations
 
@@ -192,22 +192,22 @@ def feather_mask(w: int, h: int, ratio: float) -> Tensor:
 NoiseInverseCache = namedtuple("NoiseInversionCache", ["model_hash", "x0", "xt", "noise_inversion_steps", "retouch", "prompts"])
 
 
-def get_retouch_mask(img_input, kernel_size: int):
-    """Where a grey image [H, W] uint8 carries detail: the residue of a self-guided box filter (guided filter with guide = input,
-    eps 0.01), as uint8-quantised fractions in [0, 1] float32 (upstream tile_utils/utils.py:216-247).  Host glue of Noise
-    Inversion: needs OpenCV, runs once per job on the CPU."""
-    import cv2
-    import numpy as np
-    k = (int(round(kernel_size)), int(round(kernel_size)))
-    img = img_input.astype(np.float32) / 255.0
-    mean = cv2.blur(img, k)
-    var = cv2.blur(img * img, k) - mean * mean
-    a = var / (var + 0.01)                 # cov(I, I) / (var(I) + eps)
-    b = mean - a * mean
-    gf = (a * img + b) - img
-    gf *= 255
-    gf = gf.astype(np.uint8)               # upstream quantises (and wraps negatives) exactly like this
-    return gf.clip(0, 255).astype(np.float32) / 255.0
+def get_retouch_mask(img_input, kernel_size: int) -> Tensor:
+    """Where an image carries detail: the residue of a self-guided box filter (guided filter with guide = input, eps 0.01), as
+    uint8-quantised fractions in [0, 1] float32 (upstream tile_utils/utils.py:216-247), computed on the GPU by mdtile_retouch_mask
+    (include/mdtile.h defines the result exactly).  img_input: numpy uint8 array [H, W] (grey) or [H, W, 3] (RGB, converted
+    with PIL's "L" formula on the GPU), or such a tensor already on the device.  Returns a TENSOR [H, W] on devices.device where upstream
+    returns an ndarray."""
+    if not isinstance(img_input, Tensor):
+        import warnings
+        import numpy as np
+        arr = np.ascontiguousarray(img_input)
+        if arr.dtype != np.uint8:
+            raise TypeError(f"get_retouch_mask: image bytes expected, got dtype {arr.dtype}")
+        with warnings.catch_warnings():     # np.asarray(PIL image) is read-only; it is only read here, and copying 200 MB to say so is waste
+            warnings.simplefilter("ignore", UserWarning)
+            img_input = torch.from_numpy(arr)
+    return mdtile.retouch_mask(img_input.to(devices.device).contiguous(), int(round(kernel_size)))
 
 
 def null_decorator(fn):

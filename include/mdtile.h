@@ -245,6 +245,35 @@ size_t mdtile_retouch_mask_ws_size(int H, int W, int kernel_size);
 int mdtile_retouch_mask(const uint8_t* d_img, int H, int W, int channels, int kernel_size, float* d_mask, void* d_ws, mdtile_stream_t stream);
 int mdtile_renoise_resize(const float* d_mask, int H, int W, float strength, float* d_out, int h, int w, mdtile_stream_t stream);
 
+/* 8-bit image resize (the img2img upscale of scripts/tilediffusion.py:141-147, which the host's Upscaler.upscale runs with Pillow on one CPU thread).
+ * The result is DEFINED as Pillow's Image.resize on "RGB" / "L" images for LANCZOS and NEAREST, restated here so that it is checked bit for bit
+ * (DESIGN.md 3.10).  Per axis, in -> out, a table of out rows: bounds[xx] = (first source index xmin, taps n), coef[xx][0 .. ksize-1] taps in 22-bit
+ * fixed point, zero from n on.  mdtile_resample_table computes it on the HOST in double, every step one IEEE operation (sin is libm's):
+ *   LANCZOS   f(x) = sinc(x) * sinc(x / 3) for -3 <= x < 3, else 0;   sinc(0) = 1, sinc(x) = sin(x * pi) / (x * pi)
+ *             scale = in / out;  fs = max(scale, 1.0);  support = 3.0 * fs;  ksize = 2 * ceil(support) + 1;  ss = 1.0 / fs
+ *             center = (xx + 0.5) * scale;   xmin = max((int)(center - support + 0.5), 0);   n = min((int)(center + support + 0.5), in) - xmin
+ *             w[x] = f((x + xmin - center + 0.5) * ss) for x < n;   ww = w[0] + w[1] + ... in index order;   if ww != 0: w[x] /= ww
+ *             coef[xx][x] = w[x] < 0 ? (int)(-0.5 + w[x] * 2^22) : (int)(0.5 + w[x] * 2^22)
+ *   NEAREST   ksize = 1, coef = 2^22, bounds[xx] = ((int)xo, 1) with xo = 0.5 * a for xx = 0 and xo += a from one output to the next, a = in / out
+ *             in double: the ACCUMULATED sum (the closed form (int)((xx + 0.5) * a) rounds differently and moves thousands of pixels)
+ *   pixel     acc = 2^21 + sum over x < n of src[xmin + x] * coef[xx][x]   (int32, exact);    out = clamp(acc >> 22, 0, 255)
+ * The horizontal pass runs first and leaves a uint8 intermediate [H, outW, C], the vertical pass runs on it; channels are independent, layout HWC
+ * interleaved.  An axis whose size does not change is skipped for LANCZOS (pass NULL, NULL, 0 for its tables); NEAREST takes both tables always.
+ *   mdtile_resample_ksize      ksize of one axis; 0 for arguments mdtile_resample_table refuses (a size below 1, an unknown filter, out * ksize >= 2^31)
+ *   mdtile_resample_table      h_coef [out][ksize], h_bounds [out][2]: HOST pointers
+ *   mdtile_resample_u8_ws_size bytes of the intermediate (H * outW * C; 0 for arguments the call would refuse)
+ *   mdtile_resample_u8         d_src [H, W, C] -> d_dst [outH, outW, C] bytes at any alignment; d_cx / d_bx / kx, d_cy / d_by / ky: DEVICE copies of the
+ *                              tables of (W -> outW) and (H -> outH); d_ws is read only when both axes have tables.  C is 1 or 3, every size >= 1,
+ *                              H * W * C and outH * outW * C below 2^31; anything else: MDTILE_E_ARG.  The kernels are integer only: no byte depends on
+ *                              block shape or summation order.  Tables from elsewhere may give other bytes, never an access outside the buffers. */
+#define MDTILE_RESAMPLE_NEAREST 0
+#define MDTILE_RESAMPLE_LANCZOS 1
+int mdtile_resample_ksize(int in_size, int out_size, int filter);
+int mdtile_resample_table(int in_size, int out_size, int filter, int32_t* h_coef, int32_t* h_bounds);
+size_t mdtile_resample_u8_ws_size(int H, int W, int C, int outH, int outW);
+int mdtile_resample_u8(const uint8_t* d_src, int H, int W, int C, uint8_t* d_dst, int outH, int outW, const int32_t* d_cx, const int32_t* d_bx, int kx,
+                       const int32_t* d_cy, const int32_t* d_by, int ky, void* d_ws, mdtile_stream_t stream);
+
 /* ControlNet / StableSR tile slicing (tile_methods/abstractdiffusion.py:475-544, 548-588): num_rects (<= 16) rectangles of size w x h
  * at rects_xy[2 i], rects_xy[2 i + 1] of d_x_in [N,C,H,W] are cut out, concatenated (tile-major, then the N samples: torch.cat over
  * the bboxes) and repeated `repeat` times for the sampler's cond / uncond copies:

@@ -22,6 +22,7 @@ OK, E_ARG, E_HIP, E_LIMIT = 0, -1, -2, -3
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 METHOD_MD, METHOD_MOD = 0, 1
 REGION_BG, REGION_FG = 0, 1
+RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
 BLEND_PARTIAL, BLEND_TILE_RANGE, BLEND_PACKED = 1, 2, 4
 BLEND_KERNEL_PLAIN, BLEND_KERNEL_LDS = 0, 1
 CONV_UPSAMPLE2X = 1
@@ -91,6 +92,11 @@ _SIGNATURES = {
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
     "mdtile_retouch_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mdtile_renoise_resize": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "mdtile_resample_ksize": (c_int, [c_int, c_int, c_int]),
+    "mdtile_resample_table": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mdtile_resample_u8_ws_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "mdtile_resample_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_void_p]),
     "mdtile_gather_rects": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, _IP, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mdtile_shard_init": (c_void_p, [c_int, _IP]),
     "mdtile_shard_unique_id": (c_int, [c_void_p]),
@@ -395,6 +401,66 @@ def renoise_resize(mask: torch.Tensor, size: Tuple[int, int], strength: float) -
     h, w = int(size[0]), int(size[1])
     out = torch.empty((h, w), dtype=torch.float32, device=mask.device)
     _check(lib().mdtile_renoise_resize(_p(mask), H, W, float(strength), _p(out), h, w, _stream()), "mdtile_renoise_resize")
+    return out
+
+_RESAMPLE_TABLES: dict = {}      # (in, out, filter) -> (coef [out, ksize] int32, bounds [out, 2] int32), host arrays; a job asks for a handful
+
+
+def resample_tables(in_size: int, out_size: int, filter: int):
+    """The tap table of one axis of resize_u8 (mdtile_resample_table, defined in include/mdtile.h): (coef [out, ksize], bounds [out, 2]) as numpy
+    int32 arrays, computed on the host and kept per (in, out, filter).  The arrays are shared: do not write to them."""
+    import numpy as np
+    key = (int(in_size), int(out_size), int(filter))
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    L = lib()
+    ksize = L.mdtile_resample_ksize(*key)
+    if ksize <= 0:
+        raise MdtileError(f"resample_tables: bad arguments {key[0]} -> {key[1]}, filter {key[2]} (sizes >= 1, filter RESAMPLE_NEAREST / RESAMPLE_LANCZOS)")
+    coef = np.empty((key[1], ksize), np.int32)
+    bounds = np.empty((key[1], 2), np.int32)
+    _check(L.mdtile_resample_table(key[0], key[1], key[2], c_void_p(coef.ctypes.data), c_void_p(bounds.ctypes.data)), "mdtile_resample_table")
+    if len(_RESAMPLE_TABLES) >= 32:
+        _RESAMPLE_TABLES.clear()
+    _RESAMPLE_TABLES[key] = (coef, bounds)
+    return coef, bounds
+
+
+def resize_u8(img_u8: torch.Tensor, size: Tuple[int, int], filter: int) -> torch.Tensor:
+    """Pillow's Image.resize for 8-bit images, bit for bit (include/mdtile.h): img_u8 [H, W] or [H, W, 3] bytes on the GPU -> size = (out_h, out_w),
+    filter RESAMPLE_LANCZOS or RESAMPLE_NEAREST.  Runs on the input's device and its current stream; any strides and any alignment."""
+    if not isinstance(img_u8, torch.Tensor):
+        raise TypeError("img_u8 must be a tensor")
+    if img_u8.device.type != "cuda":
+        raise MdtileError(f"img_u8 lives on {img_u8.device}; the mdtile engine only runs on the GPU (no CPU fallback)")
+    if img_u8.dtype != torch.uint8:
+        raise MdtileError(f"img_u8 has dtype {img_u8.dtype}, expected {torch.uint8}")
+    if not (img_u8.dim() == 2 or (img_u8.dim() == 3 and img_u8.shape[2] == 3)):
+        raise MdtileError(f"img_u8 has shape {tuple(img_u8.shape)}, expected [H, W] or [H, W, 3]")
+    if int(filter) not in (RESAMPLE_NEAREST, RESAMPLE_LANCZOS):
+        raise MdtileError(f"resize_u8: unknown filter {filter}")
+    img_u8 = img_u8.contiguous()
+    H, W, C = int(img_u8.shape[0]), int(img_u8.shape[1]), 1 if img_u8.dim() == 2 else 3
+    oh, ow = int(size[0]), int(size[1])
+    L = lib()
+    dev = img_u8.device
+    with torch.cuda.device(dev):
+        def axis(n_in, n_out):      # Lanczos skips an axis that keeps its size; Nearest always has both tables
+            if int(filter) == RESAMPLE_LANCZOS and n_in == n_out:
+                return None, None, 0
+            coef, bounds = resample_tables(n_in, n_out, filter)
+            return torch.from_numpy(coef).to(dev), torch.from_numpy(bounds).to(dev), coef.shape[1]
+        if H < 1 or W < 1 or oh < 1 or ow < 1:
+            raise MdtileError(f"resize_u8: bad sizes {H} x {W} -> {oh} x {ow}")
+        cx, bx, kx = axis(W, ow)
+        cy, by, ky = axis(H, oh)
+        out = torch.empty((oh, ow) if C == 1 else (oh, ow, 3), dtype=torch.uint8, device=dev)
+        ws = None
+        if kx and ky:
+            ws = torch.empty(max(1, L.mdtile_resample_u8_ws_size(H, W, C, oh, ow)), dtype=torch.uint8, device=dev)
+        _check(L.mdtile_resample_u8(_p(img_u8), H, W, C, _p(out), oh, ow, _p(cx), _p(bx), kx, _p(cy), _p(by), ky, _p(ws), _stream()),
+               "mdtile_resample_u8")
     return out
 
 

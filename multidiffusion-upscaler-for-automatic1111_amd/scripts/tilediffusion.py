@@ -25,7 +25,7 @@ from modules.processing import opt_f
 from tile_methods.abstractdiffusion import AbstractDiffusion
 from tile_methods.mixtureofdiffusers import MixtureOfDiffusers
 from tile_methods.multidiffusion import MultiDiffusion
-from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, splitable)
+from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, splitable, upscale_init_image)
 
 CFG_PATH_NOTE = "region_configs"
 BBOX_MAX_NUM = min(getattr(shared.cmd_opts, "md_max_regions", 8), 16)
@@ -118,7 +118,7 @@ class Script(scripts.Script):
                 control_tensor_cpu: bool,
                 enable_bbox_control: bool, draw_background: bool, causal_layers: bool,
                 *bbox_control_states: List[Any]):
-        self.reset()   # undo leftovers of a job that died half-way
+        self.reset(p=p)   # undo leftovers of a job that died half-way
         if not enabled:
             return
 
@@ -140,7 +140,11 @@ class Script(scripts.Script):
                 pass
             if upscaler is not None and upscaler.name != "None":
                 print(f"[Tiled Diffusion] upscaling image with {upscaler.name}...")
-                image = upscaler.scaler.upscale(image, scale_factor, upscaler.data_path)
+                # the host's upscaler.scaler.upscale(image, scale_factor, upscaler.data_path) with its Pillow resizes on the engine; the
+                # upscaled bytes stay on the device for Noise Inversion's renoise mask (AbstractDiffusion.renoise_mask)
+                image, image_bytes = upscale_init_image(image, upscaler, scale_factor)
+                if image_bytes is not None:
+                    p.init_image_bytes_md = (image, image_bytes)
                 p.extra_generation_params["Tiled Diffusion upscaler"] = upscaler.name
                 p.extra_generation_params["Tiled Diffusion scale factor"] = scale_factor
                 for i in range(len(p.init_images)):       # folder-based batches hold several entries: all become the upscaled image
@@ -213,7 +217,7 @@ class Script(scripts.Script):
     def postprocess(self, p, processed, enabled, *args):
         if not enabled:
             return
-        self.reset()
+        self.reset(p=p)
         if hasattr(p, "init_images") and hasattr(p, "init_images_original_md"):
             p.init_images.clear()       # keep the list OBJECT: XYZ-plot works on shallow copies of p
             p.init_images.extend(p.init_images_original_md)
@@ -307,7 +311,9 @@ class Script(scripts.Script):
         mdtile.region_noise(work, regions)
         return work.to(noise.dtype)
 
-    def reset(self, keep_sampler_hijack: bool = False):
+    def reset(self, keep_sampler_hijack: bool = False, p=None):
+        if p is not None and hasattr(p, "init_image_bytes_md"):      # the upscaled init image on the device (process): a job's, not the next one's
+            del p.init_image_bytes_md
         if not keep_sampler_hijack and hasattr(Script, "create_sampler_original_md"):
             sd_samplers.create_sampler = Script.create_sampler_original_md
             del Script.create_sampler_original_md

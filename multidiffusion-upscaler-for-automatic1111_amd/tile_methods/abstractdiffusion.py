@@ -444,12 +444,17 @@ class AbstractDiffusion:
     def renoise_mask(self, p, size) -> Optional[Tensor]:
         """[H, W] weight of fresh noise: where the guided filter says the input image has detail, scaled by the renoise strength
         (upstream :607-621).  An RGB init image goes up as its interleaved bytes and is made grey on the GPU; any other mode is converted
-        on the host first.  Filter and resize both run on the engine (mdtile_retouch_mask, mdtile_renoise_resize)."""
+        on the host first; an image the script has just upscaled on the engine is still on the device and is not uploaded again.  Filter and
+        resize both run on the engine (mdtile_retouch_mask, mdtile_renoise_resize)."""
         if self.noise_inverse_renoise_strength <= 0:
             return None
         import numpy as np
         img = p.init_images[0]
-        pixels = np.asarray(img if img.mode == "RGB" else img.convert("L"))
+        kept = getattr(p, "init_image_bytes_md", None)      # (image, its bytes on the device) left by the script's upscale
+        if kept is not None and kept[0] is img:
+            pixels = kept[1]
+        else:
+            pixels = np.asarray(img if img.mode == "RGB" else img.convert("L"))
         m = get_retouch_mask(pixels, self.noise_inverse_renoise_kernel)     # module attribute, looked up per call (tests replace it)
         m = torch.as_tensor(m).to(devices.device, torch.float32).contiguous()
         return mdtile.renoise_resize(m, size, self.noise_inverse_renoise_strength)

@@ -6,6 +6,7 @@ computation routed through the mdtile engine (libmdtile.so, include/mdtile.h):
     gaussian_weights  upstream utils.py:180-194  -> mdtile_gaussian_weights
     feather_mask      upstream utils.py:196-214  -> mdtile_feather_mask
     get_retouch_mask  upstream utils.py:216-247  -> mdtile_retouch_mask (upstream: OpenCV box filters on the CPU; no OpenCV here)
+    upscale_init_image  the host's Upscaler.upscale as scripts/tilediffusion.py:141-147 calls it -> mdtile_resample_u8 for its Pillow resizes
 
 Prompt / cond helpers stay thin host-side Python (they only forward to `modules.prompt_parser`).
 """
@@ -14,7 +15,7 @@ from __future__ import annotations
 import math
 from collections import namedtuple
 from enum import Enum
-from typing import Any, Dict, List, Tuple, Union
+from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -208,6 +209,75 @@ def get_retouch_mask(img_input, kernel_size: int) -> Tensor:
             warnings.simplefilter("ignore", UserWarning)
             img_input = torch.from_numpy(arr)
     return mdtile.retouch_mask(img_input.to(devices.device).contiguous(), int(round(kernel_size)))
+
+
+# the host's two resampling upscalers, by the name they are listed under AND the class behind it (an extension may reuse a name)
+ENGINE_UPSCALERS = {("Lanczos", "UpscalerLanczos"): mdtile.RESAMPLE_LANCZOS, ("Nearest", "UpscalerNearest"): mdtile.RESAMPLE_NEAREST}
+
+
+def image_to_device(image) -> Tensor:
+    """The bytes of an "RGB" / "L" PIL image as a uint8 tensor [H, W, 3] / [H, W] on devices.device."""
+    import warnings
+    import numpy as np
+    with warnings.catch_warnings():     # np.asarray(PIL image) is read-only; it is only read here
+        warnings.simplefilter("ignore", UserWarning)
+        return torch.from_numpy(np.asarray(image)).to(devices.device)
+
+
+def image_from_device(t: Tensor):
+    """uint8 [H, W, 3] / [H, W] on the device -> PIL image, through one pinned staging buffer (torch keeps it for the next job)."""
+    from PIL import Image
+    if t.device.type == "cuda":
+        host = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(t, non_blocking=True)
+        torch.cuda.current_stream(t.device).synchronize()
+    else:
+        host = t
+    return Image.fromarray(host.numpy())
+
+
+def upscale_init_image(image, upscaler, scale: float) -> Tuple[Any, Optional[Tensor]]:
+    """The host's `upscaler.scaler.upscale(image, scale, upscaler.data_path)`, step by step, with every Pillow resize of it on the engine
+    (mdtile.resize_u8: the same bytes, include/mdtile.h): the rounds of the built-in Lanczos / Nearest upscalers and the Lanczos fit to the
+    multiple of 8 that ends every upscale.  A model upscaler's rounds stay the host's `do_upscale`.  The image goes up once, stays on the
+    device between resizes and comes back once.  Returns (PIL image, its bytes on the device or None when the engine did not run); an image
+    that is neither "RGB" nor "L", or an upscaler without `do_upscale`, takes the host's call untouched."""
+    scaler = upscaler.scaler
+    if image.mode not in ("RGB", "L") or not hasattr(scaler, "do_upscale"):
+        return scaler.upscale(image, scale, upscaler.data_path), None
+    builtin = ENGINE_UPSCALERS.get((upscaler.name, type(scaler).__name__))
+    scaler.scale = scale
+    dest_w = int(image.width * scale // 8 * 8)
+    dest_h = int(image.height * scale // 8 * 8)
+    img, t = image, None                # the current image on the host / its bytes on the device: at least one of them is set
+    w, h = image.size
+    for _ in range(3):
+        if w >= dest_w and h >= dest_h:
+            break
+        before = (w, h)
+        if builtin is not None:
+            if t is None:
+                t = image_to_device(img)
+            t, img = mdtile.resize_u8(t, (int(h * scale), int(w * scale)), builtin), None
+            w, h = int(t.shape[1]), int(t.shape[0])
+        else:
+            if img is None:
+                img = image_from_device(t)
+            img, t = scaler.do_upscale(img, upscaler.data_path), None
+            w, h = img.size
+        if (w, h) == before:
+            break
+    if (w, h) != (dest_w, dest_h):
+        if t is None and img.mode not in ("RGB", "L"):      # a model that changed the mode: the host's own fit
+            from PIL import Image
+            lanczos = Image.Resampling.LANCZOS if hasattr(Image, "Resampling") else Image.LANCZOS
+            return img.resize((dest_w, dest_h), resample=lanczos), None
+        if t is None:
+            t = image_to_device(img)
+        t, img = mdtile.resize_u8(t, (dest_h, dest_w), mdtile.RESAMPLE_LANCZOS), None
+    if img is None:
+        img = image_from_device(t)
+    return img, t
 
 
 def null_decorator(fn):

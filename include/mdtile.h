@@ -274,6 +274,42 @@ size_t mdtile_resample_u8_ws_size(int H, int W, int C, int outH, int outW);
 int mdtile_resample_u8(const uint8_t* d_src, int H, int W, int C, uint8_t* d_dst, int outH, int outW, const int32_t* d_cx, const int32_t* d_bx, int kx,
                        const int32_t* d_cy, const int32_t* d_by, int ky, void* d_ws, mdtile_stream_t stream);
 
+/* Colour fix of an img2img result against its init image (StableSR's wavelet / AdaIN colour fix, which exists upstream only as CPU float code of
+ * another extension), on bytes and DEFINED here, so that it is checked bit for bit.
+ * Inputs: content (the decoded result) and style (the init image), both uint8, [H, W, C] interleaved or [H, W], C in {1, 3}, the same shape,
+ * H * W * C < 2^31.  Channels are independent.  Anything else: MDTILE_E_ARG.
+ *   WAVELET   The literal definition works per channel on byte values as reals:
+ *               blur_r(x)    the 3x3 kernel [[1,2,1],[2,4,2],[1,2,1]] / 16 with dilation r, after replicate padding by r
+ *               decompose(x) for i = 0 .. 4:  low = blur_{2^i}(x);  high += x - low;  x = low
+ *               out = clamp(floor(high(content) + low(style) + 1/2), 0, 255)
+ *             Three steps reduce it to integers: high(content) telescopes to content - low5(content); every step is linear, so
+ *             out = content + low5(style - content); the 3x3 kernel is [1,2,1] (x) [1,2,1] and operators on different axes commute, so low5 is
+ *             five 1-D levels along one axis, then five along the other.  The integer form:
+ *               d = style - content                                                                   (int, |d| <= 255)
+ *               level k on an axis of length n, r = 2^k:
+ *                   v'[i] = v[clamp(i - r, 0, n - 1)] + 2 * v[i] + v[clamp(i + r, 0, n - 1)]           (no division)
+ *               after 10 levels |v| <= 255 * 2^20 < 2^28;  out = clamp((content * 2^20 + v + 2^19) >> 20, 0, 255)   (int32, arithmetic shift)
+ *             No byte depends on block shape, pass order or summation order.  THE CLAMP IS PER LEVEL: padding the input once by 31 and then
+ *             convolving is a different function.
+ *   ADAIN     per channel and pointwise, hence a 256-entry table:
+ *               mdtile_hist_u8   the exact uint32 counts [C][256] of an image, on the device
+ *               on the host (mdtile.adain_lut), per channel from the counts as integers: n, S1 = sum x * count[x], S2 = sum x^2 * count[x]
+ *                   mean = S1 / n
+ *                   var  = (n * S2 - S1^2) / (n * (n - 1))         (integer numerator and denominator, one division; 0 when n == 1)
+ *                   std  = sqrt(var + 0.65025)                     (StableSR's eps 1e-5 in [0, 1] units, times 255^2)
+ *                   lut[c][x] = clamp(floor((x - mean_c) / std_c * std_s + mean_s + 1/2), 0, 255)      (float64, in the order written; _c of the
+ *                                                                                                       content, _s of the style)
+ *               mdtile_lut_u8    applies lut[c] to channel c, on the device
+ *             AdaIN needs no resize of the style image.  A flat content channel maps through std = sqrt(0.65025) and stays finite.
+ *   mdtile_colorfix_wavelet_ws_size  bytes of the int32 intermediate [H, W, C] (0 for arguments the call would refuse)
+ *   mdtile_colorfix_wavelet          d_content, d_style -> d_out, bytes at any alignment; d_ws: that many bytes, 16-byte aligned
+ *   mdtile_hist_u8                   d_hist [C][256] uint32 is zeroed and filled on the stream
+ *   mdtile_lut_u8                    d_lut [C][256] uint8 on the device; d_out [H, W, C] */
+size_t mdtile_colorfix_wavelet_ws_size(int H, int W, int C);
+int mdtile_colorfix_wavelet(const uint8_t* d_content, const uint8_t* d_style, uint8_t* d_out, int H, int W, int C, void* d_ws, mdtile_stream_t stream);
+int mdtile_hist_u8(const uint8_t* d_img, int H, int W, int C, uint32_t* d_hist, mdtile_stream_t stream);
+int mdtile_lut_u8(const uint8_t* d_img, int H, int W, int C, const uint8_t* d_lut, uint8_t* d_out, mdtile_stream_t stream);
+
 /* ControlNet / StableSR tile slicing (tile_methods/abstractdiffusion.py:475-544, 548-588): num_rects (<= 16) rectangles of size w x h
  * at rects_xy[2 i], rects_xy[2 i + 1] of d_x_in [N,C,H,W] are cut out, concatenated (tile-major, then the N samples: torch.cat over
  * the bboxes) and repeated `repeat` times for the sampler's cond / uncond copies:

@@ -51,7 +51,10 @@ __device__ __forceinline__ int2 window_of(int2 b, int k, int size) {
     return make_int2(lo, min(max(b.y, 0), min(k, size - lo)));
 }
 
-__device__ __forceinline__ uint8_t clip8(int acc) { return (uint8_t)min(max(acc >> RS_PRECISION, 0), 255); }
+// clamp(acc >> 22, 0, 255), written as the clamp of acc to [0, 2^30) BEFORE the shift: the same value for every int acc.  In the shift-then-clamp
+// form hipcc fuses two bytes of a packed word into one v_ashr_pk_u8_i32 and relies on the upper half of its result being zero, which an MI355X
+// does not give (csrc/colorfix.hip: fix8).
+__device__ __forceinline__ uint8_t clip8(int acc) { return (uint8_t)((uint32_t)min(max(acc, 0), (256 << RS_PRECISION) - 1) >> RS_PRECISION); }
 
 // the taps of one output pixel over `px` (its first source pixel), from registers (REG: n <= RS_KREG, taps past n are zero) or from the table
 template <int C, bool REG, typename P>

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -97,6 +98,10 @@ _SIGNATURES = {
     "mdtile_resample_u8_ws_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "mdtile_resample_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                    c_void_p, c_void_p]),
+    "mdtile_colorfix_wavelet_ws_size": (c_size_t, [c_int, c_int, c_int]),
+    "mdtile_colorfix_wavelet": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mdtile_hist_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mdtile_lut_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mdtile_gather_rects": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, _IP, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mdtile_shard_init": (c_void_p, [c_int, _IP]),
     "mdtile_shard_unique_id": (c_int, [c_void_p]),
@@ -462,6 +467,97 @@ def resize_u8(img_u8: torch.Tensor, size: Tuple[int, int], filter: int) -> torch
         _check(L.mdtile_resample_u8(_p(img_u8), H, W, C, _p(out), oh, ow, _p(cx), _p(bx), kx, _p(cy), _p(by), ky, _p(ws), _stream()),
                "mdtile_resample_u8")
     return out
+
+
+def _u8_image(t: torch.Tensor, name: str) -> Tuple[torch.Tensor, int, int, int]:
+    """A uint8 image [H, W] / [H, W, 3] on the GPU, made contiguous -> (tensor, H, W, C)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor")
+    if t.device.type != "cuda":
+        raise MdtileError(f"{name} lives on {t.device}; the mdtile engine only runs on the GPU (no CPU fallback)")
+    if t.dtype != torch.uint8:
+        raise MdtileError(f"{name} has dtype {t.dtype}, expected {torch.uint8}")
+    if not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] in (1, 3))):
+        raise MdtileError(f"{name} has shape {tuple(t.shape)}, expected [H, W], [H, W, 1] or [H, W, 3]")
+    if t.numel() == 0:
+        raise MdtileError(f"{name} has shape {tuple(t.shape)}: an empty image")
+    return t.contiguous(), int(t.shape[0]), int(t.shape[1]), 1 if t.dim() == 2 else int(t.shape[2])
+
+
+def colorfix_wavelet(content: torch.Tensor, style: torch.Tensor) -> torch.Tensor:
+    """The wavelet colour fix on bytes, bit for bit the definition in include/mdtile.h: the content's detail over the style's low frequencies,
+    out = clamp((content * 2^20 + low5(style - content) + 2^19) >> 20, 0, 255).  content, style: uint8 [H, W] or [H, W, 3] of the same shape on
+    one GPU, any strides and any alignment -> a new tensor of that shape.  Runs on the content's device and its current stream."""
+    content, H, W, C = _u8_image(content, "content")
+    style, *_ = _u8_image(style, "style")
+    if style.shape != content.shape or style.device != content.device:
+        raise MdtileError(f"colorfix_wavelet: style {tuple(style.shape)} on {style.device} does not match content {tuple(content.shape)} on "
+                          f"{content.device} (resize the style first: resize_u8)")
+    L = lib()
+    with torch.cuda.device(content.device):
+        ws = torch.empty(max(4, L.mdtile_colorfix_wavelet_ws_size(H, W, C) // 4), dtype=torch.int32, device=content.device)
+        out = torch.empty_like(content)
+        _check(L.mdtile_colorfix_wavelet(_p(content), _p(style), _p(out), H, W, C, _p(ws), _stream()), "mdtile_colorfix_wavelet")
+    return out
+
+
+def hist_u8(img: torch.Tensor) -> torch.Tensor:
+    """Exact counts of every byte value per channel: img uint8 [H, W] / [H, W, 3] on the GPU -> int64 [C, 256] on the same device (the
+    engine's uint32 counts, widened).  Runs on the input's device and its current stream."""
+    img, H, W, C = _u8_image(img, "img")
+    with torch.cuda.device(img.device):
+        counts = torch.empty((C, 256), dtype=torch.int32, device=img.device)      # uint32 bit patterns; below 2^31 by the size limit
+        _check(lib().mdtile_hist_u8(_p(img), H, W, C, _p(counts), _stream()), "mdtile_hist_u8")
+        return counts.to(torch.int64)
+
+
+def adain_lut(hist_content, hist_style):
+    """The AdaIN colour fix as per-channel 256-entry tables, on the HOST (include/mdtile.h): hist_* [C, 256] counts (tensor, array or lists) of
+    the content and of the style image -> numpy uint8 [C, 256].  Sums are Python integers, mean and variance one correctly rounded division
+    each, the table float64 in the order written in the header."""
+    import numpy as np
+
+    def stats(counts):
+        counts = [int(v) for v in counts]
+        n = sum(counts)
+        s1 = sum(x * c for x, c in enumerate(counts))
+        s2 = sum(x * x * c for x, c in enumerate(counts))
+        if n < 1:
+            raise MdtileError("adain_lut: an empty histogram")
+        mean = s1 / n
+        var = (n * s2 - s1 * s1) / (n * (n - 1)) if n > 1 else 0.0
+        return mean, math.sqrt(var + 0.65025)
+
+    hc = hist_content.cpu().tolist() if isinstance(hist_content, torch.Tensor) else np.asarray(hist_content).tolist()
+    hs = hist_style.cpu().tolist() if isinstance(hist_style, torch.Tensor) else np.asarray(hist_style).tolist()
+    if len(hc) != len(hs) or len(hc) not in (1, 3) or any(len(r) != 256 for r in hc + hs):
+        raise MdtileError("adain_lut: both histograms are [C, 256] with the same C in {1, 3}")
+    x = np.arange(256, dtype=np.float64)
+    lut = np.empty((len(hc), 256), np.uint8)
+    for c in range(len(hc)):
+        mean_c, std_c = stats(hc[c])
+        mean_s, std_s = stats(hs[c])
+        lut[c] = np.clip(np.floor((x - mean_c) / std_c * std_s + mean_s + 0.5), 0, 255).astype(np.uint8)
+    return lut
+
+
+def lut_u8(img: torch.Tensor, lut) -> torch.Tensor:
+    """out[y, x, c] = lut[c][img[y, x, c]]: img uint8 [H, W] / [H, W, 3] on the GPU, lut uint8 [C, 256] (tensor on any device, or array)."""
+    img, H, W, C = _u8_image(img, "img")
+    lut = torch.as_tensor(lut)
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (C, 256):
+        raise MdtileError(f"lut_u8: lut is {lut.dtype} {tuple(lut.shape)}, expected torch.uint8 ({C}, 256)")
+    with torch.cuda.device(img.device):
+        lut = lut.to(img.device).contiguous()
+        out = torch.empty_like(img)
+        _check(lib().mdtile_lut_u8(_p(img), H, W, C, _p(lut), _p(out), _stream()), "mdtile_lut_u8")
+    return out
+
+
+def colorfix_adain(content: torch.Tensor, style: torch.Tensor) -> torch.Tensor:
+    """The AdaIN colour fix on bytes (include/mdtile.h): every channel of the content shifted and scaled to the style's mean and deviation.
+    content, style: uint8 [H, W] / [H, W, 3] on the GPU with the same channel count; their sizes may differ."""
+    return lut_u8(content, adain_lut(hist_u8(content), hist_u8(style)))
 
 
 def gather_rects(x_in: torch.Tensor, rects_xy: Sequence[Tuple[int, int]], w: int, h: int, repeat: int = 1, tile_major: bool = True) -> torch.Tensor:

@@ -11,3 +11,8 @@ def preload(parser):
         help="Matrix-core arithmetic of Tiled VAE while it is enabled: bf16x3 (split-bf16, fp32 class), f32 (exact), bf16 / f16 (one MFMA per product, "
              "the arithmetic class of a bfloat16 / float16 VAE), auto (from the VAE's dtype: float16 -> f16, bfloat16 -> bf16, else bf16x3). "
              "Default: not set, the engine's mode is left alone (bf16x3 unless the process set another).")
+    parser.add_argument(
+        "--mdtile-color-fix", type=str, default=None, choices=["wavelet", "adain"],
+        help="Tie the colours of every Tiled Diffusion img2img result to its (upscaled) init image, on the GPU: wavelet (the result's detail over "
+             "the init image's low frequencies, five dilated 3x3 levels) or adain (per-channel mean and deviation of the init image). "
+             "Default: not set, results are left as decoded.")

@@ -25,7 +25,8 @@ from modules.processing import opt_f
 from tile_methods.abstractdiffusion import AbstractDiffusion
 from tile_methods.mixtureofdiffusers import MixtureOfDiffusers
 from tile_methods.multidiffusion import MultiDiffusion
-from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, splitable, upscale_init_image)
+from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, color_fix_image, splitable,
+                              upscale_init_image)
 
 CFG_PATH_NOTE = "region_configs"
 BBOX_MAX_NUM = min(getattr(shared.cmd_opts, "md_max_regions", 8), 16)
@@ -156,6 +157,10 @@ class Script(scripts.Script):
                 p.width, p.height = int(scale_factor * p.width_original_md), int(scale_factor * p.height_original_md)
         elif overwrite_size:
             p.width, p.height = image_width, image_height
+        if is_img2img and self.color_fix_mode() is not None:       # postprocess_image applies it to every image of the job
+            if getattr(p, "extra_generation_params", None) is None:
+                p.extra_generation_params = {}
+            p.extra_generation_params["Tiled Diffusion color fix"] = self.color_fix_mode()
 
         bbox_settings = build_bbox_settings(bbox_control_states) if enable_bbox_control else {}
         if not (splitable(p.width, p.height, tile_width, tile_height, overlap) or enable_bbox_control or (is_img2img and noise_inverse)):
@@ -213,6 +218,19 @@ class Script(scripts.Script):
     def postprocess_batch(self, p, enabled, *args, **kwargs):
         if enabled and self.delegate is not None:
             self.delegate.reset_controlnet_tensors()
+
+    @staticmethod
+    def color_fix_mode():
+        """--mdtile-color-fix: "wavelet", "adain" or None (not set, or a host that never heard of the option)."""
+        return getattr(shared.cmd_opts, "mdtile_color_fix", None)
+
+    def postprocess_image(self, p, pp, enabled, *args):
+        """The host calls this per image before saving, and before `postprocess`: p.init_images[0] is still the (upscaled) init image and
+        p.init_image_bytes_md, if the upscale ran on the engine, its bytes on the device."""
+        mode = self.color_fix_mode()
+        if not enabled or mode is None or not (hasattr(p, "init_images") and len(p.init_images or []) > 0):
+            return
+        pp.image = color_fix_image(pp.image, p.init_images[0], mode, getattr(p, "init_image_bytes_md", None))
 
     def postprocess(self, p, processed, enabled, *args):
         if not enabled:

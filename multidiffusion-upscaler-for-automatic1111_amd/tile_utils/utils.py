@@ -7,6 +7,8 @@ computation routed through the mdtile engine (libmdtile.so, include/mdtile.h):
     feather_mask      upstream utils.py:196-214  -> mdtile_feather_mask
     get_retouch_mask  upstream utils.py:216-247  -> mdtile_retouch_mask (upstream: OpenCV box filters on the CPU; no OpenCV here)
     upscale_init_image  the host's Upscaler.upscale as scripts/tilediffusion.py:141-147 calls it -> mdtile_resample_u8 for its Pillow resizes
+    color_fix_image   nothing upstream (StableSR's wavelet / AdaIN colour fix, CPU code of another extension) -> mdtile_colorfix_wavelet,
+                      mdtile_hist_u8 + mdtile_lut_u8; opt-in, --mdtile-color-fix
 
 Prompt / cond helpers stay thin host-side Python (they only forward to `modules.prompt_parser`).
 """
@@ -278,6 +280,34 @@ def upscale_init_image(image, upscaler, scale: float) -> Tuple[Any, Optional[Ten
     if img is None:
         img = image_from_device(t)
     return img, t
+
+
+COLOR_FIX_MODES = ("wavelet", "adain")
+
+
+def color_fix_image(image, style_image, mode: str, kept=None):
+    """The colour fix of --mdtile-color-fix on one finished image: `image` (the decoded result) keeps its detail and takes the low frequencies
+    (mode "wavelet") or the per-channel mean and deviation ("adain") of `style_image` (the init image), on bytes as include/mdtile.h defines
+    them.  The result goes up once; the style comes from `kept` = (PIL image, its bytes on the device), which Script.process leaves as
+    p.init_image_bytes_md, when kept[0] IS style_image, and is uploaded otherwise.  A style of another mode is converted to the result's; one of
+    another size is resized with Lanczos on the engine for "wavelet" ("adain" only reads its statistics).  Returns a PIL image; an image that is
+    neither "RGB" nor "L" comes back untouched."""
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color fix mode {mode!r}: expected one of {COLOR_FIX_MODES}")
+    if image.mode not in ("RGB", "L"):
+        return image
+    content = image_to_device(image)
+    if kept is not None and kept[0] is style_image and style_image.mode == image.mode:
+        style = kept[1]
+    else:
+        if style_image.mode != image.mode:
+            style_image = style_image.convert(image.mode)
+        style = image_to_device(style_image)
+    if mode == "adain":
+        return image_from_device(mdtile.colorfix_adain(content, style))
+    if tuple(style.shape[:2]) != tuple(content.shape[:2]):
+        style = mdtile.resize_u8(style, (int(content.shape[0]), int(content.shape[1])), mdtile.RESAMPLE_LANCZOS)
+    return image_from_device(mdtile.colorfix_wavelet(content, style))
 
 
 def null_decorator(fn):

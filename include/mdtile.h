@@ -98,6 +98,18 @@ void mdtile_plan_destroy(mdtile_plan* plan);
 int mdtile_plan_info(const mdtile_plan* plan, int* info8);
 /* xywh[4*num_tiles], row-major tile order (y outer) == upstream bbox list order */
 int mdtile_plan_bboxes(const mdtile_plan* plan, int* xywh);
+/* The canvas closed in x (360-degree panoramas): the same plan with its tile columns laid on a circle, so that tiles span x = w-1 -> 0.
+ *   tile and overlap clamp, rows, batching and tile order (row-major, y outer): as mdtile_plan_create(clamp = 1)
+ *   cols = ceil(w / (tw - ov));  x_c = (int)(c * (double)w / cols);  tile c covers the columns (x_c + i) mod w, i in [0, tw)
+ *   the origin stride w / cols is at most tw - ov: cyclic neighbours overlap by at least ov everywhere, the seam included
+ *   effective tw >= w: NULL + mdtile_last_error (a tile would meet itself)
+ * mdtile_plan_info / mdtile_plan_bboxes work on such a plan; a box reports x_c, so x_c + tw may exceed w.  mdtile_plan_wrap_x: 1 for such a plan, else 0.
+ * mdtile_weight_map_add_grid, mdtile_gather, mdtile_gather_all and mdtile_blend take a wrap-x plan (kernels of their own, csrc/wrap.hip): column
+ * indices mod w, the covering tiles summed in ascending tile index -- at a seam pixel tile column 0 before column cols-1 -- so results equal the
+ * sequential `+=` loop over the tile list bit for bit.  REFUSED on a wrap-x plan (MDTILE_E_ARG, the text names the reason): num_regions > 0, any
+ * MDTILE_BLEND_* flag, a row band, mdtile_gather_range, mdtile_blend_finalize, the packed destination of mdtile_gather_all, mdtile_blend_dispatch. */
+mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs);
+int mdtile_plan_wrap_x(const mdtile_plan* plan);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Weight maps (init time, device).

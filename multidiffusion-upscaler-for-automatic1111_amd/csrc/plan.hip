@@ -1,6 +1,7 @@
 // Grid planning: host-side integer logic + the small device lookup tables the gather-formulated kernels use.
 // Upstream behaviour followed: tile_utils/utils.py:160-177 (split_bboxes), tile_methods/abstractdiffusion.py:173-186
 // (init_grid_bbox), scripts/tilevae.py:390-462 (split_tiles / get_best_tile_size).
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -148,6 +149,95 @@ extern "C" mdtile_plan* mdtile_plan_create(int w, int h, int tile_w, int tile_h,
     p->d_colquad = p->d_rowinfo = nullptr;
     return p;
 }
+
+// ---- the canvas closed in x (panoramas) ---------------------------------------------------------------------------
+// start and length of the cyclic run of set members (the covering tile columns of a canvas column or quad: the tiles whose origin lies on the
+// arc of tw columns that ends at it); all members -> (0, n)
+static int cyclic_run(const std::vector<char>& member) {
+    const int n = (int)member.size();
+    int cnt = 0, first = 0;
+    for (int c = 0; c < n; ++c) {
+        cnt += member[c] ? 1 : 0;
+        if (member[c] && !member[(c + n - 1) % n]) first = c;
+    }
+    return first | (cnt << 16);
+}
+
+extern "C" mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs) {
+    if (w <= 0 || h <= 0 || tile_w <= 0 || tile_h <= 0 || tile_bs <= 0 || w > 65535 || h > 65535) {
+        mdt::set_error("mdtile_plan_create_wrap_x: bad arguments w=%d h=%d tile=%dx%d bs=%d", w, h, tile_w, tile_h, tile_bs);
+        return nullptr;
+    }
+    // the clamp of mdtile_plan_create(clamp = 1)
+    const int tw = tile_w < w ? tile_w : w, th = tile_h < h ? tile_h : h;
+    const int mn = tile_w < tile_h ? tile_w : tile_h;
+    int ov = overlap < mn - 4 ? overlap : mn - 4;
+    if (ov < 0) ov = 0;
+    if (tw >= w) {
+        mdt::set_error("mdtile_plan_create_wrap_x: tile width %d >= canvas width %d: a tile would meet itself across the seam", tw, w);
+        return nullptr;
+    }
+    if (tw - ov == 0 || th - ov == 0) {
+        mdt::set_error("mdtile_plan_create_wrap_x: overlap %d equals the canvas-clamped tile %dx%d (division by zero upstream)", ov, tw, th);
+        return nullptr;
+    }
+    // columns on the circle: stride w / cols <= tw - ov, so cyclic neighbours overlap by >= ov everywhere, the seam included
+    const int cols = (int)std::ceil((double)w / (double)(tw - ov));
+    std::vector<int> xs(cols), ys, rr;
+    for (int c = 0; c < cols; ++c) xs[c] = (int)((double)c * (double)w / (double)cols);
+    origins_1d(h, th, ov, ys);
+    if (xs.size() > 32767 || ys.size() > 32767) {
+        mdt::set_error("mdtile_plan_create_wrap_x: too many tiles");
+        return nullptr;
+    }
+    cover_ranges(h, th, ys, rr);
+
+    mdtile_plan* p = new mdtile_plan();
+    p->wrap_x = 1;
+    p->w = w; p->h = h; p->tw = tw; p->th = th; p->ov = ov;
+    p->cols = cols; p->rows = (int)ys.size(); p->T = p->cols * p->rows;
+    p->num_batches = (p->T + tile_bs - 1) / tile_bs;
+    p->tile_bs = (p->T + p->num_batches - 1) / p->num_batches;
+    // the block layout of mdtile_plan_create, so that mdt::plan_upload serves both kinds: [xs | ys | colrange | rowrange | pad | colquad | rowinfo]
+    const int W4 = (w + 3) / 4;
+    const size_t head = xs.size() + ys.size() + (size_t)w + rr.size();
+    p->quad_off = (head + 3) & ~(size_t)3;
+    p->table_len = p->quad_off + 4 * (size_t)W4 + 4 * (size_t)h;
+    p->h_table = new int[p->table_len]();
+    int* q = p->h_table;
+    p->h_xs = q; memcpy(q, xs.data(), xs.size() * sizeof(int)); q += xs.size();
+    p->h_ys = q; memcpy(q, ys.data(), ys.size() * sizeof(int)); q += ys.size();
+    int* cr = q; q += w;
+    memcpy(q, rr.data(), rr.size() * sizeof(int));
+    int* cq = p->h_table + p->quad_off;
+    p->nc_max = p->nr_max = 0;
+    std::vector<char> member(cols), qmember(cols);
+    for (int xq = 0; xq < W4; ++xq) {
+        std::fill(qmember.begin(), qmember.end(), 0);
+        for (int j = 0; j < 4 && 4 * xq + j < w; ++j) {
+            const int x = 4 * xq + j;
+            for (int c = 0; c < cols; ++c) {
+                member[c] = ((x - xs[c] + w) % w) < tw;
+                qmember[c] = qmember[c] || member[c];
+            }
+            cr[x] = cyclic_run(member);
+        }
+        cq[4 * xq] = cyclic_run(qmember);
+        if ((cq[4 * xq] >> 16) > p->nc_max) p->nc_max = cq[4 * xq] >> 16;
+    }
+    int* ri = cq + 4 * (size_t)W4;
+    for (int y = 0; y < h; ++y) {
+        const int f = rr[y] & 0xffff;
+        ri[4 * y + 0] = rr[y];
+        if ((rr[y] >> 16) > p->nr_max) p->nr_max = rr[y] >> 16;
+        for (int k = 0; k < 3; ++k) ri[4 * y + 1 + k] = f + k < (int)ys.size() ? ys[f + k] : 0;
+    }
+    p->d_xs = p->d_ys = p->d_colrange = p->d_rowrange = nullptr;
+    p->d_colquad = p->d_rowinfo = nullptr;
+    return p;
+}
+
+extern "C" int mdtile_plan_wrap_x(const mdtile_plan* p) { return p && p->wrap_x ? 1 : 0; }
 
 namespace mdt {
 int plan_upload(const mdtile_plan* cp) {

@@ -1,0 +1,315 @@
+// Horizontal wrap-around (panoramas): weight map, tile gather and overlap blend for a plan whose canvas is closed in x
+// (mdtile_plan_create_wrap_x).  Tile column c covers the canvas columns (xs[c] + i) mod W, i in [0, tw); the formulation is the
+// gather of blend.hip -- one thread owns its output pixels and walks the tiles that cover them -- so closing the canvas only changes WHICH
+// tile columns cover a canvas column: a cyclic run of the plan's column list instead of a plain range.  Nothing scatters across the seam.
+//
+// Order: the covering tiles are summed in ASCENDING tile index (rows outer, columns inner), which is the order of the sequential `+=` loop over
+// the tile list; at a seam pixel tile column 0 therefore comes before column cols - 1.  Per-term operations and epilogues are those of k_blend's
+// generic walk (blend.hip): Mixture of Diffusers w = tile_w * rescale[y, x], term out * w; MultiDiffusion weights > 1 ? buf / weights : buf.
+// fp32 accumulation from +0.0, -ffp-contract=off: results equal the sequential loop bit for bit.
+//
+// Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
+// mdtile_blend_finalize -- wrap-around is not combined with regions or with the multi-GPU partial path.
+#include "common.h"
+
+using namespace mdt;
+
+namespace {
+
+// the cyclic run (first | count << 16 over `cols` tile columns) walked in ascending column index: [0, head) then [first, first + count - head)
+struct ColRun {
+    int first, count, head;
+    __device__ __forceinline__ ColRun(int packed, int cols) {
+        first = packed & 0xffff;
+        count = packed >> 16;
+        head = first + count > cols ? first + count - cols : 0;
+    }
+    __device__ __forceinline__ int col(int k) const { return k < head ? k : first + (k - head); }
+};
+
+// canvas column x relative to a tile origin xo, on the circle of W columns: in [0, W); covered by the tile iff < tw
+__device__ __forceinline__ int rel_x(int x, int xo, int W) {
+    const int d = x - xo;
+    return d < 0 ? d + W : d;
+}
+
+// weights[p] += sum over the covering tiles, ascending tile index, of tile_w[...] (or 1.0)
+__global__ __launch_bounds__(256) void k_wrap_weight_grid(int W, int H, int tw, int cols, const int* __restrict__ xs, const int* __restrict__ ys,
+                                                          const int* __restrict__ colrange, const int* __restrict__ rowrange,
+                                                          const float* __restrict__ tile_w, float* __restrict__ weights) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= W * H) return;
+    const int y = idx / W, x = idx - y * W;
+    const ColRun run(colrange[x], cols);
+    const int rr = rowrange[y], r0 = rr & 0xffff, nr = rr >> 16;
+    float s = 0.0f;
+    for (int r = r0; r < r0 + nr; ++r) {
+        const int ty = y - ys[r];
+        for (int k = 0; k < run.count; ++k) {
+            const int tx = rel_x(x, xs[run.col(k)], W);
+            s += tile_w ? tile_w[ty * tw + tx] : 1.0f;
+        }
+    }
+    weights[idx] += s;
+}
+
+struct WrapGatherParams {
+    int W, H, tw, th, cols, tile_bs, N, C;
+    int t_lo, _pad;
+    const int *xs, *ys;
+    const void* x_in;
+    void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(WrapGatherParams) <= 4096, "kernel argument block must stay under 4 KiB");
+
+// x_tile[i*N + n, c, ty, tx] = x_in[n, c, y_i + ty, (x_i + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = tile
+template <typename T>
+__global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
+    const int tw4 = (P.tw + 3) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= tw4 * P.th) return;
+    const int ty = idx / tw4, tx0 = (idx - ty * tw4) << 2;
+    const int plane = blockIdx.y, n = plane / P.C, c = plane - n * P.C;
+    const int t = P.t_lo + blockIdx.z;
+    const int r = t / P.cols, cc = t - r * P.cols;
+    const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + P.ys[r] + ty) * P.W;
+    const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+    T* dst = reinterpret_cast<T*>(P.batch[b]) + (((size_t)i * P.N + n) * P.C + c) * ((size_t)P.th * P.tw) + (size_t)ty * P.tw + tx0;
+    int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw < W: one subtraction brings it back onto the canvas
+    if (sx >= P.W) sx -= P.W;
+    const int nvalid = P.tw - tx0 < 4 ? P.tw - tx0 : 4;
+    if (nvalid == 4 && sx + 3 < P.W) {    // the four source columns are consecutive in memory
+        float v[4];
+        load4<T>(srow + sx, v);
+        store4<T>(dst, v);
+    } else {
+        for (int j = 0; j < nvalid; ++j) {
+            const int x = sx + j < P.W ? sx + j : sx + j - P.W;
+            dst[j] = srow[x];
+        }
+    }
+}
+
+struct WrapBlendParams {
+    int W, H, tw, th, cols, tile_bs, N, C;
+    const int *xs, *ys;
+    const int4 *colquad, *rowinfo;
+    const float *weights, *tile_w, *rescale;
+    void* out;
+    const void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(WrapBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+
+// 4 consecutive elements at an address aligned to their total size (16 bytes of fp32, 8 bytes of a 16-bit type): one load instruction
+template <typename T> __device__ __forceinline__ void load4_aligned(const T* p, float (&o)[4]);
+template <> __device__ __forceinline__ void load4_aligned<float>(const float* p, float (&o)[4]) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+}
+template <> __device__ __forceinline__ void load4_aligned<__half>(const __half* p, float (&o)[4]) {
+    const ushort4 t = *reinterpret_cast<const ushort4*>(p);
+    o[0] = __half2float(__ushort_as_half(t.x)); o[1] = __half2float(__ushort_as_half(t.y));
+    o[2] = __half2float(__ushort_as_half(t.z)); o[3] = __half2float(__ushort_as_half(t.w));
+}
+template <> __device__ __forceinline__ void load4_aligned<__hip_bfloat16>(const __hip_bfloat16* p, float (&o)[4]) {
+    const ushort4 t = *reinterpret_cast<const ushort4*>(p);
+    o[0] = __uint_as_float((unsigned)t.x << 16); o[1] = __uint_as_float((unsigned)t.y << 16);
+    o[2] = __uint_as_float((unsigned)t.z << 16); o[3] = __uint_as_float((unsigned)t.w << 16);
+}
+
+// One thread owns one quad (4 consecutive canvas columns of one row; rows start at x = 0, so a quad never straddles the seam) for PP planes.
+// A TILE's row segment may straddle it: per candidate tile the quad is either one contiguous piece of the tile row (tile-relative x0 .. x0 + 3
+// all below tw) -- vector loads when that piece is also aligned in memory -- or it is cut by a tile edge / the seam: per-element loads of the
+// covered pixels only.
+template <typename T, int METHOD, int PP>
+__global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
+    const int W4 = (P.W + 3) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= W4 * P.H) return;
+    const int y = idx / W4, xq = idx - y * W4;
+    const int x0 = xq << 2;
+    const int p0 = blockIdx.y * PP;                        // the host guarantees N*C % PP == 0
+    const int nvalid = P.W - x0 < 4 ? P.W - x0 : 4;
+    const size_t tile_elems = (size_t)P.th * P.tw;
+
+    float acc[PP][4];
+#pragma unroll
+    for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
+
+    const ColRun run(P.colquad[xq].x, P.cols);
+    const int rq = P.rowinfo[y].x, r0 = rq & 0xffff, nr = rq >> 16;
+    float resc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (METHOD == MDTILE_METHOD_MOD) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
+    }
+
+    for (int r = r0; r < r0 + nr; ++r) {                   // ascending tile index: rows outer, columns inner
+        const int ty = y - P.ys[r];
+        for (int k = 0; k < run.count; ++k) {
+            const int c = run.col(k);
+            const int t = r * P.cols + c;
+            const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+            const int tx = rel_x(x0, P.xs[c], P.W);
+            const size_t roff = (size_t)ty * P.tw;        // the tile row inside a [th, tw] plane (and inside the tile-weight map)
+            const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * P.N * P.C + p0) * tile_elems + roff;
+            // one contiguous piece of the tile row, at an address aligned for the vector load in this plane and (tile_elems % 4 == 0) in the others
+            const bool whole = nvalid == 4 && tx + 3 < P.tw;
+            if (whole && (reinterpret_cast<uintptr_t>(row + tx) & (4 * sizeof(T) - 1)) == 0 && (tile_elems & 3) == 0) {
+                float wg[4] = {1.f, 1.f, 1.f, 1.f};
+                if (METHOD == MDTILE_METHOD_MOD) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) wg[j] = P.tile_w[roff + tx + j] * resc[j];
+                }
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) {
+                    float v[4];
+                    load4_aligned<T>(row + (size_t)pp * tile_elems + tx, v);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v[j] * wg[j];
+                        else acc[pp][j] += v[j];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int txj = tx + j;                      // tx < W, j < 4: one subtraction
+                    if (txj >= P.W) txj -= P.W;
+                    if (j >= nvalid || txj >= P.tw) continue;
+                    float wgt = 1.0f;
+                    if (METHOD == MDTILE_METHOD_MOD) wgt = P.tile_w[roff + txj] * resc[j];
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) {
+                        const float v = to_f32<T>(row[(size_t)pp * tile_elems + txj]);
+                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
+                        else acc[pp][j] += v;
+                    }
+                }
+            }
+        }
+    }
+
+    // MD normalisation: x = where(weights > 1, buf / weights, buf)
+    if (METHOD == MDTILE_METHOD_MD) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= nvalid) continue;
+            const float w = P.weights[(size_t)y * P.W + x0 + j];
+            if (w > 1.0f) {
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
+            }
+        }
+    }
+
+#pragma unroll
+    for (int pp = 0; pp < PP; ++pp) {
+        T* dst = reinterpret_cast<T*>(P.out) + ((size_t)(p0 + pp) * P.H + y) * P.W + x0;
+        if (nvalid == 4) store4<T>(dst, acc[pp]);
+        else {
+            dst[0] = from_f32<T>(acc[pp][0]);
+            if (nvalid > 1) dst[1] = from_f32<T>(acc[pp][1]);
+            if (nvalid > 2) dst[2] = from_f32<T>(acc[pp][2]);
+        }
+    }
+}
+
+template <typename T, int PP>
+void launch_wrap_blend(const WrapBlendParams& P, int method, hipStream_t s) {
+    dim3 grid(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / PP), block(256);
+    if (method == MDTILE_METHOD_MD) hipLaunchKernelGGL((k_wrap_blend<T, MDTILE_METHOD_MD, PP>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((k_wrap_blend<T, MDTILE_METHOD_MOD, PP>), grid, block, 0, s, P);
+}
+
+template <typename T>
+void launch_wrap_blend_planes(const WrapBlendParams& P, int method, hipStream_t s) {
+    // planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as blend.hip sizes k_blend
+    const int planes = P.N * P.C;
+    const long long work = (long long)P.H * ((P.W + 3) / 4) * planes;
+    if (planes % 4 == 0 && work / 4 >= 131072) launch_wrap_blend<T, 4>(P, method, s);
+    else if (planes % 2 == 0 && work / 2 >= 131072) launch_wrap_blend<T, 2>(P, method, s);
+    else launch_wrap_blend<T, 1>(P, method, s);
+}
+
+}  // namespace
+
+namespace mdt {
+
+int wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_weights, hipStream_t s) {
+    if (int rc = plan_upload(p)) return rc;
+    const int n = p->w * p->h;
+    hipLaunchKernelGGL(k_wrap_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, s, p->w, p->h, p->tw, p->cols, p->d_xs, p->d_ys, p->d_colrange,
+                       p->d_rowrange, d_tile_w, d_weights);
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+// tiles [t_lo, t_hi) into the plan's batch buffers ptrs[0 .. nptrs) (holes are fine: only the batches of those tiles are touched)
+int wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi, hipStream_t s) {
+    MDT_CHECK_ARG(p && d_x_in && ptrs, "mdtile_gather: null argument");
+    MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_gather: bad N=%d C=%d", N, C);
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather: bad dtype %d", dtype);
+    MDT_CHECK_ARG(t_lo >= 0 && t_hi <= p->T && t_lo < t_hi && t_hi - t_lo <= 65535, "mdtile_gather: bad tile range [%d,%d) of %d", t_lo, t_hi, p->T);
+    MDT_CHECK_ARG(nptrs == p->num_batches, "mdtile_gather: %d batches given, the wrap-x plan has %d", nptrs, p->num_batches);
+    if (nptrs > MDTILE_MAX_BATCHES) {
+        set_error("mdtile_gather: %d batches > MDTILE_MAX_BATCHES=%d (a wrap-x plan has no packed form)", nptrs, MDTILE_MAX_BATCHES);
+        return MDTILE_E_LIMIT;
+    }
+    for (int t = t_lo; t < t_hi; ++t) MDT_CHECK_ARG(ptrs[t / p->tile_bs], "mdtile_gather: null batch pointer %d", t / p->tile_bs);
+    if (int rc = plan_upload(p)) return rc;
+    WrapGatherParams P;
+    memset(&P, 0, sizeof(P));
+    P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.tile_bs = p->tile_bs; P.N = N; P.C = C;
+    P.t_lo = t_lo; P.xs = p->d_xs; P.ys = p->d_ys; P.x_in = d_x_in;
+    for (int b = 0; b < nptrs; ++b) P.batch[b] = ptrs[b];
+    dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, t_hi - t_lo), block(256);
+    switch (dtype) {
+        case MDTILE_DT_F32: hipLaunchKernelGGL(k_wrap_gather<float>, grid, block, 0, s, P); break;
+        case MDTILE_DT_F16: hipLaunchKernelGGL(k_wrap_gather<__half>, grid, block, 0, s, P); break;
+        default: hipLaunchKernelGGL(k_wrap_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
+    }
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+int wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, hipStream_t s) {
+    MDT_CHECK_ARG(p && a, "mdtile_blend: null plan/args");
+    // what this form does not do, by name
+    MDT_CHECK_ARG(num_regions == 0, "mdtile_blend: a wrap-x plan takes no custom regions (%d given): wrap-around is not combined with regions", num_regions);
+    MDT_CHECK_ARG(a->flags == 0, "mdtile_blend: a wrap-x plan takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", a->flags);
+    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "mdtile_blend: a wrap-x plan takes no row band [%d,%d): wrap-around is not combined with the multi-GPU path",
+                  a->row_lo, a->row_hi);
+    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "mdtile_blend: bad N=%d C=%d", a->N, a->C);
+    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "mdtile_blend: bad method %d", a->method);
+    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "mdtile_blend: bad dtype %d", a->dtype);
+    MDT_CHECK_ARG(a->d_x_out, "mdtile_blend: null output");
+    MDT_CHECK_ARG(batch_out && num_batches == p->num_batches, "mdtile_blend: %d batches given, the wrap-x plan has %d", num_batches, p->num_batches);
+    if (num_batches > MDTILE_MAX_BATCHES) {
+        set_error("mdtile_blend: %d batches > MDTILE_MAX_BATCHES=%d (a wrap-x plan has no packed form: raise the tile batch size)", num_batches,
+                  MDTILE_MAX_BATCHES);
+        return MDTILE_E_LIMIT;
+    }
+    if (a->method == MDTILE_METHOD_MD) MDT_CHECK_ARG(a->d_weights, "mdtile_blend: MultiDiffusion needs d_weights");
+    else MDT_CHECK_ARG(a->d_tile_w && a->d_rescale, "mdtile_blend: Mixture of Diffusers needs d_tile_w and d_rescale");
+    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "mdtile_blend: null batch pointer %d", b);
+    if (int rc = plan_upload(p)) return rc;
+    WrapBlendParams P;
+    memset(&P, 0, sizeof(P));
+    P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
+    P.xs = p->d_xs; P.ys = p->d_ys; P.colquad = p->d_colquad; P.rowinfo = p->d_rowinfo;
+    P.weights = a->d_weights; P.tile_w = a->d_tile_w; P.rescale = a->d_rescale; P.out = a->d_x_out;
+    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
+    switch (a->dtype) {
+        case MDTILE_DT_F32: launch_wrap_blend_planes<float>(P, a->method, s); break;
+        case MDTILE_DT_F16: launch_wrap_blend_planes<__half>(P, a->method, s); break;
+        default: launch_wrap_blend_planes<__hip_bfloat16>(P, a->method, s); break;
+    }
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+}  // namespace mdt

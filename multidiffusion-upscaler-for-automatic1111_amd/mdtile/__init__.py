@@ -71,6 +71,8 @@ _SIGNATURES = {
     "mdtile_set_precision": (c_int, [c_int]),
     "mdtile_get_precision": (c_int, []),
     "mdtile_plan_create": (c_void_p, [c_int] * 7),
+    "mdtile_plan_create_wrap_x": (c_void_p, [c_int] * 6),
+    "mdtile_plan_wrap_x": (c_int, [c_void_p]),
     "mdtile_plan_destroy": (None, [c_void_p]),
     "mdtile_plan_info": (c_int, [c_void_p, _IP]),
     "mdtile_plan_bboxes": (c_int, [c_void_p, _IP]),
@@ -279,11 +281,19 @@ def dtype_code(dt: torch.dtype) -> int:
 
 # ---------------------------------------------------------------------------------------------------------------------
 class Plan:
-    """Grid plan == split_bboxes + init_grid_bbox (tile_utils/utils.py:160-177, abstractdiffusion.py:173-186)."""
+    """Grid plan == split_bboxes + init_grid_bbox (tile_utils/utils.py:160-177, abstractdiffusion.py:173-186).
+    wrap_x: the canvas is closed in x (panoramas, mdtile_plan_create_wrap_x): tile columns lie on a circle, a box's x + w may pass the canvas
+    width (its columns are taken mod w), clamp is always on.  A tile as wide as the canvas raises MdtileError."""
 
-    def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True):
+    def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True, wrap_x: bool = False):
         L = lib()
-        self._h = L.mdtile_plan_create(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(clamp))
+        self.wrap_x = bool(wrap_x)
+        if self.wrap_x:
+            if not clamp:
+                raise MdtileError("Plan(wrap_x=True) always clamps tile and overlap (clamp=False is not available)")
+            self._h = L.mdtile_plan_create_wrap_x(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs))
+        else:
+            self._h = L.mdtile_plan_create(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(clamp))
         if not self._h:
             raise MdtileError("mdtile_plan_create: " + L.mdtile_last_error().decode(errors="replace"))
         info = (c_int * 8)()

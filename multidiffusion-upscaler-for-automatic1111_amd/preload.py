@@ -16,3 +16,8 @@ def preload(parser):
         help="Tie the colours of every Tiled Diffusion img2img result to its (upscaled) init image, on the GPU: wavelet (the result's detail over "
              "the init image's low frequencies, five dilated 3x3 levels) or adain (per-channel mean and deviation of the init image). "
              "Default: not set, results are left as decoded.")
+    parser.add_argument(
+        "--mdtile-wrap-x", action="store_true",
+        help="Close the canvas horizontally (360-degree panoramas): Tiled Diffusion lays its tile columns on a circle, so that tiles span the seam "
+             "between the right and the left edge, and Tiled VAE pads its input with the columns of the other edge instead of zeros. Not combined "
+             "with region control. Default: off, the canvas is a strip with two ends.")

@@ -152,6 +152,12 @@ def _cmd_line_precision(net) -> Optional[int]:
     return resolve_precision(value, None if p is None else p.dtype)
 
 
+def _cmd_line_wrap_x() -> bool:
+    """--mdtile-wrap-x (preload.py): the canvas is closed in x; False on a host that never heard of the option."""
+    import modules.shared as shared
+    return bool(getattr(shared.cmd_opts, "mdtile_wrap_x", False))
+
+
 def _cmd_line_devices(net) -> Optional[List[int]]:
     """--mdtile-devices (preload.py) for the hooks of `net` (the VAE's decoder); None when the option is not set."""
     import modules.shared as shared
@@ -206,12 +212,26 @@ class VAEHook:
             if self.to_gpu:
                 self.net = self.net.to(devices.get_optimal_device())
             B, C, H, W = x.shape
-            if max(H, W) <= self.pad * 2 + self.tile_size:
-                print("[Tiled VAE]: the input size is tiny and unnecessary to tile.")
-                return self.net.original_forward(x)
-            return self.vae_tile_forward(x)
+            P = self.pad
+            if not (_cmd_line_wrap_x() and W > 2 * P):
+                return self._forward(x)
+            # the canvas closed in x: every conv would zero-pad at the left and right border; instead the input is padded by the tile pad
+            # with the columns of the OTHER edge and runs through the unchanged path; the padding's share of the result is cut off again.
+            # The columns next to the seam thus see their true neighbours up to P input px away -- the approximation every interior
+            # tile border already gets (upstream's pad of 11 latent / 32 image px).
+            out = self._forward(torch.cat([x[..., W - P:], x, x[..., :P]], dim=-1))
+            cut = 8 * P if self.is_decoder else P // 8
+            return out[..., cut:out.shape[-1] - cut].contiguous()
         finally:
             self.net = self.net.to(original_device)
+
+    def _forward(self, x):
+        """The body of upstream's __call__ (:375-388): untiled when the input is tiny, else the tiled sweep."""
+        B, C, H, W = x.shape
+        if max(H, W) <= self.pad * 2 + self.tile_size:
+            print("[Tiled VAE]: the input size is tiny and unnecessary to tile.")
+            return self.net.original_forward(x)
+        return self.vae_tile_forward(x)
 
     # ---- geometry (host ints via the C ABI) -------------------------------------------------------------------------
     def get_best_tile_size(self, lowerbound, upperbound):

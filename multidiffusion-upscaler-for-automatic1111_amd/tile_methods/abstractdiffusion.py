@@ -68,6 +68,10 @@ class AbstractDiffusion:
         self.plan: Optional[mdtile.Plan] = None
         self.tile_w = self.tile_h = self.tile_bs = self.num_tiles = self.num_batches = None
         self.batched_bboxes: List[List[BBox]] = []
+        # --mdtile-wrap-x: the canvas closed in x (init_grid_bbox); wrap_ext = columns by which the last tile column passes the right edge
+        self.wrap_x = False
+        self.wrap_ext = 0
+        self._wrap_copies: Dict[str, tuple] = {}
 
         # region prompt control
         self.enable_custom_bbox = False
@@ -116,6 +120,8 @@ class AbstractDiffusion:
         return None
 
     def init_done(self):
+        if self.enable_custom_bbox:
+            self._refuse_wrap_x_with("custom regions (region prompt control)")
         self.total_bboxes = 0
         if self.enable_grid_bbox:
             self.total_bboxes += self.num_batches
@@ -173,7 +179,7 @@ class AbstractDiffusion:
     def slice_icond(self, icond: Tensor, bbox: BBox) -> Tensor:
         """img2img image-conditioning follows the tile (it has the latent's spatial size); txt2img's dummy does not."""
         if tuple(icond.shape[2:]) == (self.h, self.w):
-            return icond[bbox.slicer]
+            return self.extended_x(icond, "icond")[bbox.slicer]      # custom regions never pass the edge; grid tiles of a wrap-x plan may
         return icond
 
     # ------------------------------------------------------------------------------------------------ grid
@@ -181,18 +187,58 @@ class AbstractDiffusion:
         """Per-tile weight: scalar 1.0 (MultiDiffusion) or a [tile_h, tile_w] map (Mixture of Diffusers)."""
         return 1.0
 
+    @staticmethod
+    def wrap_x_requested() -> bool:
+        """--mdtile-wrap-x (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_wrap_x", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
         # clamps (tile <= canvas; overlap <= min(requested tile) - 4), origins and batching all happen in the plan
-        self.plan = mdtile.Plan(self.w, self.h, tile_w, tile_h, overlap, tile_bs, clamp=True)
+        self.wrap_x = False
+        if self.wrap_x_requested():
+            if min(int(tile_w), self.w) >= self.w:
+                print(f"[Tiled Diffusion] --mdtile-wrap-x ignored: the tile ({tile_w} latent px) is as wide as the canvas ({self.w}), it would meet "
+                      "itself across the seam; the plain grid is used.")
+            else:
+                self.wrap_x = True
+        self.plan = mdtile.Plan(self.w, self.h, tile_w, tile_h, overlap, tile_bs, clamp=True, wrap_x=self.wrap_x)
+        # wrap-x: tiles that span the seam end at x + w > W; the Python slices below cut them from a copy of their source that repeats its
+        # first `wrap_ext` columns behind the last one (extended_x)
+        self.wrap_ext = max((b[0] + b[2] - self.w for b in self.plan.bboxes), default=0) if self.wrap_x else 0
+        self._wrap_copies = {}
+        if self.wrap_x:
+            if getattr(self.p, "extra_generation_params", None) is None:
+                self.p.extra_generation_params = {}
+            self.p.extra_generation_params["Tiled Diffusion wrap x"] = True
         self.tile_w, self.tile_h = self.plan.tile_w, self.plan.tile_h
         self.num_tiles, self.num_batches, self.tile_bs = self.plan.num_tiles, self.plan.num_batches, self.plan.tile_bs
         tile_weights = self.get_tile_weights()
         mdtile.weight_map_add_grid(self.plan, tile_weights if isinstance(tile_weights, Tensor) else None, self.weights)
         self.batched_bboxes = [[BBox(*b) for b in batch] for batch in self.plan.batches]
 
+    def extended_x(self, t: Tensor, slot: str, scale: int = 1) -> Tensor:
+        """wrap-x: cat(t, t[..., :E]) with E = scale * wrap_ext, so that the slice / rectangle of a tile that spans the seam is contiguous in
+        it (the columns past the right edge are the first ones again).  Built once per source tensor and kept under `slot` while the source
+        stays the same object with the same content version; any other plan returns t itself."""
+        E = self.wrap_ext * scale
+        if E <= 0:
+            return t
+        hit = self._wrap_copies.get(slot)
+        if hit is not None and hit[0] is t and hit[1] == t._version:
+            return hit[2]
+        ext = torch.cat([t, t[..., :E]], dim=-1).contiguous()
+        self._wrap_copies[slot] = (t, t._version, ext)
+        return ext
+
+    def _refuse_wrap_x_with(self, what: str):
+        if self.wrap_x:
+            raise RuntimeError(f"[Tiled Diffusion] --mdtile-wrap-x cannot be combined with {what}: the wrap-around blend has no "
+                               "region path. Turn one of them off.")
+
     # ------------------------------------------------------------------------------------------------ regions
     def init_custom_bbox(self, bbox_settings: Dict[int, BBoxSettings], draw_background: bool, causal_layers: bool):
+        self._refuse_wrap_x_with("custom regions (region prompt control)")
         self.enable_custom_bbox = True
         self.causal_layers = causal_layers
         self.draw_background = draw_background
@@ -378,8 +424,8 @@ class AbstractDiffusion:
         bboxes = self.batched_bboxes[batch_id]
         rects = [(b.x * opt_f, b.y * opt_f) for b in bboxes]
         w, h = bboxes[0].w * opt_f, bboxes[0].h * opt_f
-        for param, hint in zip(self.control_params, self.org_control_tensor_batch):
-            hint = self._hint_on_device(hint).contiguous()
+        for k, (param, hint) in enumerate(zip(self.control_params, self.org_control_tensor_batch)):
+            hint = self._hint_on_device(self.extended_x(hint, f"hint{k}", opt_f)).contiguous()
             if self.is_kdiff:      # every tile's x_batch_size copies are consecutive (tile-major model batch)
                 param.hint_cond = mdtile.gather_rects(hint[:1], rects[:tile_batch_size], w, h, repeat=x_batch_size, tile_major=True)
             else:                  # DDIM: the tile stack as a whole, repeated for cond + uncond (once when only denoising)
@@ -418,7 +464,7 @@ class AbstractDiffusion:
         if not self._stablesr_live():
             return
         bboxes = self.batched_bboxes[batch_id]
-        t = self.stablesr_tensor.contiguous()
+        t = self.extended_x(self.stablesr_tensor, "stablesr").contiguous()
         self.stablesr_script.stablesr_model.latent_image = mdtile.gather_rects(t, [(b.x, b.y) for b in bboxes], bboxes[0].w, bboxes[0].h)
 
     def set_custom_stablesr_tensors(self, bbox_id: int):

@@ -29,7 +29,7 @@
 // cold 8K evaluation for k_blend alone (profiles/r6c).
 #include <type_traits>
 
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 

@@ -31,12 +31,6 @@ bool attn_strict_f32();   // ... / MDTILE_ATTN_MODE=f32: attention on the exact-
 bool mfma_single_term();  // mdtile_set_precision(MDTILE_PRECISION_BF16): one bf16 MFMA (w_hi x x_hi) per product where no strict bit applies
 bool mode_f16();          // mdtile_set_precision(MDTILE_PRECISION_F16): fp16 MFMAs behind a norm, three terms on the raw stream, attention as in MDTILE_PRECISION_BF16
 int plan_upload(const struct ::mdtile_plan* plan);  // mirror the plan's lookup tables to the current device (idempotent)
-// wrap-x plans (mdtile_plan_create_wrap_x): the public entry points hand such a plan to these launchers (wrap.hip)
-int wrap_weight_map(const struct ::mdtile_plan* plan, const float* d_tile_w, float* d_weights, hipStream_t s);
-int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi,
-                hipStream_t s);
-int wrap_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
-               int num_regions, hipStream_t s);
 
 #define MDT_CHECK_ARG(cond, ...)           \
     do {                                   \

@@ -2,7 +2,7 @@
 // 4-wave blocks per CU): kernel parameters, the inline-asm LDS-DMA, the split, the shared epilogue and the LDS input stage.
 // See vae_conv_rec.hip for the record-image format and the upstream call sites (scripts/tilevae.py:115-195, 218-245, 614-616).
 #pragma once
-#include "common.h"
+#include "launchers.h"
 #include "f16_convert.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -45,6 +45,17 @@ struct ConvRParams {
     int dbg;                  // probing (MDTILE_REC_DBG): bit 0 = skip the epilogue (K loop only: nothing is written); bit 3 = block 0 of the
                               // one-block kernel writes s_memtime stamps per wave and item to `census` (probes/conv_item_timeline.py)
 };
+
+using RecKernel = void (*)(ConvRParams);      // every record conv kernel
+
+// The launchers conv_rec_launch (vae_conv_rec.hip) hands its filled ConvRParams to (launchers.h declares everything else):
+// vae_conv_rec2.hip: the two-blocks-per-CU form of the cout % 128 == 0 kernels; `one`: the one-term kernels (bf16 or, with x16, fp16)
+int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, bool one, int x16, int y16);
+// probes/csrc/vae_conv_recd.hip (PROBES twin of the library only -- a measured, rejected form: DESIGN.md / docs/history/r5.md): 64-cout items with
+// the epilogue dripped into the next item's K loop (direct 3x3, cin % 32 == 0, cin >= 128).  Declared here, defined only in that build: the one
+// call sits in a discarded `if constexpr (kProbes)` statement, so the shipping library neither references nor carries the kernel.
+bool conv_recd_supported(int cout, int cin);
+int conv_recd_launch(ConvRParams P, int B, hipStream_t s, int cus);
 
 }  // namespace mdt
 

@@ -1,0 +1,82 @@
+// Every function of libmdtile that one .hip file defines and another calls, grouped by the file that defines it.  Default arguments are
+// written here and nowhere else.  The defining files include this header and define these functions by their qualified names
+// (`int mdt::conv_rec_launch(...)`), which only compiles against a matching declaration: a signature that drifts is a compile error.
+// (conv_rec2_launch and the probes-only conv_recd_* take the kernels' ConvRParams: conv_rec_common.h declares them next to it.)
+#pragma once
+#include "common.h"
+
+namespace mdt {
+
+// ---- wrap.hip: wrap-x plans (mdtile_plan_create_wrap_x); the public entry points hand such a plan to these launchers
+int wrap_weight_map(const struct ::mdtile_plan* plan, const float* d_tile_w, float* d_weights, hipStream_t s);
+int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi,
+                hipStream_t s);
+int wrap_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+               int num_regions, hipStream_t s);
+
+// ---- vae_conv_bf16x3.hip
+bool conv_bf16x3_eligible(int cout, int cin, int ksize);
+size_t conv_bf16x3_direct_records(int cout, int cin);
+size_t conv_bf16x3_packed_floats(int cout, int cin);
+int conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
+bool conv_rec_narrow_eligible(int cout, int cin, int ksize);
+size_t conv_rec_narrow_packed_floats(int cin);
+int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
+size_t conv_f16_plane_floats(int cout, int cin);
+int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s);
+bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up);
+bool conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up);
+size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W);
+int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
+                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part = nullptr, int w16 = 0);
+int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
+                             hipStream_t s);
+
+// ---- vae_conv1x1_bf16x3.hip
+bool conv1x1_bf16x3_eligible(int cout, int cin);
+size_t conv1x1_bf16x3_packed_floats(int cout, int cin);
+int conv1x1_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
+int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
+                          int cout, size_t HW, hipStream_t s, bool attn_proj = false);
+
+// ---- vae_norm.hip
+int conv_stats_finish_launch(const double* d_cpart, int B, int cout, size_t HW, int units, int NCB, int QB, int groups, float* d_mean, float* d_var,
+                             void* d_gnws, hipStream_t s);
+
+// ---- vae_conv_rec.hip
+bool conv_rec_supported(int cout, int cin, int ksize);
+size_t rec_image_bytes(int B, int C, int H, int W);
+size_t rec_plane_records(int H, int W);
+int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
+int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
+// One record conv as a C entry point (vae_conv.hip) hands it to conv_rec_launch.  Host side only: the kernels take ConvRParams.
+struct RecConvCall {
+    const void* x_rec = nullptr;     // input record image
+    const void* w_rec = nullptr;     // split-bf16 record image of the weights (direct records, then the sub-pixel ones); x16: the fp16 plane
+    const float* bias = nullptr;
+    const float* res = nullptr;      // fp32 residual or null
+    float* y32 = nullptr;            // fp32 output or null
+    void* y_rec = nullptr;           // record output or null
+    const float* y_coef = nullptr;   // activation of the record output, (a, s) per image and channel, or null
+    int B = 0, cin = 0, cout = 0, H = 0, W = 0;      // H, W: OUTPUT size
+    int up = 0;                      // nearest-2x in front of the conv (sub-pixel kernels)
+    // win (sub-pixel upsample kernel only, else null): {HinF, WinF, y0[0], x0[0], ..., y0[7], x0[7]} -- x_rec is the record image of
+    // [B, cin, HinF, WinF] and image b's conv reads its window [y0[b & 7] : .. + H/2, x0[b & 7] : .. + W/2]  (all 8 slots filled)
+    const int* win = nullptr;
+    int family = 0;                  // 0 = chosen per launch, 1 / 2 = one / two blocks per CU, 3 = the dripped-epilogue kernel (PROBES twin only)
+    double* d_part = nullptr;        // statistics of the output from the epilogue: the per-wave partials (one-block family only)
+    // x16 (MDTILE_PRECISION_F16): x_rec is an activated record image in its fp16 form and w_rec the fp16 weight plane -> the fp16 kernels;
+    // y16: the (activated) record output is written in the fp16 form.  The C entry points have checked both against the mode.
+    int x16 = 0, y16 = 0;
+};
+int conv_rec_launch(const RecConvCall& c, hipStream_t s);
+bool conv_rec_stats_in_epilogue(int B, int cout, int H, int W, int up);
+int conv_rec_stats_units(int H, int W, int up);
+
+// ---- vae_attn_bf16x3.hip
+bool attn_bf16x3_eligible(int C);
+size_t attn_bf16x3_ws_bytes(int B, int C, int Tq, int Tk);
+int attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok, float* d_out, int B, int C, int Tq, int Tk, float scale,
+                       void* d_ws, hipStream_t s, bool v_channel_major = false);
+
+}  // namespace mdt

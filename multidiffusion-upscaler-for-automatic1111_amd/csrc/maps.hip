@@ -1,6 +1,6 @@
 // Init-time weight maps (K8-K10).  Tiny, launch-latency-bound kernels; written for exact parity, not speed.
 // Upstream: tile_utils/utils.py:160-214, tile_methods/multidiffusion.py:44-46, tile_methods/mixtureofdiffusers.py:29-55.
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 

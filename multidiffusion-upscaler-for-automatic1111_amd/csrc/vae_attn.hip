@@ -16,7 +16,7 @@
 //       result rows are channels / columns are tokens = coalesced 128-B stores into [B, C, T].
 // Work split: 4 waves; for the scores each wave owns one 32x32 tile of the 64x64 block; for the output each wave owns
 // C/4 channels x 64 queries (C = 512: 8 accumulator tiles = 128 AGPRs).
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 
@@ -205,16 +205,6 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ q, const
 
 }  // namespace
 
-// vae_attn_bf16x3.hip
-namespace mdt {
-bool attn_bf16x3_eligible(int C);
-size_t attn_bf16x3_ws_bytes(int B, int C, int Tq, int Tk);
-int attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok, float* d_out, int B, int C, int Tq, int Tk, float scale,
-                       void* d_ws, hipStream_t s, bool v_channel_major = false);
-}  // namespace mdt
-
-static bool attn_force_f32() { return attn_strict_f32(); }
-
 // the flash formulation keeps every intermediate on chip; the split-bf16 path needs room for the fragment-order
 // bf16 hi/lo images of q, k and v
 extern "C" size_t mdtile_vae_attn_ws_size(int B, int C, int T) {
@@ -224,7 +214,7 @@ extern "C" size_t mdtile_vae_attn_ws_size(int B, int C, int T) {
 
 // one predicate for the dispatch below AND for the host's choice of the v layout (round 3's host-side test looked at mdtile_get_precision,
 // which reports F32 only when conv AND attention are forced: MDTILE_ATTN_MODE=f32 alone sent a channel-major v to the exact kernel)
-static bool attn_takes_bf16x3(int C, int flags) { return !(flags & MDTILE_ATTN_EXACT_F32) && !attn_force_f32() && attn_bf16x3_eligible(C); }
+static bool attn_takes_bf16x3(int C, int flags) { return !(flags & MDTILE_ATTN_EXACT_F32) && !attn_strict_f32() && attn_bf16x3_eligible(C); }
 
 extern "C" int mdtile_vae_attn_takes_channel_major(int C, int flags) { return attn_takes_bf16x3(C, flags) ? 1 : 0; }
 

@@ -23,7 +23,7 @@
 //                the 128 x C output block lives in registers (8 waves x 8 accumulator tiles for C = 512); the V^T fragments
 //                of a wave are its own (nobody shares them) and come straight from global memory
 //   LDS: two 64 KB slab stages (K + Q slabs by DMA; the P records of a key block overlay the stage that is free) + statistics.
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 
@@ -187,9 +187,7 @@ __global__ __launch_bounds__(256) void k_attn_combine(const float* __restrict__ 
 
 }  // namespace
 
-namespace mdt {
-
-bool attn_bf16x3_eligible(int C) { return C == 128 || C == 256 || C == 512; }
+bool mdt::attn_bf16x3_eligible(int C) { return C == 128 || C == 256 || C == 512; }
 
 // Key-range split factor: 1 block per CU (133 KB LDS), so the launch runs in ceil(blocks / CUs) rounds; pick the smallest
 // nsplit <= 4 whose round occupancy is within 3 % of the best.  MDTILE_ATTN_SPLIT=n forces it.
@@ -230,7 +228,7 @@ static int attn_nsplit(int B, int Tq, int Tk) {
 
 // workspace: Qrec (B * Tq128 * C * 4 bytes: hi + lo bf16 per element), Krec, Vrec (B * Tk128 * C * 4 bytes each)
 // [+ nsplit un-normalised parts B*C*Tq fp32 and their (max, sum) rows 2*B*Tq128 fp32 when the key range is split]
-size_t attn_bf16x3_ws_bytes(int B, int C, int Tq, int Tk) {
+size_t mdt::attn_bf16x3_ws_bytes(int B, int C, int Tq, int Tk) {
     const size_t Tq128 = ((size_t)Tq + 127) / 128 * 128, Tk128 = ((size_t)Tk + 127) / 128 * 128;
     const int ns = attn_nsplit(B, Tq, Tk);
     size_t bytes = (size_t)B * (Tq128 + 2 * Tk128) * C * 4;
@@ -238,7 +236,7 @@ size_t attn_bf16x3_ws_bytes(int B, int C, int Tq, int Tk) {
     return bytes;
 }
 
-int attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok, float* d_out, int B, int C, int Tq, int Tk, float scale,
+int mdt::attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok, float* d_out, int B, int C, int Tq, int Tk, float scale,
                        void* d_ws, hipStream_t s, bool v_channel_major) {
     const int Tq128 = (Tq + 127) / 128 * 128, Tk128 = (Tk + 127) / 128 * 128;
     const size_t perq = (size_t)B * Tq128 * C * 4 / 16, perk = (size_t)B * Tk128 * C * 4 / 16;   // records per operand
@@ -281,5 +279,3 @@ int attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v_tok,
     }
     return MDTILE_OK;
 }
-
-}  // namespace mdt

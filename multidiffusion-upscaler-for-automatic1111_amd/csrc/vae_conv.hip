@@ -14,7 +14,7 @@
 //     written to the other LDS buffer after them: one barrier per slab.
 //   * nearest-2x upsample and the residual add are fused (source index >> 1 while staging; epilogue add).
 //   * XCD-aware block order: the BN-blocks of one pixel tile sit on the same XCD (same L2) back to back.
-#include "common.h"
+#include "launchers.h"
 #include <algorithm>
 
 using namespace mdt;
@@ -325,45 +325,6 @@ int launch_conv_down2(ConvParams& P, hipStream_t s) {
 
 }  // namespace
 
-// vae_conv_bf16x3.hip
-namespace mdt {
-bool conv_bf16x3_eligible(int cout, int cin, int ksize);
-size_t conv_bf16x3_packed_floats(int cout, int cin);
-int conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
-bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up);
-int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
-                             hipStream_t s);
-int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part = nullptr, int w16 = 0);
-size_t conv_f16_plane_floats(int cout, int cin);
-int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s);
-bool conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up);
-size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W);
-// vae_norm.hip
-int conv_stats_finish_launch(const double* d_cpart, int B, int cout, size_t HW, int units, int NCB, int QB, int groups, float* d_mean, float* d_var,
-                             void* d_gnws, hipStream_t s);
-bool conv_rec_narrow_eligible(int cout, int cin, int ksize);
-size_t conv_rec_narrow_packed_floats(int cin);
-int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
-// vae_conv_rec.hip
-bool conv_rec_supported(int cout, int cin, int ksize);
-size_t rec_image_bytes(int B, int C, int H, int W);
-size_t rec_plane_records(int H, int W);
-int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
-int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16 = 0);
-int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y32, void* d_yrec,
-                    const float* d_ycoef, int B, int cin, int cout, int H, int W, int up, hipStream_t s, const int* win = nullptr, int family = 0,
-                    double* d_part = nullptr, int x16 = 0, int y16 = 0);
-bool conv_rec_stats_in_epilogue(int B, int cin, int cout, int H, int W, int up);
-int conv_rec_stats_units(int H, int W, int up);
-// vae_conv1x1_bf16x3.hip
-bool conv1x1_bf16x3_eligible(int cout, int cin);
-size_t conv1x1_bf16x3_packed_floats(int cout, int cin);
-int conv1x1_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s);
-int conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                          int cout, size_t HW, hipStream_t s, bool attn_proj = false);
-}  // namespace mdt
-
 // packed buffer = [ fp32 image (tap, cin, coutP) | split-bf16 record image (only for shapes the bf16x3 kernels take) ]
 static size_t f32_packed_floats(int cout, int cin, int ksize) { return ((size_t)ksize * ksize * cin * round_up(cout, 32) + 3) & ~(size_t)3; }
 
@@ -461,10 +422,8 @@ extern "C" int mdtile_conv2d(const float* d_x, const float* d_w_packed, const fl
     return launch_conv<1, 16, 4, 1, 2, 1>(P, out_layout, s);
 }
 
-static bool conv_force_f32() { return conv_strict_f32(); }
-
 extern "C" int mdtile_conv2d_gn_supported(int cout, int cin, int ksize, int flags, int out_layout) {
-    if (conv_force_f32() || (flags & MDTILE_CONV_EXACT_F32) || out_layout != 0) return 0;
+    if (conv_strict_f32() || (flags & MDTILE_CONV_EXACT_F32) || out_layout != 0) return 0;
     return conv_bf16x3_gn_supported(cout, cin, ksize, (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0) ? 1 : 0;
 }
 
@@ -573,42 +532,47 @@ extern "C" int mdtile_rec_to_f32_fmt(const void* d_rec, float* d_x, int B, int C
     return rec_to_f32_launch(d_rec, d_x, B, C, H, W, as_stream(stream), fmt == MDTILE_REC_F16);
 }
 
-// MDTILE_CONV_REC_X_F16 / _Y_F16 of a record conv call against the mode: x16 needs the mode (its kernels exist for nothing else) and a direct conv;
-// y16 must be set exactly when the call writes an activated record in MDTILE_PRECISION_F16
-static int rec_formats_ok(const char* who, int flags, int up, const void* d_y_rec, const void* d_y_coef) {
-    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0, y16 = (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0;
+extern "C" int mdtile_conv2d_rec_supported(int cout, int cin, int ksize, int flags) {
+    if (conv_strict_f32() || (flags & MDTILE_CONV_EXACT_F32)) return 0;
+    return conv_rec_supported(cout, cin, ksize) ? 1 : 0;
+}
+
+// MDTILE_CONV_REC_ONE_BLOCK / _TWO_BLOCKS: the caller names the kernel family (tests, probes); 0 = chosen per launch (vae_conv_rec.hip: rec_route)
+// (bit 16 names the dripped-epilogue probe kernel, in the PROBES twin of the library only: probes/csrc/vae_conv_recd.hip)
+static int rec_family(int flags) { return (flags & MDTILE_CONV_REC_ONE_BLOCK) ? 1 : (flags & MDTILE_CONV_REC_TWO_BLOCKS) ? 2 : (kProbes && (flags & 16)) ? 3 : 0; }
+
+// The call of conv_rec_launch from what the three record entry points are given: flags, pointers, OUTPUT shape.  Checks the shape and the record
+// formats (`who` names the entry point in the error texts) and picks the weight image.
+// MDTILE_CONV_REC_X_F16 / _Y_F16 against the mode: x16 needs the mode (its kernels exist for nothing else) and a direct conv; y16 must be set
+// exactly when the call writes an activated record in MDTILE_PRECISION_F16
+static int rec_call(RecConvCall& c, const char* who, int flags, const void* d_x_rec, const float* d_w_packed, const float* d_bias, const float* d_residual,
+                    float* d_y, void* d_y_rec, const float* d_y_coef, int B, int cin, int cout, int H, int W) {
+    const int up = (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0, x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0, y16 = (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0;
+    MDT_CHECK_ARG(!up || (H % 2 == 0 && W % 2 == 0), "%s: upsample2x needs even output size, got %dx%d", who, H, W);
+    MDT_CHECK_ARG(rec_image_ok(B, cin, up ? H / 2 : H, up ? W / 2 : W) && (cout % 32 != 0 || rec_image_ok(B, cout, H, W)),
+                  "%s: unsupported shape B=%d cin=%d cout=%d H=%d W=%d", who, B, cin, cout, H, W);
     MDT_CHECK_ARG(!x16 || (mode_f16() && !up), "%s: record format mismatch: MDTILE_CONV_REC_X_F16 (fp16 input record, fp16 weight plane) needs MDTILE_PRECISION_F16 and a "
                   "direct conv (mode %d, upsample %d)", who, mdtile_get_precision(), up);
     const int want = (d_y_rec && rec_writes_f16(d_y_coef)) ? 1 : 0;
     MDT_CHECK_ARG(y16 == want, "%s: record format mismatch: the call %s MDTILE_CONV_REC_Y_F16 but its record output is %s (mode %d, d_y_coef %s)", who,
                   y16 ? "sets" : "does not set", want ? "the fp16 form" : "a bf16 split or absent", mdtile_get_precision(), d_y_coef ? "given" : "NULL");
+    c.x_rec = d_x_rec; c.bias = d_bias; c.res = d_residual; c.y32 = d_y; c.y_rec = d_y_rec; c.y_coef = d_y_coef;
+    c.w_rec = x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3);      // (x16: d_w_packed IS the fp16 plane)
+    c.B = B; c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.up = up;
+    c.family = rec_family(flags); c.x16 = x16; c.y16 = y16;
     return MDTILE_OK;
 }
-
-extern "C" int mdtile_conv2d_rec_supported(int cout, int cin, int ksize, int flags) {
-    if (conv_force_f32() || (flags & MDTILE_CONV_EXACT_F32)) return 0;
-    return conv_rec_supported(cout, cin, ksize) ? 1 : 0;
-}
-
-// MDTILE_CONV_REC_ONE_BLOCK / _TWO_BLOCKS: the caller names the kernel family (tests, probes); 0 = chosen per launch (rec_two_blocks)
-// (bit 16 names the dripped-epilogue probe kernel, in the PROBES twin of the library only: probes/csrc/vae_conv_recd.hip)
-static int rec_family(int flags) { return (flags & MDTILE_CONV_REC_ONE_BLOCK) ? 1 : (flags & MDTILE_CONV_REC_TWO_BLOCKS) ? 2 : (kProbes && (flags & 16)) ? 3 : 0; }
 
 extern "C" int mdtile_conv2d_rec(const void* d_x_rec, const float* d_w_packed, const float* d_bias, const float* d_residual, float* d_y,
                                  void* d_y_rec, const float* d_y_coef, int B, int cin, int cout, int H, int W, int flags,
                                  mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x_rec && d_w_packed && (d_y || d_y_rec), "mdtile_conv2d_rec: null argument (one of d_y / d_y_rec is required)");
     MDT_CHECK_ARG(mdtile_conv2d_rec_supported(cout, cin, 3, flags), "mdtile_conv2d_rec: no record kernel for cout=%d cin=%d flags=%d", cout, cin, flags);
-    const int up = (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0;
-    MDT_CHECK_ARG(!up || (H % 2 == 0 && W % 2 == 0), "mdtile_conv2d_rec: upsample2x needs even output size, got %dx%d", H, W);
-    MDT_CHECK_ARG(rec_image_ok(B, cin, up ? H / 2 : H, up ? W / 2 : W) && (cout % 32 != 0 || rec_image_ok(B, cout, H, W)),
-                  "mdtile_conv2d_rec: unsupported shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
-    MDT_CHECK_ARG(cout % 128 == 0 || (!up && !d_y_rec && !d_residual),
+    MDT_CHECK_ARG(cout % 128 == 0 || (!(flags & MDTILE_CONV_UPSAMPLE2X) && !d_y_rec && !d_residual),
                   "mdtile_conv2d_rec: the narrow (cout < 32) kernel writes fp32 only, no residual, no upsample (cout=%d)", cout);
-    if (const int rc = rec_formats_ok("mdtile_conv2d_rec", flags, up, d_y_rec, d_y_coef)) return rc;
-    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0;      // (then d_w_packed IS the fp16 plane)
-    return conv_rec_launch(d_x_rec, x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, d_residual, d_y, d_y_rec, d_y_coef, B, cin, cout,
-                           H, W, up, as_stream(stream), nullptr, rec_family(flags), nullptr, x16, (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0);
+    RecConvCall c;
+    if (const int rc = rec_call(c, "mdtile_conv2d_rec", flags, d_x_rec, d_w_packed, d_bias, d_residual, d_y, d_y_rec, d_y_coef, B, cin, cout, H, W)) return rc;
+    return conv_rec_launch(c, as_stream(stream));
 }
 
 extern "C" int mdtile_conv2d_rec_stats_supported(int cout, int cin, int ksize, int flags, int groups) {
@@ -621,24 +585,20 @@ extern "C" int mdtile_conv2d_rec_stats(const void* d_x_rec, const float* d_w_pac
     MDT_CHECK_ARG(d_x_rec && d_w_packed && d_y && d_mean && d_var && d_ws, "mdtile_conv2d_rec_stats: null argument");
     MDT_CHECK_ARG(mdtile_conv2d_rec_stats_supported(cout, cin, 3, flags, groups),
                   "mdtile_conv2d_rec_stats: no statistics kernel for cout=%d cin=%d flags=%d groups=%d", cout, cin, flags, groups);
-    const int up = (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0;
-    MDT_CHECK_ARG(!up || (H % 2 == 0 && W % 2 == 0), "mdtile_conv2d_rec_stats: upsample2x needs even output size, got %dx%d", H, W);
-    MDT_CHECK_ARG(rec_image_ok(B, cin, up ? H / 2 : H, up ? W / 2 : W) && rec_image_ok(B, cout, H, W),
-                  "mdtile_conv2d_rec_stats: unsupported shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
+    RecConvCall c;
+    if (const int rc = rec_call(c, "mdtile_conv2d_rec_stats", flags, d_x_rec, d_w_packed, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W)) return rc;
     hipStream_t s = as_stream(stream);
-    if (const int rc = rec_formats_ok("mdtile_conv2d_rec_stats", flags, up, nullptr, nullptr)) return rc;
-    const int x16 = (flags & MDTILE_CONV_REC_X_F16) ? 1 : 0;
-    const float* w = x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3);
-    if (rec_family(flags) == 0 && !conv_rec_stats_in_epilogue(B, cin, cout, H, W, up)) {
+    if (c.family == 0 && !conv_rec_stats_in_epilogue(B, cout, H, W, c.up)) {
         // a launch of a few item rounds: the two-blocks-per-CU family gains more than the statistics pass costs (conv_rec_stats_in_epilogue)
-        const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s, nullptr, 0, nullptr, x16, 0);
+        const int rc = conv_rec_launch(c, s);
         return rc != MDTILE_OK ? rc : mdtile_gn_stats(d_y, B, cout, H * W, groups, d_mean, d_var, d_ws, stream);
     }
-    MDT_CHECK_ARG(rec_family(flags) <= 1, "mdtile_conv2d_rec_stats: only the one-block-per-CU family leaves statistics (flags=%d)", flags);
-    double* d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
-    const int rc = conv_rec_launch(d_x_rec, w, d_bias, d_residual, d_y, nullptr, nullptr, B, cin, cout, H, W, up, s, nullptr, 1, d_part, x16, 0);
+    MDT_CHECK_ARG(c.family <= 1, "mdtile_conv2d_rec_stats: only the one-block-per-CU family leaves statistics (flags=%d)", flags);
+    c.family = 1;
+    c.d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
+    const int rc = conv_rec_launch(c, s);
     if (rc != MDTILE_OK) return rc;
-    return conv_stats_finish_launch(d_part, B, cout, (size_t)H * W, conv_rec_stats_units(H, W, up), cout / 128, 32, groups, d_mean, d_var, d_ws, s);
+    return conv_stats_finish_launch(c.d_part, B, cout, (size_t)H * W, conv_rec_stats_units(H, W, c.up), cout / 128, 32, groups, d_mean, d_var, d_ws, s);
 }
 
 // Nearest-2x + 3x3 conv of a WINDOW of the input record image (live-window narrowing of the decoder tiles, see include/mdtile.h)
@@ -662,9 +622,11 @@ extern "C" int mdtile_upconv2d_rec_window(const void* d_x_rec, const float* d_w_
     }
     MDT_CHECK_ARG(rec_image_ok(B, cin, Hin, Win) && rec_image_ok(B, cout, 2 * h, 2 * w),
                   "mdtile_upconv2d_rec_window: unsupported shape B=%d cin=%d cout=%d Hin=%d Win=%d", B, cin, cout, Hin, Win);
-    if (const int rc = rec_formats_ok("mdtile_upconv2d_rec_window", flags, 1, d_y_rec, d_y_coef)) return rc;
-    return conv_rec_launch(d_x_rec, d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, nullptr, d_y, d_y_rec, d_y_coef, B, cin, cout,
-                           2 * h, 2 * w, 1, as_stream(stream), win, rec_family(flags), nullptr, 0, (flags & MDTILE_CONV_REC_Y_F16) ? 1 : 0);
+    RecConvCall c;      // (the conv of the window: output 2h x 2w; its checks above cover the whole input image)
+    if (const int rc = rec_call(c, "mdtile_upconv2d_rec_window", flags | MDTILE_CONV_UPSAMPLE2X, d_x_rec, d_w_packed, d_bias, nullptr, d_y, d_y_rec, d_y_coef, B, cin,
+                                cout, 2 * h, 2 * w)) return rc;
+    c.win = win;
+    return conv_rec_launch(c, as_stream(stream));
 }
 
 // ldm Downsample: y = conv3x3_stride2(pad(x, right 1, bottom 1)); output (Hin - 2) / 2 + 1 rows (likewise columns).

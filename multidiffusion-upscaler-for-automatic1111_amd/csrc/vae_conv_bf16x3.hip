@@ -21,7 +21,7 @@
 // K loop = phases (16-channel K-step, dy): 3 taps x (2 x NROW) tiles x 3 MFMAs per wave and phase, ONE barrier per phase;
 // the next phase's weights (24 KB, L2-resident) and the next K-step's input slab are fetched into registers at the start
 // of a phase and written to the other LDS stage at its end (fp32 -> hi/lo split happens on that write).
-#include "common.h"
+#include "launchers.h"
 #include "f16_convert.h"
 
 using namespace mdt;
@@ -229,17 +229,15 @@ inline int round_up_i(int v, int m) { return (v + m - 1) / m * m; }
 
 }  // namespace
 
-namespace mdt {
-
 // shapes the split-bf16 3x3 kernel takes; everything else stays on the exact-fp32 kernel
-bool conv_bf16x3_eligible(int cout, int cin, int ksize) { return ksize == 3 && cin % 16 == 0 && cout >= 32; }
+bool mdt::conv_bf16x3_eligible(int cout, int cin, int ksize) { return ksize == 3 && cin % 16 == 0 && cout >= 32; }
 // cout tiles per block: 128-cout blocks for the wide convs, 64-cout blocks for the small decoders' narrow ones
 static int conv_bf16x3_mt(int cout) { return cout <= 64 ? 2 : 4; }
 // K-step channel order (kstep_c0 / kstep_cj): the accumulator-lane order whenever whole 32-channel groups exist
 static int conv_bf16x3_perm(int cin) { return cin % 32 == 0 ? 1 : 0; }
 
 // record image = [ direct 3x3 records (9 taps) | sub-pixel upsample records (4 parities x 4 merged taps) ]
-size_t conv_bf16x3_direct_records(int cout, int cin) {
+size_t mdt::conv_bf16x3_direct_records(int cout, int cin) {
     const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
     return (size_t)NCB * NK * 3 * 2 * 3 * MT * 64;
 }
@@ -247,11 +245,11 @@ static size_t upconv_records(int cout, int cin) {
     const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
     return (size_t)2 * NCB * NK * 2 * 2 * 2 * 2 * MT * 64;
 }
-size_t conv_bf16x3_packed_floats(int cout, int cin) {   // size of the record array in floats (4 per 16-byte record)
+size_t mdt::conv_bf16x3_packed_floats(int cout, int cin) {   // size of the record array in floats (4 per 16-byte record)
     return (conv_bf16x3_direct_records(cout, cin) + upconv_records(cout, cin)) * 4;
 }
 
-int conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
+int mdt::conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
     const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16, perm = conv_bf16x3_perm(cin);
     const size_t n = conv_bf16x3_direct_records(cout, cin);
     hipLaunchKernelGGL(k_conv_pack_bf16x3, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_oihw, (u32x4*)d_out, cout, cin, MT, NCB, NK, perm);
@@ -264,9 +262,9 @@ int conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipS
 
 // narrow convs (cout < 32: conv_out) only exist as a record-image kernel (vae_conv_rec.hip, one 32-cout tile per block): their
 // packed image is the direct 3x3 records with MT = 1, NCB = 1, permuted K order
-bool conv_rec_narrow_eligible(int cout, int cin, int ksize) { return ksize == 3 && cin % 32 == 0 && cout >= 1 && cout < 32; }
-size_t conv_rec_narrow_packed_floats(int cin) { return (size_t)(cin / 16) * 3 * 2 * 3 * 1 * 64 * 4; }
-int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
+bool mdt::conv_rec_narrow_eligible(int cout, int cin, int ksize) { return ksize == 3 && cin % 32 == 0 && cout >= 1 && cout < 32; }
+size_t mdt::conv_rec_narrow_packed_floats(int cin) { return (size_t)(cin / 16) * 3 * 2 * 3 * 1 * 64 * 4; }
+int mdt::conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
     const int NK = cin / 16;
     const size_t n = (size_t)NK * 3 * 2 * 3 * 64;
     hipLaunchKernelGGL(k_conv_pack_bf16x3, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_oihw, (u32x4*)d_out, cout, cin, 1, 1, NK, 1);
@@ -275,11 +273,11 @@ int conv_rec_narrow_pack(const float* d_w_oihw, void* d_out, int cout, int cin, 
 }
 
 // fp16 weight plane of a 3x3 conv the record / hand-over kernels take: the size and geometry of the direct records of the split image
-size_t conv_f16_plane_floats(int cout, int cin) {
+size_t mdt::conv_f16_plane_floats(int cout, int cin) {
     if (conv_rec_narrow_eligible(cout, cin, 3)) return conv_rec_narrow_packed_floats(cin);
     return conv_bf16x3_eligible(cout, cin, 3) ? conv_bf16x3_direct_records(cout, cin) * 4 : 0;
 }
-int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s) {
+int mdt::conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s) {
     const bool narrow = conv_rec_narrow_eligible(cout, cin, 3);
     const int MT = narrow ? 1 : conv_bf16x3_mt(cout), NCB = narrow ? 1 : round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
     const int perm = narrow ? 1 : conv_bf16x3_perm(cin);
@@ -290,20 +288,20 @@ int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipSt
     return MDTILE_OK;
 }
 
-bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up) {
+bool mdt::conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up) {
     return conv_bf16x3_eligible(cout, cin, ksize) && !up && cin <= MAX_GN_CIN;
 }
 
 // statistics in the epilogue (k_conv3x3_bf16x3<4, true, 1, true>): 128-cout blocks with the fused pre-activation, whole blocks of couts
-bool conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up) {
+bool mdt::conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up) {
     return conv_bf16x3_gn_supported(cout, cin, ksize, up) && conv_bf16x3_mt(cout) == 4 && cout % 128 == 0;
 }
 // doubles of the per-block partials: [B][ptiles][NCB][32 quads][2]
-size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W) {
+size_t mdt::conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W) {
     return (size_t)B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * (cout / 128) * 64;
 }
 
-int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
+int mdt::conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
                        int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part, int w16) {
     // w16 (MDTILE_PRECISION_F16, fused pre-activation only): d_w_rec is the fp16 weight plane -> k_conv3x3_f16
     MDT_CHECK_ARG(!w16 || (d_coef && !up), "conv_bf16x3_launch: the fp16 form exists for the fused pre-activation conv only");
@@ -361,7 +359,7 @@ int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bia
 }
 
 // ldm Downsample (encoder): conv3x3 stride 2 over pad(x, right 1, bottom 1); output (Hin - 2) / 2 + 1 rows / columns
-int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
+int mdt::conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
                              hipStream_t s) {
     ConvBParams P;
     P.perm = conv_bf16x3_perm(cin);
@@ -384,5 +382,3 @@ int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float*
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
-
-}  // namespace mdt

@@ -259,10 +259,6 @@ __global__ __launch_bounds__(256) void k_rec_to_f32(const u32x4* __restrict__ re
 
 }  // namespace
 
-namespace mdt {
-
-size_t conv_bf16x3_direct_records(int cout, int cin);   // vae_conv_bf16x3.hip
-
 // MDTILE_REC_PERSIST=0 (probes build only): one item per block (A/B of the persistent schedule; read per launch so a probe can flip it in-process)
 constexpr int REC_STAGGER_PCT_DEFAULT = 0;      // off: -2 ... -5 % on single conv1 launches (profiles/r4u, r4v), nothing on the 8K decode (profiles/r4y: 1869 / 1870 vs 1870 / 1874 ms)
 
@@ -287,14 +283,6 @@ static int num_cus() {
     return n;
 }
 
-// vae_conv_rec2.hip: the two-blocks-per-CU form of the cout % 128 == 0 kernels
-int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, int x16 = 0, int y16 = 0);
-// probes/csrc/vae_conv_recd.hip (PROBES twin of the library only -- a measured, rejected form: DESIGN.md / docs/history/r5.md): 64-cout items with
-// the epilogue dripped into the next item's K loop (direct 3x3, cin % 32 == 0, cin >= 128).  Declared here, defined only in that build: the one
-// call sits in a discarded `if constexpr (kProbes)` statement, so the shipping library neither references nor carries the kernel.
-bool conv_recd_supported(int cout, int cin);
-int conv_recd_launch(ConvRParams P, int B, hipStream_t s, int cus);
-
 // Which kernel family takes a launch.  The two-blocks-per-CU kernels (vae_conv_rec2.hip) lose 3-12 % on launches that fill the chip many
 // times over (profiles/r4a: their 8-row items double the weight stream through the CU's memory pipe and the store epilogue is not
 // hidden), but their items are half as large and 512 of them are resident: launches of only a few item rounds quantise better
@@ -317,13 +305,42 @@ static bool rec_two_blocks(long long items16, long long items8, int cus, int up,
     return t2 < 0.97 * t1;
 }
 
-bool conv_rec_supported(int cout, int cin, int ksize) { return ksize == 3 && cin % 32 == 0 && (cout % 128 == 0 || (cout >= 1 && cout < 32)); }
+// The route of a launch: the family that takes it (1 / 2 = one / two blocks per CU, 3 = the dripped-epilogue kernel of the PROBES twin) and the
+// items it has in the first two (16 / 8 output rows x 32 px x 128 couts; the sub-pixel form tiles the INPUT grid in 8 / 4 rows, per row parity).
+// Statistics force the one-block family; the cost model prices the persistent 128-cout kernels only, on whole XCD rows of the CUs; a NAMED
+// family is honoured or refused, never silently replaced by the cost model (family 3 exists for the bf16 record forms only).
+struct RecRoute {
+    int family;
+    long long items16, items8;
+};
+static RecRoute rec_route(int B, int cout, int H, int W, int up, int family, bool fp16_forms, bool stats) {
+    const int hin = up ? H / 2 : H, win = up ? W / 2 : W, per = (cout % 128 == 0 ? cout / 128 : 1) * (up ? 2 : 1);
+    const long long px = (win + 31) / 32;
+    RecRoute r;
+    r.items16 = (px * ((hin + (up ? 7 : 15)) / (up ? 8 : 16)) + 7) / 8 * 8 * per * B;
+    r.items8 = (px * ((hin + (up ? 3 : 7)) / (up ? 4 : 8)) + 7) / 8 * 8 * per * B;
+    if (stats) family = 1;
+    if (kProbes && family == 3 && !fp16_forms) r.family = 3;
+    else r.family = (cout % 128 == 0 && rec_persistent() && rec_two_blocks(r.items16, r.items8, num_cus() / 8 * 8, up, family)) ? 2 : 1;
+    return r;
+}
 
-size_t rec_image_bytes(int B, int C, int H, int W) { return (size_t)B * C * (H + 2) * rec_pitch(W) * 4; }
+// The one-block-per-CU kernel of a launch, from the six facts the families share: upsample, one-term arithmetic (MDTILE_PRECISION_BF16, or the
+// fp16 kernels of x16), the fp16 record forms x16 / y16, statistics, the narrow cout (conv_out: one 32-cout tile, bias padded to 32 by the caller)
+static RecKernel rec_kernel(int up, bool one, int x16, int y16, bool st, bool narrow) {
+    if (up) return y16 ? k_upconv_rec_o16 : one ? (st ? k_upconv_rec1t_st : k_upconv_rec1t) : (st ? k_upconv_rec_st : k_upconv_rec);
+    if (x16) return st ? k_conv3x3_rec_f16_st<2, 2, 4> : narrow ? k_conv3x3_rec_f16s<1, 1, 2> : y16 ? k_conv3x3_rec_f16<2, 2, 4> : k_conv3x3_rec_f16s<2, 2, 4>;
+    if (one) return st ? k_conv3x3_rec1t_st<2, 2, 4> : narrow ? k_conv3x3_rec1t<1, 1, 2> : k_conv3x3_rec1t<2, 2, 4>;
+    return st ? k_conv3x3_rec_st<2, 2, 4> : narrow ? k_conv3x3_rec<1, 1, 2> : k_conv3x3_rec<2, 2, 4>;
+}
 
-size_t rec_plane_records(int H, int W) { return (size_t)(H + 2) * rec_pitch(W); }
+bool mdt::conv_rec_supported(int cout, int cin, int ksize) { return ksize == 3 && cin % 32 == 0 && (cout % 128 == 0 || (cout >= 1 && cout < 32)); }
 
-int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16) {
+size_t mdt::rec_image_bytes(int B, int C, int H, int W) { return (size_t)B * C * (H + 2) * rec_pitch(W) * 4; }
+
+size_t mdt::rec_plane_records(int H, int W) { return (size_t)(H + 2) * rec_pitch(W); }
+
+int mdt::rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int B, int C, int H, int W, hipStream_t s, int f16) {
     dim3 grid(cdiv(W + 2, 256), H + 2, B * (C / 8));
     if (f16) hipLaunchKernelGGL(k_rec_from_f32_f16, grid, dim3(256), 0, s, d_x, d_coef, (u32x4*)d_rec, C, H, W);
     else hipLaunchKernelGGL(k_rec_from_f32, grid, dim3(256), 0, s, d_x, d_coef, (u32x4*)d_rec, C, H, W);
@@ -331,7 +348,7 @@ int rec_from_f32_launch(const float* d_x, const float* d_coef, void* d_rec, int 
     return MDTILE_OK;
 }
 
-int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16) {
+int mdt::rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W, hipStream_t s, int f16) {
     dim3 grid(cdiv(W, 256), H, B * (C / 8));
     if (f16) hipLaunchKernelGGL(k_rec_to_f32_f16, grid, dim3(256), 0, s, (const u32x4*)d_rec, d_x, C, H, W);
     else hipLaunchKernelGGL(k_rec_to_f32, grid, dim3(256), 0, s, (const u32x4*)d_rec, d_x, C, H, W);
@@ -339,39 +356,25 @@ int rec_to_f32_launch(const void* d_rec, float* d_x, int B, int C, int H, int W,
     return MDTILE_OK;
 }
 
-// win (sub-pixel upsample kernel only, else null): {HinF, WinF, y0[0], x0[0], ..., y0[7], x0[7]} -- d_xrec is the record image of
-// [B, cin, HinF, WinF] and image b's conv reads its window [y0[b & 7] : .. + H/2, x0[b & 7] : .. + W/2]  (all 8 slots filled)
 // statistics in the epilogue: one-block-per-CU kernels of the 128-cout family only.  A launch the cost model would hand to the two-blocks
 // family (a few item rounds: the 278 x 278 level of the 8K decode) gains more from that family than from dropping the statistics pass.
-bool conv_rec_stats_in_epilogue(int B, int cin, int cout, int H, int W, int up) {
-    if (cout % 128 != 0 || !rec_persistent()) return false;
-    const int cus = num_cus() / 8 * 8;
-    const int hin = up ? H / 2 : H, win = up ? W / 2 : W, per = (cout / 128) * (up ? 2 : 1);
-    const long long px = (win + 31) / 32;
-    const long long items16 = (px * ((hin + (up ? 7 : 15)) / (up ? 8 : 16)) + 7) / 8 * 8 * per * B;
-    const long long items8 = (px * ((hin + (up ? 3 : 7)) / (up ? 4 : 8)) + 7) / 8 * 8 * per * B;
-    (void)cin;
-    return !rec_two_blocks(items16, items8, cus, up, 0);
+bool mdt::conv_rec_stats_in_epilogue(int B, int cout, int H, int W, int up) {
+    return cout % 128 == 0 && rec_persistent() && rec_route(B, cout, H, W, up, 0, false, false).family == 1;
 }
 // units of the per-wave partials a statistics launch writes (conv_stats_finish_launch): [B][units][NCB][32 quads][2] doubles
-int conv_rec_stats_units(int H, int W, int up) {
+int mdt::conv_rec_stats_units(int H, int W, int up) {
     return up ? ((W / 2 + 31) / 32) * ((H / 2 + 7) / 8) * 8 : ((W + 31) / 32) * ((H + 15) / 16) * 4;
 }
 
-int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y32, void* d_yrec,
-                    const float* d_ycoef, int B, int cin, int cout, int H, int W, int up, hipStream_t s, const int* win, int family,
-                    double* d_part, int x16, int y16) {
-    // x16 (MDTILE_PRECISION_F16): d_xrec is an activated record image in its fp16 form and d_w_rec the fp16 weight plane -> the fp16 kernels;
-    // y16: the (activated) record output is written in the fp16 form.  The C entry points have checked both against the mode.
-    MDT_CHECK_ARG(!(x16 && up) && !(y16 && !(d_yrec && d_ycoef)) && !(y16 && d_part), "conv_rec_launch: fp16 record forms: x16=%d up=%d y16=%d", x16, up, y16);
+int mdt::conv_rec_launch(const RecConvCall& c, hipStream_t s) {
+    const int B = c.B, cin = c.cin, cout = c.cout, H = c.H, W = c.W, up = c.up, x16 = c.x16, y16 = c.y16;
+    const int* win = c.win;
+    MDT_CHECK_ARG(!(x16 && up) && !(y16 && !(c.y_rec && c.y_coef)) && !(y16 && c.d_part), "conv_rec_launch: fp16 record forms: x16=%d up=%d y16=%d", x16, up, y16);
+    MDT_CHECK_ARG(!c.d_part || (cout % 128 == 0 && rec_persistent()), "conv_rec_launch: no statistics kernel for cout=%d", cout);
     ConvRParams P;
-    P.gn_part = d_part;
-    if (d_part) {
-        MDT_CHECK_ARG(cout % 128 == 0 && rec_persistent(), "conv_rec_launch: no statistics kernel for cout=%d", cout);
-        family = 1;
-    }
-    P.x = (const u32x4*)d_xrec; P.w = (const u32x4*)d_w_rec; P.bias = d_bias; P.res = d_res; P.y32 = d_y32;
-    P.yrec = (u32x4*)d_yrec; P.coef = d_ycoef;
+    P.gn_part = c.d_part;
+    P.x = (const u32x4*)c.x_rec; P.w = (const u32x4*)c.w_rec; P.bias = c.bias; P.res = c.res; P.y32 = c.y32;
+    P.yrec = (u32x4*)c.y_rec; P.coef = c.y_coef;
     P.B = B; P.Cin = cin; P.Cout = cout; P.H = H; P.W = W;
     P.Hin = up ? H / 2 : H; P.Win = up ? W / 2 : W;
     P.HinF = win ? win[0] : P.Hin; P.WinF = win ? win[1] : P.Win;
@@ -386,68 +389,33 @@ int conv_rec_launch(const void* d_xrec, const void* d_w_rec, const float* d_bias
     if (const char* e = probe_env("MDTILE_REC_DBG")) P.dbg = atoi(e);      // probing only (probes/conv_rec_diag.py, conv_item_timeline.py): see ConvRParams::dbg
     if (P.dbg & 8)
         if (const char* e = probe_env("MDTILE_REC_STAMPS")) P.census = reinterpret_cast<unsigned*>((uintptr_t)strtoull(e, nullptr, 16));
-    if (up) P.w = (const u32x4*)d_w_rec + conv_bf16x3_direct_records(cout, cin);
+    if (up) P.w = (const u32x4*)c.w_rec + conv_bf16x3_direct_records(cout, cin);
+    // MDTILE_PRECISION_BF16: the one-term kernels, a third of the MFMAs per step; x16: the fp16 kernels (one term as well), never the upsample conv
+    const bool one = up ? (mfma_single_term() && !y16) : (mfma_single_term() || x16);
+    const RecRoute r = rec_route(B, cout, H, W, up, c.family, x16 || y16, c.d_part != nullptr);
     if constexpr (kProbes) {
-        if (family == 3 && !x16 && !y16) {      // a NAMED family is honoured or refused, never silently replaced by the cost model
-            MDT_CHECK_ARG(!up && !win && !d_part && conv_recd_supported(cout, cin), "conv_rec_launch: the dripped-epilogue kernel takes direct 3x3 convs with cin %% 32 == 0, "
+        if (r.family == 3) {
+            MDT_CHECK_ARG(!up && !win && conv_recd_supported(cout, cin), "conv_rec_launch: the dripped-epilogue kernel takes direct 3x3 convs with cin %% 32 == 0, "
                           "cin >= 128, cout %% 128 == 0, no window, no statistics (cout=%d cin=%d up=%d)", cout, cin, up);
             return conv_recd_launch(P, B, s, num_cus());
         }
     }
-    if (cout % 128 == 0 && rec_persistent()) {
-        const int cus = num_cus() / 8 * 8;
-        const int hin = up ? P.Hin : H, win = up ? P.Win : W, per = P.NCB * (up ? 2 : 1);      // items tile the INPUT grid of the sub-pixel form
-        const long long px = (win + 31) / 32;
-        const long long items16 = (px * ((hin + (up ? 7 : 15)) / (up ? 8 : 16)) + 7) / 8 * 8 * per * B;
-        const long long items8 = (px * ((hin + (up ? 3 : 7)) / (up ? 4 : 8)) + 7) / 8 * 8 * per * B;
-        if (rec_two_blocks(items16, items8, cus, up, family)) return conv_rec2_launch(P, B, up, s, num_cus(), x16, y16);
-    }
+    if (r.family == 2) return conv_rec2_launch(P, B, up, s, num_cus(), one, x16, y16);
+    // one block per CU (155 KB LDS, 2 waves per SIMD)
+    P.PX = ((up ? P.Win : W) + 31) / 32;
+    P.ptiles = P.PX * (up ? (P.Hin + 7) / 8 : (H + 15) / 16);
+    const int cus = num_cus();
     // start-up stagger (stagger_start): spread = MDTILE_REC_STAGGER_PCT percent of an estimated item period, launches of >= 6 rounds only
     // default: a quarter period for launches that write records ONLY (a conv1: -2 ... -5 % per launch, profiles/r4u, r4v; launches with an fp32
     // stream run at their CU's own memory-pipe floor either way and only pay the late end)
-    auto stagger = [&](long long items, int cus, unsigned period_ticks) {
+    if (up || cout % 128 == 0) {
         const char* e = probe_env("MDTILE_REC_STAGGER_PCT");      // (read per launch: probes/conv_stagger_ab.py switches it between launches)
-        const int p = e ? atoi(e) : ((!d_y32 && !d_res) ? REC_STAGGER_PCT_DEFAULT : 0);
-        P.skew_ticks = (rec_persistent() && items >= 6LL * cus && p > 0) ? period_ticks * (unsigned)p / 100u : 0u;
-    };
-    if (up) {
-        P.PX = (P.Win + 31) / 32;
-        P.ptiles = P.PX * ((P.Hin + 7) / 8);
-        const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * 2 * B;
-        const int cus = num_cus();
-        stagger(items, cus, (unsigned)P.NK * 400u + 2000u);
-        dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-        if (y16) hipLaunchKernelGGL(k_upconv_rec_o16, grid, block, 0, s, P);
-        else if (mfma_single_term()) {
-            if (d_part) hipLaunchKernelGGL(k_upconv_rec1t_st, grid, block, 0, s, P);
-            else hipLaunchKernelGGL(k_upconv_rec1t, grid, block, 0, s, P);
-        } else {
-            if (d_part) hipLaunchKernelGGL(k_upconv_rec_st, grid, block, 0, s, P);
-            else hipLaunchKernelGGL(k_upconv_rec, grid, block, 0, s, P);
-        }
-        MDT_LAUNCH_CHECK();
-        return MDTILE_OK;
+        const int p = e ? atoi(e) : ((!c.y32 && !c.res) ? REC_STAGGER_PCT_DEFAULT : 0);
+        const unsigned period_ticks = up ? (unsigned)P.NK * 400u + 2000u : (unsigned)P.NK * 900u + 1500u;
+        P.skew_ticks = (rec_persistent() && r.items16 >= 6LL * cus && p > 0) ? period_ticks * (unsigned)p / 100u : 0u;
     }
-    P.PX = (W + 31) / 32;
-    P.ptiles = P.PX * ((H + 15) / 16);
-    const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * B;
-    const int cus = num_cus();                    // one block per CU (155 KB LDS, 2 waves per SIMD)
-    if (cout % 128 == 0) stagger(items, cus, (unsigned)P.NK * 900u + 1500u);
-    dim3 grid((unsigned)((items < cus || !rec_persistent()) ? items : cus / 8 * 8)), block(512);
-    if (x16) {
-        if (d_part) hipLaunchKernelGGL((k_conv3x3_rec_f16_st<2, 2, 4>), grid, block, 0, s, P);
-        else if (cout % 128 != 0) hipLaunchKernelGGL((k_conv3x3_rec_f16s<1, 1, 2>), grid, block, 0, s, P);
-        else if (y16) hipLaunchKernelGGL((k_conv3x3_rec_f16<2, 2, 4>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_rec_f16s<2, 2, 4>), grid, block, 0, s, P);
-    } else if (mfma_single_term()) {
-        if (d_part) hipLaunchKernelGGL((k_conv3x3_rec1t_st<2, 2, 4>), grid, block, 0, s, P);
-        else if (cout % 128 == 0) hipLaunchKernelGGL((k_conv3x3_rec1t<2, 2, 4>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_rec1t<1, 1, 2>), grid, block, 0, s, P);
-    } else if (d_part) hipLaunchKernelGGL((k_conv3x3_rec_st<2, 2, 4>), grid, block, 0, s, P);
-    else if (cout % 128 == 0) hipLaunchKernelGGL((k_conv3x3_rec<2, 2, 4>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_conv3x3_rec<1, 1, 2>), grid, block, 0, s, P);      // conv_out: one 32-cout tile, bias padded to 32 by the caller
+    dim3 grid((unsigned)((r.items16 < cus || !rec_persistent()) ? r.items16 : cus / 8 * 8)), block(512);
+    hipLaunchKernelGGL(rec_kernel(up, one, x16, y16, c.d_part != nullptr, cout % 128 != 0), grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
-
-}  // namespace mdt

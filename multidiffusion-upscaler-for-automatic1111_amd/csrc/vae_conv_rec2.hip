@@ -156,8 +156,6 @@ __device__ __forceinline__ int wrap6(int x) { return x >= 6 ? x - 6 : x; }
 
 }  // namespace
 
-namespace mdt {
-
 // arrival counters of startup_skew: one buffer per device, allocated on first use (under a lock: launches may come from several host
 // threads), zeroed once; every launch takes a fresh epoch (see startup_skew), so nothing is ever reset.  The counter words are per
 // DEVICE, not per stream: two rec2 launches in flight on one device at once (different streams) re-stamp each other's arrival counts,
@@ -185,11 +183,18 @@ static unsigned* cu_counters(unsigned* epoch) {
     return buf[dev];
 }
 
+// The two-blocks-per-CU kernel of a launch, from the facts conv_rec_launch hands over (vae_conv_rec.hip: rec_kernel; no statistics, no narrow cout here)
+static RecKernel rec2_kernel(int up, bool one, int x16, int y16) {
+    if (up) return y16 ? k_upconv_rec2_o16 : one ? k_upconv_rec2_1t : k_upconv_rec2;
+    if (x16) return y16 ? k_conv3x3_rec2_f16<2, 2, 4> : k_conv3x3_rec2_f16s<2, 2, 4>;
+    return one ? k_conv3x3_rec2_1t<2, 2, 4> : k_conv3x3_rec2<2, 2, 4>;
+}
+
 // Probing switches (PROBES build of the library only -- common.h: probe_env; read per launch so that a probe can flip them in-process):
 //   MDTILE_REC2_SKEW    0 = no start-up delay, 1 = by block index (>= grid / 2), 2 = by the per-CU arrival counter (default)
 //   MDTILE_REC2_SKEW_PCT  the delay as a percentage of an item's K loop at one block per CU-half (default 100)
 //   MDTILE_REC2_CENSUS  device address (hex) of a [grid] unsigned buffer that receives every block's hardware CU id
-int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, int x16, int y16) {
+int mdt::conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, bool one, int x16, int y16) {
     int skew = 2, pct = 100;
     if (const char* e = probe_env("MDTILE_REC2_SKEW")) skew = atoi(e);
     if (const char* e = probe_env("MDTILE_REC2_SKEW_PCT")) pct = atoi(e);
@@ -200,33 +205,15 @@ int conv_rec2_launch(ConvRParams P, int B, int up, hipStream_t s, int cus, int x
     int per_cu = 2;                                   // two blocks per CU
     if (const char* e = probe_env("MDTILE_REC2_PER_CU")) per_cu = atoi(e) == 1 ? 1 : 2;      // probing: a 4-wave block alone on its CU
     const int grid_max = per_cu * (cus / 8 * 8);
-    // MDTILE_PRECISION_BF16: the one-term kernels, a third of the MFMAs per step; x16: the fp16 kernels (one term as well), never the upsample conv
-    const bool one = up ? (mfma_single_term() && !y16) : (mfma_single_term() || x16);
-    if (up) {
-        // K loop of one item with the SIMDs to itself: NK x 8 steps x 12 MFMAs x 32 clk at ~2 GHz = NK x 1.5 us; in 10 ns ticks
-        P.skew_ticks = skew ? (unsigned)((long long)P.NK * 154 * pct / (one ? 300 : 100)) : 0u;
-        P.PX = (P.Win + 31) / 32;
-        P.ptiles = P.PX * ((P.Hin + 3) / 4);
-        const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * 2 * B;
-        dim3 grid((unsigned)(items < grid_max ? items : grid_max)), block(256);
-        if (y16) hipLaunchKernelGGL(k_upconv_rec2_o16, grid, block, 0, s, P);
-        else if (one) hipLaunchKernelGGL(k_upconv_rec2_1t, grid, block, 0, s, P);
-        else hipLaunchKernelGGL(k_upconv_rec2, grid, block, 0, s, P);
-        MDT_LAUNCH_CHECK();
-        return MDTILE_OK;
-    }
-    // NK x 9 steps x 24 MFMAs x 32 clk = NK x 3.5 us
-    P.skew_ticks = skew ? (unsigned)((long long)P.NK * 346 * pct / (one ? 300 : 100)) : 0u;
-    P.PX = (P.W + 31) / 32;
-    P.ptiles = P.PX * ((P.H + 7) / 8);
-    const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * B;
+    // K loop of one item with the SIMDs to itself, in 10 ns ticks.  up: NK x 8 steps x 12 MFMAs x 32 clk at ~2 GHz = NK x 1.5 us; direct: NK x 9 steps
+    // x 24 MFMAs x 32 clk = NK x 3.5 us
+    P.skew_ticks = skew ? (unsigned)((long long)P.NK * (up ? 154 : 346) * pct / (one ? 300 : 100)) : 0u;
+    P.PX = ((up ? P.Win : P.W) + 31) / 32;
+    P.ptiles = P.PX * (up ? (P.Hin + 3) / 4 : (P.H + 7) / 8);
+    const long long items = (long long)((P.ptiles + 7) / 8) * 8 * P.NCB * (up ? 2 : 1) * B;
     dim3 grid((unsigned)(items < grid_max ? items : grid_max)), block(256);
-    if (x16 && y16) hipLaunchKernelGGL((k_conv3x3_rec2_f16<2, 2, 4>), grid, block, 0, s, P);
-    else if (x16) hipLaunchKernelGGL((k_conv3x3_rec2_f16s<2, 2, 4>), grid, block, 0, s, P);
-    else if (one) hipLaunchKernelGGL((k_conv3x3_rec2_1t<2, 2, 4>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_conv3x3_rec2<2, 2, 4>), grid, block, 0, s, P);
+    hipLaunchKernelGGL(rec2_kernel(up, one, x16, y16), grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
 
-}  // namespace mdt

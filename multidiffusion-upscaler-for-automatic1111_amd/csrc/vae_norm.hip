@@ -1,7 +1,7 @@
 // HBM-bound Tiled-VAE kernels: GroupNorm statistics (K11), pooling (K12), fixed-statistics GroupNorm + SiLU (K13),
 // SiLU / residual add (K16), crop + assemble (K17), fast-mode estimator input (K18).
 // Upstream: scripts/tilevae.py:102-104, 207-259, 289-361, 545-559, 612-632.  All tensors fp32 NCHW.
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 
@@ -315,10 +315,9 @@ __global__ __launch_bounds__(256) void k_fast_apply(const float* __restrict__ z,
 
 }  // namespace
 
-namespace mdt {
 // mean / var [B * groups] of a conv output [B, cout, H * W = HW] from the partials its epilogue left (d_cpart, see k_conv_stats_partial);
 // d_gnws: mdtile_gn_stats_ws_size(B, groups) bytes
-int conv_stats_finish_launch(const double* d_cpart, int B, int cout, size_t HW, int units, int NCB, int QB, int groups, float* d_mean, float* d_var,
+int mdt::conv_stats_finish_launch(const double* d_cpart, int B, int cout, size_t HW, int units, int NCB, int QB, int groups, float* d_mean, float* d_var,
                              void* d_gnws, hipStream_t s) {
     const int BG = B * groups, cpg = cout / groups;
     MDT_CHECK_ARG(groups > 0 && cout % groups == 0 && cpg % 4 == 0 && (4 * QB) % cpg == 0 && BG <= 65535,
@@ -329,7 +328,6 @@ int conv_stats_finish_launch(const double* d_cpart, int B, int cout, size_t HW, 
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
-}  // namespace mdt
 
 extern "C" size_t mdtile_gn_stats_ws_size(int B, int groups) { return (size_t)B * groups * GN_NBLK * 2 * sizeof(double); }
 

@@ -10,7 +10,7 @@
 //
 // Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
 // mdtile_blend_finalize -- wrap-around is not combined with regions or with the multi-GPU partial path.
-#include "common.h"
+#include "launchers.h"
 
 using namespace mdt;
 
@@ -237,9 +237,7 @@ void launch_wrap_blend_planes(const WrapBlendParams& P, int method, hipStream_t 
 
 }  // namespace
 
-namespace mdt {
-
-int wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_weights, hipStream_t s) {
+int mdt::wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_weights, hipStream_t s) {
     if (int rc = plan_upload(p)) return rc;
     const int n = p->w * p->h;
     hipLaunchKernelGGL(k_wrap_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, s, p->w, p->h, p->tw, p->cols, p->d_xs, p->d_ys, p->d_colrange,
@@ -249,7 +247,7 @@ int wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_weight
 }
 
 // tiles [t_lo, t_hi) into the plan's batch buffers ptrs[0 .. nptrs) (holes are fine: only the batches of those tiles are touched)
-int wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi, hipStream_t s) {
+int mdt::wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi, hipStream_t s) {
     MDT_CHECK_ARG(p && d_x_in && ptrs, "mdtile_gather: null argument");
     MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_gather: bad N=%d C=%d", N, C);
     MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather: bad dtype %d", dtype);
@@ -276,7 +274,7 @@ int wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_i
     return MDTILE_OK;
 }
 
-int wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, hipStream_t s) {
+int mdt::wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, hipStream_t s) {
     MDT_CHECK_ARG(p && a, "mdtile_blend: null plan/args");
     // what this form does not do, by name
     MDT_CHECK_ARG(num_regions == 0, "mdtile_blend: a wrap-x plan takes no custom regions (%d given): wrap-around is not combined with regions", num_regions);
@@ -311,5 +309,3 @@ int wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* con
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
-
-}  // namespace mdt

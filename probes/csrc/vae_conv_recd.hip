@@ -575,12 +575,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_recd(const ConvRParams P) {
 
 }  // namespace
 
-namespace mdt {
-
 // cin % 64 == 0 (whole 4-K-step trips), 128-cout packed blocks; H, W: output = input size
-bool conv_recd_supported(int cout, int cin) { return cin % 32 == 0 && cin >= 128 && cout % 128 == 0; }
+bool mdt::conv_recd_supported(int cout, int cin) { return cin % 32 == 0 && cin >= 128 && cout % 128 == 0; }
 
-int conv_recd_launch(ConvRParams P, int B, hipStream_t s, int cus) {
+int mdt::conv_recd_launch(ConvRParams P, int B, hipStream_t s, int cus) {
     P.PX = (P.W + 31) / 32;
     P.ptiles = P.PX * ((P.H + 15) / 16);
     const long long items = (long long)((P.ptiles + 7) / 8) * 8 * (P.Cout / 64) * B;
@@ -590,5 +588,3 @@ int conv_recd_launch(ConvRParams P, int B, hipStream_t s, int cus) {
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
-
-}  // namespace mdt

@@ -240,6 +240,39 @@ def test_upconv_window_rejects_a_window_outside_the_image(plugin, cuda):
             pc.call_rec(xr, upsample2x=True, window=bad)
 
 
+@pytest.mark.parametrize("case,match", [
+    ("x16_with_upsample", "record format mismatch"),
+    ("y16_set_without_an_fp16_output", "record format mismatch"),
+    ("y16_unset_with_an_fp16_output", "record format mismatch"),
+    ("stats_with_two_blocks", "only the one-block-per-CU family leaves statistics"),
+    ("narrow_cout_with_residual", "narrow"),
+])
+def test_record_conv_calls_refused_on_the_host(plugin, cuda, monkeypatch, case, match):
+    """Calls the C entry points refuse before any launch (mdtile_conv2d_rec / _rec_stats), through the binding with valid tensors at the smallest
+    shape the kernels take: were a refusal lost, the call would run a small valid conv and this test would say so."""
+    E = plugin.engine
+    torch.manual_seed(7)
+    cout = 3 if case.startswith("narrow") else 128
+    conv = torch.nn.Conv2d(32, cout, 3, 1, 1)
+    pc = E.PackedConv(conv.weight.detach().to(cuda), conv.bias.detach().to(cuda))
+    x, coef = torch.randn(1, 32, 8, 8, device=cuda), _coef(1, 32, 2).to(cuda)
+    with pytest.raises(E.MdtileError, match=match):
+        if case == "x16_with_upsample":
+            with E.precision(E.PRECISION_F16):
+                pc.call_rec(E.rec_from_f32(x, coef), upsample2x=True)      # an activated record is the fp16 form there
+        elif case == "y16_set_without_an_fp16_output":
+            pc.call_rec(E.rec_from_f32(x), want_rec=True, family=E.CONV_REC_Y_F16)      # (`family` is or-ed into the call's flags)
+        elif case == "y16_unset_with_an_fp16_output":
+            with E.precision(E.PRECISION_F16):
+                monkeypatch.setattr(E, "_act_rec_fmt", lambda coef: E.REC_BF16X2)      # the binding would set the flag: tag the output as a split
+                pc.call_rec(E.rec_from_f32(x), want_rec=True, rec_coef=_coef(1, 128, 3).to(cuda))
+        elif case == "stats_with_two_blocks":
+            pc.call_rec_stats(E.rec_from_f32(x), family=E.CONV_REC_TWO_BLOCKS)
+        else:
+            pc.call_rec(E.rec_from_f32(x), residual=torch.randn(1, 3, 8, 8, device=cuda))
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("hw,ts,N", [((64, 88), 32, 1), ((40, 40), 64, 1), ((70, 40), 16, 2), ((70, 40), 16, 3)])
 def test_fast_decode_with_live_windows_equals_the_whole_tile_sweep(plugin, cuda, hw, ts, N):
     """Full-width SD decoder, fast mode: tiles narrowed where the resolution doubles (default) == whole padded tiles, BIT FOR BIT on the

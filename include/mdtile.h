@@ -110,6 +110,18 @@ int mdtile_plan_bboxes(const mdtile_plan* plan, int* xywh);
  * MDTILE_BLEND_* flag, a row band, mdtile_gather_range, mdtile_blend_finalize, the packed destination of mdtile_gather_all, mdtile_blend_dispatch. */
 mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs);
 int mdtile_plan_wrap_x(const mdtile_plan* plan);
+/* The canvas closed in y as well (seamless textures: a torus), or in y alone (a vertical strip that tiles): per-axis wrap.
+ *   tile and overlap clamp, batching and tile order (row-major, y outer): as mdtile_plan_create(clamp = 1)
+ *   a wrapped axis uses the circle rule of the wrap-x columns: rows = ceil(h / (th - ov));  y_r = (int)(r * (double)h / rows);  tile row r covers
+ *   the rows (y_r + i) mod h, i in [0, th); a box reports y_r, so y_r + th may exceed h.  An unwrapped axis keeps the plain origins.
+ *   (wrap_x, wrap_y) = (1, 0): exactly the plan of mdtile_plan_create_wrap_x.   (0, 0): NULL + mdtile_last_error (use mdtile_plan_create).
+ *   effective tw >= w on a wrapped x, th >= h on a wrapped y: NULL + mdtile_last_error, the text names the axis.
+ * mdtile_plan_wrap_x / mdtile_plan_wrap_y: 1 when that axis of the plan wraps, else 0.
+ * Everything said above of a wrap-x plan holds for a plan with wrap_y: the same calls take it (both indices mod the canvas, the covering tiles
+ * summed in ascending tile index -- rows outer, columns inner -- so results equal the sequential `+=` loop over the tile list bit for bit), and
+ * the same calls are refused. */
+mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int wrap_x, int wrap_y);
+int mdtile_plan_wrap_y(const mdtile_plan* plan);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Weight maps (init time, device).

@@ -146,4 +146,15 @@ struct mdtile_plan {
     // tile columns of a canvas column / of a quad are a CYCLIC run: colrange[x] and colquad[x/4].x hold first | count << 16 with `first` the
     // run's start on the circle (first + count may pass cols: the run goes on at column 0); colquad's .y .z .w are unused.  Rows as above.
     int wrap_x;
+    // mdtile_plan_create_wrap with wrap_y: the canvas is closed in y as well (a torus) or in y alone.  ys[r] + th may pass h (tile row r covers
+    // the rows (ys[r] + i) mod h); rowrange[y] and rowinfo[y].x hold the CYCLIC run of the row list, as above; rowinfo's .y .z .w are unused.
+    // With wrap_x == 0 the columns are plain (origins_1d) and their runs never pass cols.
+    int wrap_y;
 };
+
+namespace mdt {
+// a plan whose canvas is closed in x, in y or in both: wrap.hip's kernels take it, and what they do not do is refused by name
+static inline bool plan_wraps(const ::mdtile_plan* p) { return p->wrap_x || p->wrap_y; }
+// what an error text calls such a plan
+static inline const char* wrap_kind(const ::mdtile_plan* p) { return !p->wrap_y ? "wrap-x" : p->wrap_x ? "wrap-x + wrap-y (torus)" : "wrap-y"; }
+}  // namespace mdt

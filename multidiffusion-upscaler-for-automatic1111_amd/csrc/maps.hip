@@ -99,7 +99,7 @@ extern "C" int mdtile_feather_mask(int w, int h, double ratio, float* d_out, mdt
 
 extern "C" int mdtile_weight_map_add_grid(const mdtile_plan* p, const float* d_tile_w, float* d_weights, mdtile_stream_t stream) {
     MDT_CHECK_ARG(p && d_weights, "mdtile_weight_map_add_grid: null argument");
-    if (p->wrap_x) return wrap_weight_map(p, d_tile_w, d_weights, as_stream(stream));   // wrap.hip
+    if (plan_wraps(p)) return wrap_weight_map(p, d_tile_w, d_weights, as_stream(stream));   // wrap.hip
     if (int rc = plan_upload(p)) return rc;
     int n = p->w * p->h;
     hipLaunchKernelGGL(k_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), p->w, p->h, p->tw, p->cols,

@@ -239,6 +239,103 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int 
 
 extern "C" int mdtile_plan_wrap_x(const mdtile_plan* p) { return p && p->wrap_x ? 1 : 0; }
 
+// ---- the canvas closed in y, or in both axes (seamless textures: a torus) ---------------------------------------------
+// origins of one axis: on the circle when it wraps (the rule of the wrap-x columns), origins_1d when it does not
+static void axis_origins(int extent, int tile, int ov, bool wrap, std::vector<int>& out) {
+    if (!wrap) return origins_1d(extent, tile, ov, out);
+    const int n = (int)std::ceil((double)extent / (double)(tile - ov));
+    out.resize(n);
+    for (int i = 0; i < n; ++i) out[i] = (int)((double)i * (double)extent / (double)n);
+}
+
+// does the tile with origin `org` cover coordinate p?  (a plain tile never passes the edge: org + tile <= extent)
+static inline bool axis_covers(int p, int org, int tile, int extent, bool wrap) {
+    return wrap ? ((p - org + extent) % extent) < tile : (org <= p && p < org + tile);
+}
+
+extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int wrap_x, int wrap_y) {
+    if (!wrap_x && !wrap_y) {
+        mdt::set_error("mdtile_plan_create_wrap: neither axis wraps: the plain grid is mdtile_plan_create");
+        return nullptr;
+    }
+    if (!wrap_y) return mdtile_plan_create_wrap_x(w, h, tile_w, tile_h, overlap, tile_bs);
+    if (w <= 0 || h <= 0 || tile_w <= 0 || tile_h <= 0 || tile_bs <= 0 || w > 65535 || h > 65535) {
+        mdt::set_error("mdtile_plan_create_wrap: bad arguments w=%d h=%d tile=%dx%d bs=%d", w, h, tile_w, tile_h, tile_bs);
+        return nullptr;
+    }
+    // the clamp of mdtile_plan_create(clamp = 1)
+    const int tw = tile_w < w ? tile_w : w, th = tile_h < h ? tile_h : h;
+    const int mn = tile_w < tile_h ? tile_w : tile_h;
+    int ov = overlap < mn - 4 ? overlap : mn - 4;
+    if (ov < 0) ov = 0;
+    if (wrap_x && tw >= w) {
+        mdt::set_error("mdtile_plan_create_wrap: x axis: tile width %d >= canvas width %d: a tile would meet itself across the seam", tw, w);
+        return nullptr;
+    }
+    if (th >= h) {
+        mdt::set_error("mdtile_plan_create_wrap: y axis: tile height %d >= canvas height %d: a tile would meet itself across the seam", th, h);
+        return nullptr;
+    }
+    if (tw - ov == 0 || th - ov == 0) {
+        mdt::set_error("mdtile_plan_create_wrap: overlap %d equals the canvas-clamped tile %dx%d (division by zero upstream)", ov, tw, th);
+        return nullptr;
+    }
+    std::vector<int> xs, ys;
+    axis_origins(w, tw, ov, wrap_x != 0, xs);
+    axis_origins(h, th, ov, true, ys);
+    if (xs.size() > 32767 || ys.size() > 32767) {
+        mdt::set_error("mdtile_plan_create_wrap: too many tiles");
+        return nullptr;
+    }
+    const int cols = (int)xs.size(), rows = (int)ys.size();
+
+    mdtile_plan* p = new mdtile_plan();
+    p->wrap_x = wrap_x ? 1 : 0;
+    p->wrap_y = 1;
+    p->w = w; p->h = h; p->tw = tw; p->th = th; p->ov = ov;
+    p->cols = cols; p->rows = rows; p->T = cols * rows;
+    p->num_batches = (p->T + tile_bs - 1) / tile_bs;
+    p->tile_bs = (p->T + p->num_batches - 1) / p->num_batches;
+    // the block layout of mdtile_plan_create (mdt::plan_upload serves every kind): [xs | ys | colrange | rowrange | pad | colquad | rowinfo]
+    const int W4 = (w + 3) / 4;
+    const size_t head = (size_t)cols + rows + w + h;
+    p->quad_off = (head + 3) & ~(size_t)3;
+    p->table_len = p->quad_off + 4 * (size_t)W4 + 4 * (size_t)h;
+    p->h_table = new int[p->table_len]();
+    p->h_xs = p->h_table; memcpy(p->h_xs, xs.data(), xs.size() * sizeof(int));
+    p->h_ys = p->h_xs + cols; memcpy(p->h_ys, ys.data(), ys.size() * sizeof(int));
+    int* cr = p->h_ys + rows;
+    int* rr = cr + w;
+    int* cq = p->h_table + p->quad_off;
+    int* ri = cq + 4 * (size_t)W4;
+    p->nc_max = p->nr_max = 0;
+    std::vector<char> member(cols), qmember(cols);
+    for (int xq = 0; xq < W4; ++xq) {
+        std::fill(qmember.begin(), qmember.end(), 0);
+        for (int j = 0; j < 4 && 4 * xq + j < w; ++j) {
+            const int x = 4 * xq + j;
+            for (int c = 0; c < cols; ++c) {
+                member[c] = axis_covers(x, xs[c], tw, w, wrap_x != 0);
+                qmember[c] = qmember[c] || member[c];
+            }
+            cr[x] = cyclic_run(member);
+        }
+        cq[4 * xq] = cyclic_run(qmember);
+        if ((cq[4 * xq] >> 16) > p->nc_max) p->nc_max = cq[4 * xq] >> 16;
+    }
+    std::vector<char> rmember(rows);
+    for (int y = 0; y < h; ++y) {
+        for (int r = 0; r < rows; ++r) rmember[r] = axis_covers(y, ys[r], th, h, true);
+        rr[y] = ri[4 * y] = cyclic_run(rmember);
+        if ((rr[y] >> 16) > p->nr_max) p->nr_max = rr[y] >> 16;
+    }
+    p->d_xs = p->d_ys = p->d_colrange = p->d_rowrange = nullptr;
+    p->d_colquad = p->d_rowinfo = nullptr;
+    return p;
+}
+
+extern "C" int mdtile_plan_wrap_y(const mdtile_plan* p) { return p && p->wrap_y ? 1 : 0; }
+
 namespace mdt {
 int plan_upload(const mdtile_plan* cp) {
     mdtile_plan* p = const_cast<mdtile_plan*>(cp);

@@ -73,6 +73,8 @@ _SIGNATURES = {
     "mdtile_plan_create": (c_void_p, [c_int] * 7),
     "mdtile_plan_create_wrap_x": (c_void_p, [c_int] * 6),
     "mdtile_plan_wrap_x": (c_int, [c_void_p]),
+    "mdtile_plan_create_wrap": (c_void_p, [c_int] * 8),
+    "mdtile_plan_wrap_y": (c_int, [c_void_p]),
     "mdtile_plan_destroy": (None, [c_void_p]),
     "mdtile_plan_info": (c_int, [c_void_p, _IP]),
     "mdtile_plan_bboxes": (c_int, [c_void_p, _IP]),
@@ -283,14 +285,20 @@ def dtype_code(dt: torch.dtype) -> int:
 class Plan:
     """Grid plan == split_bboxes + init_grid_bbox (tile_utils/utils.py:160-177, abstractdiffusion.py:173-186).
     wrap_x: the canvas is closed in x (panoramas, mdtile_plan_create_wrap_x): tile columns lie on a circle, a box's x + w may pass the canvas
-    width (its columns are taken mod w), clamp is always on.  A tile as wide as the canvas raises MdtileError."""
+    width (its columns are taken mod w), clamp is always on.  A tile as wide as the canvas raises MdtileError.
+    wrap_y: the same for the rows (mdtile_plan_create_wrap); with wrap_x the canvas is a torus (seamless textures).  A box's y + h may pass the
+    canvas height; a tile as tall as the canvas raises MdtileError."""
 
-    def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True, wrap_x: bool = False):
+    def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True, wrap_x: bool = False,
+                 wrap_y: bool = False):
         L = lib()
-        self.wrap_x = bool(wrap_x)
-        if self.wrap_x:
-            if not clamp:
-                raise MdtileError("Plan(wrap_x=True) always clamps tile and overlap (clamp=False is not available)")
+        self.wrap_x, self.wrap_y = bool(wrap_x), bool(wrap_y)
+        if (self.wrap_x or self.wrap_y) and not clamp:
+            axes = "wrap_x=True" if not self.wrap_y else "wrap_y=True"
+            raise MdtileError(f"Plan({axes}) always clamps tile and overlap (clamp=False is not available)")
+        if self.wrap_y:
+            self._h = L.mdtile_plan_create_wrap(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(self.wrap_x), 1)
+        elif self.wrap_x:
             self._h = L.mdtile_plan_create_wrap_x(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs))
         else:
             self._h = L.mdtile_plan_create(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(clamp))

@@ -21,3 +21,8 @@ def preload(parser):
         help="Close the canvas horizontally (360-degree panoramas): Tiled Diffusion lays its tile columns on a circle, so that tiles span the seam "
              "between the right and the left edge, and Tiled VAE pads its input with the columns of the other edge instead of zeros. Not combined "
              "with region control. Default: off, the canvas is a strip with two ends.")
+    parser.add_argument(
+        "--mdtile-wrap-y", action="store_true",
+        help="Close the canvas vertically: tile rows on a circle, tiles span the seam between the bottom and the top edge, and Tiled VAE pads its "
+             "input with the rows of the other edge. With --mdtile-wrap-x the canvas is a torus (seamless textures that tile in both directions). "
+             "Not combined with region control. Default: off.")

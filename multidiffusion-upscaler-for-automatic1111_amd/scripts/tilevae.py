@@ -158,6 +158,12 @@ def _cmd_line_wrap_x() -> bool:
     return bool(getattr(shared.cmd_opts, "mdtile_wrap_x", False))
 
 
+def _cmd_line_wrap_y() -> bool:
+    """--mdtile-wrap-y (preload.py): the canvas is closed in y; False on a host that never heard of the option."""
+    import modules.shared as shared
+    return bool(getattr(shared.cmd_opts, "mdtile_wrap_y", False))
+
+
 def _cmd_line_devices(net) -> Optional[List[int]]:
     """--mdtile-devices (preload.py) for the hooks of `net` (the VAE's decoder); None when the option is not set."""
     import modules.shared as shared
@@ -213,15 +219,26 @@ class VAEHook:
                 self.net = self.net.to(devices.get_optimal_device())
             B, C, H, W = x.shape
             P = self.pad
-            if not (_cmd_line_wrap_x() and W > 2 * P):
+            # each axis decides for itself: a canvas no larger than two pads along one axis leaves that axis as it is
+            pad_x, pad_y = _cmd_line_wrap_x() and W > 2 * P, _cmd_line_wrap_y() and H > 2 * P
+            if not (pad_x or pad_y):
                 return self._forward(x)
             # the canvas closed in x: every conv would zero-pad at the left and right border; instead the input is padded by the tile pad
             # with the columns of the OTHER edge and runs through the unchanged path; the padding's share of the result is cut off again.
             # The columns next to the seam thus see their true neighbours up to P input px away -- the approximation every interior
-            # tile border already gets (upstream's pad of 11 latent / 32 image px).
-            out = self._forward(torch.cat([x[..., W - P:], x, x[..., :P]], dim=-1))
+            # tile border already gets (upstream's pad of 11 latent / 32 image px).  Closed in y: the same with rows, AFTER the columns, so
+            # that on a torus the corners of the padded input come from the diagonal neighbour.
+            if pad_x:
+                x = torch.cat([x[..., W - P:], x, x[..., :P]], dim=-1)
+            if pad_y:
+                x = torch.cat([x[..., H - P:, :], x, x[..., :P, :]], dim=-2)
+            out = self._forward(x)
             cut = 8 * P if self.is_decoder else P // 8
-            return out[..., cut:out.shape[-1] - cut].contiguous()
+            if pad_x:
+                out = out[..., cut:out.shape[-1] - cut]
+            if pad_y:
+                out = out[..., cut:out.shape[-2] - cut, :]
+            return out.contiguous()
         finally:
             self.net = self.net.to(original_device)
 

@@ -71,6 +71,9 @@ class AbstractDiffusion:
         # --mdtile-wrap-x: the canvas closed in x (init_grid_bbox); wrap_ext = columns by which the last tile column passes the right edge
         self.wrap_x = False
         self.wrap_ext = 0
+        # --mdtile-wrap-y: the same for the rows; wrap_ext_y = rows by which the last tile row passes the bottom edge.  Both: a torus
+        self.wrap_y = False
+        self.wrap_ext_y = 0
         self._wrap_copies: Dict[str, tuple] = {}
 
         # region prompt control
@@ -192,6 +195,11 @@ class AbstractDiffusion:
         """--mdtile-wrap-x (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_wrap_x", False))
 
+    @staticmethod
+    def wrap_y_requested() -> bool:
+        """--mdtile-wrap-y (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_wrap_y", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
         # clamps (tile <= canvas; overlap <= min(requested tile) - 4), origins and batching all happen in the plan
@@ -202,15 +210,26 @@ class AbstractDiffusion:
                       "itself across the seam; the plain grid is used.")
             else:
                 self.wrap_x = True
-        self.plan = mdtile.Plan(self.w, self.h, tile_w, tile_h, overlap, tile_bs, clamp=True, wrap_x=self.wrap_x)
+        self.wrap_y = False
+        if self.wrap_y_requested():      # each axis decides for itself: a tile as tall as the canvas drops wrap-y only
+            if min(int(tile_h), self.h) >= self.h:
+                print(f"[Tiled Diffusion] --mdtile-wrap-y ignored: the tile ({tile_h} latent px) is as tall as the canvas ({self.h}), it would meet "
+                      "itself across the seam; the rows of the plain grid are used.")
+            else:
+                self.wrap_y = True
+        self.plan = mdtile.Plan(self.w, self.h, tile_w, tile_h, overlap, tile_bs, clamp=True, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
         # wrap-x: tiles that span the seam end at x + w > W; the Python slices below cut them from a copy of their source that repeats its
         # first `wrap_ext` columns behind the last one (extended_x)
         self.wrap_ext = max((b[0] + b[2] - self.w for b in self.plan.bboxes), default=0) if self.wrap_x else 0
+        self.wrap_ext_y = max((b[1] + b[3] - self.h for b in self.plan.bboxes), default=0) if self.wrap_y else 0
         self._wrap_copies = {}
-        if self.wrap_x:
+        if self.wrap_x or self.wrap_y:
             if getattr(self.p, "extra_generation_params", None) is None:
                 self.p.extra_generation_params = {}
-            self.p.extra_generation_params["Tiled Diffusion wrap x"] = True
+            if self.wrap_x:
+                self.p.extra_generation_params["Tiled Diffusion wrap x"] = True
+            if self.wrap_y:
+                self.p.extra_generation_params["Tiled Diffusion wrap y"] = True
         self.tile_w, self.tile_h = self.plan.tile_w, self.plan.tile_h
         self.num_tiles, self.num_batches, self.tile_bs = self.plan.num_tiles, self.plan.num_batches, self.plan.tile_bs
         tile_weights = self.get_tile_weights()
@@ -220,20 +239,26 @@ class AbstractDiffusion:
     def extended_x(self, t: Tensor, slot: str, scale: int = 1) -> Tensor:
         """wrap-x: cat(t, t[..., :E]) with E = scale * wrap_ext, so that the slice / rectangle of a tile that spans the seam is contiguous in
         it (the columns past the right edge are the first ones again).  Built once per source tensor and kept under `slot` while the source
-        stays the same object with the same content version; any other plan returns t itself."""
-        E = self.wrap_ext * scale
-        if E <= 0:
+        stays the same object with the same content version; any other plan returns t itself.
+        wrap-y: the copy then gains its own first scale * wrap_ext_y rows behind the last one -- rows AFTER columns, so the corner block of a
+        tile that spans both seams is the source's top-left corner."""
+        E, Ey = self.wrap_ext * scale, self.wrap_ext_y * scale
+        if E <= 0 and Ey <= 0:
             return t
         hit = self._wrap_copies.get(slot)
         if hit is not None and hit[0] is t and hit[1] == t._version:
             return hit[2]
-        ext = torch.cat([t, t[..., :E]], dim=-1).contiguous()
+        ext = torch.cat([t, t[..., :E]], dim=-1) if E > 0 else t
+        if Ey > 0:
+            ext = torch.cat([ext, ext[..., :Ey, :]], dim=-2)
+        ext = ext.contiguous()
         self._wrap_copies[slot] = (t, t._version, ext)
         return ext
 
     def _refuse_wrap_x_with(self, what: str):
-        if self.wrap_x:
-            raise RuntimeError(f"[Tiled Diffusion] --mdtile-wrap-x cannot be combined with {what}: the wrap-around blend has no "
+        if self.wrap_x or self.wrap_y:
+            opts = " / ".join(o for o, on in (("--mdtile-wrap-x", self.wrap_x), ("--mdtile-wrap-y", self.wrap_y)) if on)
+            raise RuntimeError(f"[Tiled Diffusion] {opts} cannot be combined with {what}: the wrap-around blend has no "
                                "region path. Turn one of them off.")
 
     # ------------------------------------------------------------------------------------------------ regions

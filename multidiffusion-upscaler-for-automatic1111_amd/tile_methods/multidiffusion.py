@@ -93,7 +93,7 @@ class MultiDiffusion(AbstractDiffusion):
         tcond = self.repeat_tensor(self.get_tcond(cond_in), n)
         icond = self.get_icond(cond_in)
         if tuple(icond.shape[2:]) == (self.h, self.w):   # img2img: the image conditioning is tiled like the latent
-            icond = self.extended_x(icond, "icond")      # wrap-x: tiles that span the seam are contiguous in the extended copy
+            icond = self.extended_x(icond, "icond")      # wrap-x / wrap-y: tiles that span a seam are contiguous in the extended copy
             icond = torch.cat([icond[b.slicer] for b in bboxes], dim=0)
         else:
             icond = self.repeat_tensor(icond, n)

@@ -1,10 +1,11 @@
-"""A/B of the wrap-x blend (csrc/wrap.hip), one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache),
+"""A/B of the wrap-x and torus blends (csrc/wrap.hip), one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache),
 20 back-to-back launches per HIP-event pair, median of 7 rounds -- the method of DESIGN.md 3.4 / probes/blend_r6_ab.py -- at latent 1024^2,
 tile 128 / overlap 8 and tile 96 / overlap 48, N = 2, C = 4, fp32, MultiDiffusion:
+    torus      mdtile_blend on the plan closed in both axes (mdtile_plan_create_wrap: k_torus_blend)
     wrap-x     mdtile_blend on the wrap-x plan
     plain      mdtile_blend on the plain plan of the same canvas (what it dispatches: k_blend / k_blend_lds), batches handed over the same way
     copy       mdtile_stream_copy of the wrap-x launch's bytes: the floor of one launch of that size
-The wrap-x result is checked first against a torch restatement of the sequential `+=` loop on the device (bitwise).
+The torus and wrap-x results are checked first against a torch restatement of the sequential `+=` loop on the device (bitwise).
     python probes/wrap_ab.py            (on the GPU box; the shipping library)"""
 import os
 import sys
@@ -57,13 +58,24 @@ def restatement(plan, tiles, weights):
     flat = torch.cat(tiles, dim=0)
     for t, (x, y, w, h) in enumerate(plan.bboxes):
         cols = (x + torch.arange(w, device=dev)) % plan.w
-        buf[:, :, y:y + h, cols] += flat[t * N:(t + 1) * N]
+        rows = ((y + torch.arange(h, device=dev)) % plan.h)[:, None]
+        buf[:, :, rows, cols] += flat[t * N:(t + 1) * N]
     return torch.where(weights > 1, buf / weights, buf)
 
 
 for (L, tile, ov) in ((1024, 128, 8), (1024, 96, 48)):
     wplan, pplan = E.Plan(L, L, tile, tile, ov, 4, wrap_x=True), E.Plan(L, L, tile, tile, ov, 4)
-    print(f"{L}x{L} latent, tile {tile} overlap {ov}: wrap-x {wplan.cols} x {wplan.rows} tiles, plain {pplan.cols} x {pplan.rows}")
+    tplan = E.Plan(L, L, tile, tile, ov, 4, wrap_x=True, wrap_y=True)
+    print(f"{L}x{L} latent, tile {tile} overlap {ov}: torus {tplan.cols} x {tplan.rows} tiles, wrap-x {wplan.cols} x {wplan.rows}, "
+          f"plain {pplan.cols} x {pplan.rows}")
+    weights, tbytes, bufs, calls = setup(tplan)
+    got = calls[0]()
+    torch.cuda.synchronize()
+    same = torch.equal(got.view(torch.int32), restatement(tplan, bufs[0][0], weights).view(torch.int32))
+    print(f"  torus == sequential loop, bitwise: {same}")
+    report(f"torus ({tbytes / 1e6:.1f} MB, {len(bufs)} sets)", timed(calls), tbytes)
+    del bufs, calls
+    torch.cuda.empty_cache()
     weights, nbytes, bufs, calls = setup(wplan)
     got = calls[0]()
     torch.cuda.synchronize()

@@ -557,6 +557,31 @@ typedef struct mdtile_vae_tile {
 } mdtile_vae_tile;
 int mdtile_vae_assemble(const mdtile_vae_tile* tiles, int n_tiles, int N, int C, int is_decoder, float* d_result, int RH, int RW,
                         mdtile_stream_t stream);
+/* mdtile_vae_assemble with the tile borders cross-faded over the padding that crop_valid_region throws away (opt-in; upstream pastes
+ * edge to edge).  tiles: the rows x cols tiles of one call in row-major order, as mdtile_vae_split_tiles yields them; their out boxes
+ * partition the result as a tensor-product grid.
+ *   Band and weights.  band = b >= 1 output px.  At an interior vertical border at column X (the left tile's out_x2 == the right tile's
+ *     out_x1) the band is the columns x in [X - b, X + b) with the integer ramp through the pixel centres
+ *         aR(x) = 2 (x - X + b) + 1,   aL(x) = 4 b - aR(x)          (both odd, in [1, 4 b - 1], never zero);
+ *     a horizontal border at row Y has aB(y), aT(y) in the same way.
+ *   Outside every band: the owning tile's value, copied bit for bit -- there the image is mdtile_vae_assemble's (NaN payloads, -0.0
+ *     and denormals included).
+ *   In one band only: the two tiles on either side contribute with (aL, aR) or (aT, aB), D = 4 b.
+ *   In a column band and a row band: four tiles with aT aL, aT aR, aB aL, aB aR, D = 16 b^2 (b <= 1024: every weight < 2^24, exact in fp32).
+ *   A band pixel:  acc = +0.0f;  for the contributing tiles in ascending tile index: acc = acc + (float)w_k * v_k (product and sum each
+ *     rounded once; the library is built with -ffp-contract=off);  out = acc / (float)D (IEEE division).  v_k is read from tile k's
+ *     PADDED output at the pixel's position.
+ *   Legality, checked for the whole table before anything is launched (MDTILE_E_ARG, tile and reason in mdtile_last_error, nothing
+ *     written): the out boxes form the grid (shared borders, covering [0, RW) x [0, RH)); a tile next to a border is at least b wide
+ *     (tall) there and one with a border on both sides of an axis at least 2 b (bands may touch, not overlap); every tile's padded
+ *     output contains its out box grown by b on each side that has a neighbour (margins from in_bbox4 by the is_decoder rule of
+ *     mdtile_vae_assemble: in * 8 / in / 8); the peer, device and size checks of mdtile_vae_assemble.
+ * Every pixel of the result is written exactly once (no atomics, no read-modify-write: the result need not be zeroed); the table travels
+ * in the kernel arguments, each tile with its neighbours (MDTILE_VAE_BLEND_CHUNK tiles per launch): stream-ordered, no allocation, no
+ * host synchronisation, no host memory referenced after the call returns. */
+#define MDTILE_VAE_BLEND_CHUNK 16
+int mdtile_vae_assemble_blend(const mdtile_vae_tile* tiles, int rows, int cols, int N, int C, int is_decoder, int band, float* d_result,
+                              int RH, int RW, mdtile_stream_t stream);
 /* idempotent: kernels running on `device` may read memory of `peer` afterwards (MDTILE_E_ARG when the hardware cannot) */
 int mdtile_enable_peer_access(int device, int peer);
 

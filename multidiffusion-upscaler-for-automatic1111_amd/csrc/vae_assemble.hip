@@ -161,3 +161,229 @@ extern "C" int mdtile_vae_assemble(const mdtile_vae_tile* tiles, int n_tiles, in
     }
     return MDTILE_OK;
 }
+
+// ---- the assembly with cross-faded tile borders (include/mdtile.h: mdtile_vae_assemble_blend) --------------------------
+namespace {
+
+struct SeamSrc {
+    const float* p;   // element (0, 0) of plane 0 of the padded tile
+    long long off;    // index of image pixel (0, 0) in that plane: -(ty0 * pitch + tx0), (tx0, ty0) = the image position of element (0, 0)
+    int plane;        // th * tw
+    int pitch;        // tw
+};
+
+struct SeamTile {
+    SeamSrc s[9];     // the tile's 3 x 3 neighbourhood in the grid, row-major, itself at [4]; a neighbour that does not exist is never read
+    int ox0, oy0;     // out box origin
+    int cw, ch;       // out box: columns, rows
+    int nb;           // neighbours: bit 0 left, 1 right, 2 up, 3 down
+    int pad_;
+};
+
+struct SeamArgs {
+    SeamTile t[MDTILE_VAE_BLEND_CHUNK];
+    float* dst;
+    long long dst_plane;  // RH * RW
+    int dst_pitch;        // RW
+    int planes;           // N * C
+    int band;             // b
+};
+static_assert(sizeof(SeamArgs) <= 4096, "the table of one launch travels in the kernel arguments");
+
+// value of image pixel (x, row) in a source whose row starts at index `row` (SeamSrc::off + plane and row terms)
+__device__ __forceinline__ float seam_at(const SeamSrc& s, long long row, int x) { return s.p[row + x]; }
+
+// k_vae_assemble's structure: block (bx, t), its four waves take rows (plane, yy) of tile t's out box.  Per row the vertical partner (up,
+// down or none) and aT / aB are wave-uniform; the head band (b columns, left partner) and the tail band (b columns, right partner) blend
+// 2 or 4 sources per pixel; the columns between them are one source (k_vae_assemble's 16-byte non-temporal copy) or, on a row inside a
+// row band, two.  Sums in ascending tile index: (up, left) < (up, right) < (down, left) < (down, right).
+__global__ __launch_bounds__(256) void k_vae_seam_blend(const SeamArgs a) {
+    const SeamTile& t = a.t[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = a.band;
+    const int rows = a.planes * t.ch;
+    const int nwaves = gridDim.x * 4;
+    const int hb = (t.nb & 1) ? b : 0, tb = (t.nb & 2) ? b : 0;   // columns of the head / tail band
+    const int cm = t.cw - hb - tb;                                // columns between them (>= 0: the bands fit the tile)
+    const float d2 = (float)(4 * b), d4 = (float)(16 * b * b);
+    for (int r = blockIdx.x * 4 + wave; r < rows; r += nwaves) {
+        const int p = r / t.ch, yy = r - p * t.ch;     // one division per row
+        const int y = t.oy0 + yy;
+        // the row band this row lies in: grid rows (rT, rB) of the neighbourhood with weights (aT, aB); aB == 0: none
+        int rT = 1, rB = 1, aB = 0;
+        if ((t.nb & 4) && yy < b) {
+            rT = 0;
+            aB = 2 * (yy + b) + 1;
+        } else if ((t.nb & 8) && yy >= t.ch - b) {
+            rB = 2;
+            aB = 2 * (yy - t.ch + b) + 1;
+        }
+        const int aT = 4 * b - aB;
+        const SeamSrc* sT = t.s + 3 * rT;
+        const SeamSrc* sB = t.s + 3 * rB;
+        long long oT[3], oB[3];                        // row starts in the (left, middle, right) source of the upper / lower grid row
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            oT[c] = (long long)p * sT[c].plane + sT[c].off + (long long)y * sT[c].pitch;
+            oB[c] = (long long)p * sB[c].plane + sB[c].off + (long long)y * sB[c].pitch;
+        }
+        float* d = a.dst + (size_t)p * a.dst_plane + (size_t)y * a.dst_pitch + t.ox0;
+        // head band (cL = 0: columns 0, 1 of the neighbourhood) and tail band (cL = 1: columns 1, 2)
+#pragma unroll
+        for (int cL = 0; cL < 2; ++cL) {
+            const int n = cL ? tb : hb, x0 = cL ? t.cw - tb : 0;
+            for (int j = lane; j < n; j += 64) {
+                const int xx = x0 + j, x = t.ox0 + xx;
+                const int aR = 2 * (j + (cL ? 0 : b)) + 1, aL = 4 * b - aR;
+                float acc = 0.0f;
+                if (aB == 0) {
+                    acc = acc + (float)aL * seam_at(sT[cL], oT[cL], x);
+                    acc = acc + (float)aR * seam_at(sT[cL + 1], oT[cL + 1], x);
+                    d[xx] = acc / d2;
+                } else {
+                    acc = acc + (float)(aT * aL) * seam_at(sT[cL], oT[cL], x);
+                    acc = acc + (float)(aT * aR) * seam_at(sT[cL + 1], oT[cL + 1], x);
+                    acc = acc + (float)(aB * aL) * seam_at(sB[cL], oB[cL], x);
+                    acc = acc + (float)(aB * aR) * seam_at(sB[cL + 1], oB[cL + 1], x);
+                    d[xx] = acc / d4;
+                }
+            }
+        }
+        if (aB != 0) {                                 // between the bands, inside a row band: the tiles above and below
+            for (int j = lane; j < cm; j += 64) {
+                const int xx = hb + j, x = t.ox0 + xx;
+                float acc = 0.0f;
+                acc = acc + (float)aT * seam_at(sT[1], oT[1], x);
+                acc = acc + (float)aB * seam_at(sB[1], oB[1], x);
+                d[xx] = acc / d2;
+            }
+            continue;
+        }
+        // between the bands, in no row band: k_vae_assemble's copy of the tile's own columns [hb, cw - tb)
+        const float* s = t.s[4].p + (oT[1] + t.ox0 + hb);
+        d += hb;
+        int head = (int)((16 - (reinterpret_cast<size_t>(d) & 15)) & 15) >> 2;
+        head = head < cm ? head : cm;
+        if (lane < head) d[lane] = s[lane];
+        const float* sb = s + head;
+        float* db = d + head;
+        const int n4 = (cm - head) >> 2;
+        const f32x4* sv = reinterpret_cast<const f32x4*>(sb);
+        f32x4* dv = reinterpret_cast<f32x4*>(db);
+        if ((reinterpret_cast<size_t>(sb) & 15) == 0) {
+            for (int j = lane; j < n4; j += 256) {
+                f32x4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (j + u * 64 < n4) v[u] = __builtin_nontemporal_load(sv + j + u * 64);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (j + u * 64 < n4) __builtin_nontemporal_store(v[u], dv + j + u * 64);
+            }
+        } else {
+            for (int j = lane; j < n4; j += 64) {
+                const float* q = sb + 4 * j;
+                f32x4 v = {q[0], q[1], q[2], q[3]};
+                __builtin_nontemporal_store(v, dv + j);
+            }
+        }
+        const int tail = (cm - head) & 3;
+        if (lane < tail) db[4 * n4 + lane] = sb[4 * n4 + lane];
+    }
+}
+
+}  // namespace
+
+extern "C" int mdtile_vae_assemble_blend(const mdtile_vae_tile* tiles, int rows, int cols, int N, int C, int is_decoder, int band,
+                                         float* d_result, int RH, int RW, mdtile_stream_t stream) {
+    MDT_CHECK_ARG(tiles && d_result && rows > 0 && cols > 0 && N > 0 && C > 0 && RH > 0 && RW > 0, "mdtile_vae_assemble_blend: bad arguments");
+    MDT_CHECK_ARG((long long)rows * cols <= 0x7fffffff, "mdtile_vae_assemble_blend: %d x %d tiles", rows, cols);
+    MDT_CHECK_ARG(band >= 1 && band <= 1024, "mdtile_vae_assemble_blend: band %d is not in 1 .. 1024", band);
+    int cur = 0;
+    MDT_HIP(hipGetDevice(&cur));
+    MDT_CHECK_ARG(device_of(d_result) == cur, "mdtile_vae_assemble_blend: the result is not device memory of the calling device %d", cur);
+    const int n_tiles = rows * cols;
+    auto margin = [&](const mdtile_vae_tile& t, int k) { return t.out_bbox4[k] - (is_decoder ? t.in_bbox4[k] * 8 : t.in_bbox4[k] / 8); };
+    // validate the whole table (and map every source device) before the first launch: an error return leaves the image untouched
+    unsigned long long peers_ok = 0;   // bit d: device d's memory is readable from here
+    for (int i = 0; i < n_tiles; ++i) {
+        const mdtile_vae_tile& t = tiles[i];
+        const int gr = i / cols, gc = i - gr * cols;
+        MDT_CHECK_ARG(t.tile && t.th > 0 && t.tw > 0, "mdtile_vae_assemble_blend: tile %d: bad arguments", i);
+        int m[4];
+        for (int k = 0; k < 4; ++k) m[k] = margin(t, k);
+        const int cw = t.tw + m[1] - m[0], ch = t.th + m[3] - m[2];
+        MDT_CHECK_ARG(m[0] >= 0 && m[2] >= 0 && m[1] <= 0 && m[3] <= 0 && cw > 0 && ch > 0,
+                      "mdtile_vae_assemble_blend: tile %d: inconsistent bboxes (margins %d %d %d %d)", i, m[0], m[1], m[2], m[3]);
+        MDT_CHECK_ARG(cw == t.out_bbox4[1] - t.out_bbox4[0] && ch == t.out_bbox4[3] - t.out_bbox4[2],
+                      "mdtile_vae_assemble_blend: tile %d: crop %dx%d != target window %dx%d", i, cw, ch, t.out_bbox4[1] - t.out_bbox4[0],
+                      t.out_bbox4[3] - t.out_bbox4[2]);
+        // the grid: column borders as row 0 has them, row borders as column 0 has them, from 0 to the result's size
+        const int* o = t.out_bbox4;
+        const int* o_col = tiles[gc].out_bbox4;
+        const int* o_row = tiles[gr * cols].out_bbox4;
+        MDT_CHECK_ARG(o[0] == o_col[0] && o[1] == o_col[1] && o[2] == o_row[2] && o[3] == o_row[3] &&
+                          o[0] == (gc == 0 ? 0 : tiles[i - 1].out_bbox4[1]) && o[2] == (gr == 0 ? 0 : tiles[i - cols].out_bbox4[3]) &&
+                          (gc < cols - 1 || o[1] == RW) && (gr < rows - 1 || o[3] == RH),
+                      "mdtile_vae_assemble_blend: tile %d: out box x %d..%d y %d..%d does not lie on the %d x %d grid over the %d x %d result "
+                      "(hole or overlap)", i, o[0], o[1], o[2], o[3], rows, cols, RW, RH);
+        const int nbx = (gc > 0) + (gc < cols - 1), nby = (gr > 0) + (gr < rows - 1);
+        MDT_CHECK_ARG(cw >= band * nbx, "mdtile_vae_assemble_blend: tile %d: %d px wide, %s", i, cw,
+                      nbx == 2 && cw >= band ? "its two column bands overlap" : "the band is wider than the tile");
+        MDT_CHECK_ARG(ch >= band * nby, "mdtile_vae_assemble_blend: tile %d: %d px tall, %s", i, ch,
+                      nby == 2 && ch >= band ? "its two row bands overlap" : "the band is taller than the tile");
+        MDT_CHECK_ARG((gc == 0 || m[0] >= band) && (gc == cols - 1 || -m[1] >= band) && (gr == 0 || m[2] >= band) &&
+                          (gr == rows - 1 || -m[3] >= band),
+                      "mdtile_vae_assemble_blend: tile %d: margin smaller than the band %d (margins %d %d %d %d)", i, band, m[0], -m[1], m[2], -m[3]);
+        MDT_CHECK_ARG((long long)N * C * ch <= 0x7fffffff && (long long)t.th * t.tw <= 0x7fffffff, "mdtile_vae_assemble_blend: tile %d too large", i);
+        const int dev = device_of(t.tile);
+        MDT_CHECK_ARG(dev >= 0 && dev < 64, "mdtile_vae_assemble_blend: tile %d is not device memory", i);
+        if (dev != cur && !(peers_ok >> dev & 1)) {
+            const int rc = mdtile_enable_peer_access(cur, dev);
+            if (rc != MDTILE_OK) return rc;
+            peers_ok |= 1ull << dev;
+        }
+    }
+    hipStream_t s = as_stream(stream);
+    SeamArgs a;
+    a.dst = d_result;
+    a.dst_plane = (long long)RH * RW;
+    a.dst_pitch = RW;
+    a.planes = N * C;
+    a.band = band;
+    for (int c0 = 0; c0 < n_tiles; c0 += MDTILE_VAE_BLEND_CHUNK) {
+        const int nt = n_tiles - c0 < MDTILE_VAE_BLEND_CHUNK ? n_tiles - c0 : MDTILE_VAE_BLEND_CHUNK;
+        long long max_rows = 0;
+        for (int k = 0; k < nt; ++k) {
+            const int i = c0 + k, gr = i / cols, gc = i - gr * cols;
+            SeamTile& q = a.t[k];
+            q.nb = (gc > 0 ? 1 : 0) | (gc < cols - 1 ? 2 : 0) | (gr > 0 ? 4 : 0) | (gr < rows - 1 ? 8 : 0);
+            q.pad_ = 0;
+            for (int dr = -1; dr <= 1; ++dr)
+                for (int dc = -1; dc <= 1; ++dc) {
+                    const int nr = gr + dr, nc = gc + dc;
+                    const bool there = nr >= 0 && nr < rows && nc >= 0 && nc < cols;
+                    const mdtile_vae_tile& t = tiles[there ? nr * cols + nc : i];
+                    SeamSrc& src = q.s[3 * (dr + 1) + dc + 1];
+                    src.p = t.tile;
+                    src.plane = t.th * t.tw;
+                    src.pitch = t.tw;
+                    src.off = -((long long)(t.out_bbox4[2] - margin(t, 2)) * t.tw + (t.out_bbox4[0] - margin(t, 0)));
+                }
+            const mdtile_vae_tile& t = tiles[i];
+            q.ox0 = t.out_bbox4[0];
+            q.oy0 = t.out_bbox4[2];
+            q.cw = t.out_bbox4[1] - t.out_bbox4[0];
+            q.ch = t.out_bbox4[3] - t.out_bbox4[2];
+            const long long nrows = (long long)N * C * q.ch;
+            max_rows = nrows > max_rows ? nrows : max_rows;
+        }
+        // about 2048 blocks (8 per CU) over the chunk; a tile never gets more blocks than it has 4-row groups
+        long long bx = (max_rows + 3) / 4, cap = 2048 / nt;
+        bx = bx < cap ? bx : cap;
+        hipLaunchKernelGGL(k_vae_seam_blend, dim3((unsigned)(bx > 0 ? bx : 1), nt), dim3(256), 0, s, a);
+        MDT_LAUNCH_CHECK();
+    }
+    return MDTILE_OK;
+}

@@ -36,6 +36,7 @@ ATTN_EXACT_F32 = 1
 ATTN_V_CHANNEL_MAJOR = 2
 MAX_BATCHES, MAX_REGIONS = 320, 16
 VAE_ASSEMBLE_CHUNK = 32
+VAE_BLEND_CHUNK = 16
 
 _DTYPES = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 
@@ -174,6 +175,7 @@ _SIGNATURES = {
     "mdtile_vae_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "mdtile_crop_store": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _IP, _IP, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_vae_assemble": (c_int, [POINTER(_VaeTile), c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "mdtile_vae_assemble_blend": (c_int, [POINTER(_VaeTile), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_enable_peer_access": (c_int, [c_int, c_int]),
     "mdtile_vae_fast_size": (c_int, [c_int, c_int, c_int, _IP, _IP]),
     "mdtile_vae_fast_ws_size": (c_size_t, [c_int]),
@@ -1289,6 +1291,25 @@ def vae_assemble(tiles: Sequence[Tuple[torch.Tensor, Sequence[int], Sequence[int
             raise MdtileError(f"tiles[{k}] has shape {tuple(t.shape)}, the result {tuple(result.shape)}")
         table[k] = _VaeTile(t.data_ptr(), t.shape[2], t.shape[3], (c_int * 4)(*ib), (c_int * 4)(*ob))
     _check(lib().mdtile_vae_assemble(table, len(tiles), N, C, int(is_decoder), _p(result), RH, RW, _stream()), "mdtile_vae_assemble")
+
+
+def vae_assemble_blend(tiles: Sequence[Tuple[torch.Tensor, Sequence[int], Sequence[int]]], rows: int, cols: int, result: torch.Tensor, band: int,
+                       is_decoder: bool = True) -> None:
+    """vae_assemble with the tile borders cross-faded over `band` output px per side (include/mdtile.h: mdtile_vae_assemble_blend): the
+    rows x cols tiles of one call in row-major order, each read in its padded extent.  Every pixel of `result` is written once (it need not
+    be zeroed).  MdtileError, and nothing written, when the grid does not admit the band."""
+    _dev_tensor(result, "result", torch.float32)
+    N, C, RH, RW = result.shape
+    if rows < 1 or cols < 1 or len(tiles) != rows * cols:
+        raise MdtileError(f"vae_assemble_blend: {len(tiles)} tiles are no {rows} x {cols} grid")
+    table = (_VaeTile * len(tiles))()
+    for k, (t, ib, ob) in enumerate(tiles):
+        _dev_tensor(t, f"tiles[{k}]", torch.float32)
+        if tuple(t.shape[:2]) != (N, C):
+            raise MdtileError(f"tiles[{k}] has shape {tuple(t.shape)}, the result {tuple(result.shape)}")
+        table[k] = _VaeTile(t.data_ptr(), t.shape[2], t.shape[3], (c_int * 4)(*ib), (c_int * 4)(*ob))
+    _check(lib().mdtile_vae_assemble_blend(table, int(rows), int(cols), N, C, int(is_decoder), int(band), _p(result), RH, RW, _stream()),
+           "mdtile_vae_assemble_blend")
 
 
 def enable_peer_access(device: int, peer: int) -> None:

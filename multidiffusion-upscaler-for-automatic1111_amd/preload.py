@@ -26,3 +26,8 @@ def preload(parser):
         help="Close the canvas vertically: tile rows on a circle, tiles span the seam between the bottom and the top edge, and Tiled VAE pads its "
              "input with the rows of the other edge. With --mdtile-wrap-x the canvas is a torus (seamless textures that tile in both directions). "
              "Not combined with region control. Default: off.")
+    parser.add_argument(
+        "--mdtile-vae-seam-blend", type=int, default=None, metavar="PX",
+        help="Tiled VAE decoder: cross-fade neighbouring tiles over PX image pixels per side of a tile border (1-88; 16-32 is a sensible range), out "
+             "of the padding that is otherwise decoded and thrown away, instead of pasting the tiles edge to edge. Every decoded tile is kept "
+             "until the image is assembled. Default: not set, edge to edge.")

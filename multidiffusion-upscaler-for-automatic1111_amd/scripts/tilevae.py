@@ -182,6 +182,58 @@ def _cmd_line_devices(net) -> Optional[List[int]]:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# cross-faded tile borders (preload.py: --mdtile-vae-seam-blend)
+# ---------------------------------------------------------------------------------------------------------------------
+SEAM_BLEND_MAX = 88      # the decoder's padding: 11 latent px
+
+
+def seam_grid(in_bboxes, out_bboxes, RH: int, RW: int, band: int, is_decoder: bool = True):
+    """The legality rules of mdtile_vae_assemble_blend (include/mdtile.h) on the host, for tiles whose padded output is their input bbox
+    scaled: ((rows, cols), None) when the row-major tile list is a grid that admits `band` px per side of every border, else
+    (None, reason).  Pure."""
+    n = len(out_bboxes)
+    if band < 1:
+        return None, f"band {band} is smaller than 1"
+    if n == 0 or len(in_bboxes) != n:
+        return None, "no tiles"
+    cols = next((i for i in range(1, n) if out_bboxes[i][2] != out_bboxes[0][2]), n)
+    rows = n // cols
+    if rows * cols != n:
+        return None, f"{n} tiles are no grid of {cols} columns"
+    for i, (ib, ob) in enumerate(zip(in_bboxes, out_bboxes)):
+        r, c = divmod(i, cols)
+        oc, orow = out_bboxes[c], out_bboxes[r * cols]
+        if not (ob[0] == oc[0] and ob[1] == oc[1] and ob[2] == orow[2] and ob[3] == orow[3]
+                and ob[0] == (0 if c == 0 else out_bboxes[i - 1][1]) and ob[2] == (0 if r == 0 else out_bboxes[i - cols][3])
+                and (c < cols - 1 or ob[1] == RW) and (r < rows - 1 or ob[3] == RH) and ob[1] > ob[0] and ob[3] > ob[2]):
+            return None, f"tile {i}: its out box {tuple(ob)} does not lie on the {rows} x {cols} grid (hole or overlap)"
+        nbx, nby = (c > 0) + (c < cols - 1), (r > 0) + (r < rows - 1)
+        w, h = ob[1] - ob[0], ob[3] - ob[2]
+        if w < band * nbx:
+            return None, f"tile {i}: {w} px wide, " + ("its two column bands overlap" if nbx == 2 and w >= band else "the band is wider than the tile")
+        if h < band * nby:
+            return None, f"tile {i}: {h} px tall, " + ("its two row bands overlap" if nby == 2 and h >= band else "the band is taller than the tile")
+        m = [ob[k] - (ib[k] * 8 if is_decoder else ib[k] // 8) for k in range(4)]
+        if m[0] < 0 or m[2] < 0 or m[1] > 0 or m[3] > 0:
+            return None, f"tile {i}: inconsistent bboxes (margins {m})"
+        if (c > 0 and m[0] < band) or (c < cols - 1 and -m[1] < band) or (r > 0 and m[2] < band) or (r < rows - 1 and -m[3] < band):
+            return None, f"tile {i}: margin smaller than the band {band} (margins {m[0]} {-m[1]} {m[2]} {-m[3]})"
+    return (rows, cols), None
+
+
+def _cmd_line_seam_blend() -> Optional[int]:
+    """--mdtile-vae-seam-blend (preload.py): image px per side of a tile border, or None (not set, or out of range: one line)."""
+    import modules.shared as shared
+    value = getattr(shared.cmd_opts, "mdtile_vae_seam_blend", None)
+    if value is None:
+        return None
+    if not isinstance(value, int) or isinstance(value, bool) or not 1 <= value <= SEAM_BLEND_MAX:
+        print(f"[Tiled VAE]: --mdtile-vae-seam-blend {value!r} is not in 1 .. {SEAM_BLEND_MAX} image px; the option is ignored")
+        return None
+    return value
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 class VAEHook:
 
     def __init__(self, net, tile_size, is_decoder: bool, fast_decoder: bool, fast_encoder: bool, color_fix: bool,
@@ -211,6 +263,10 @@ class VAEHook:
         # slot).  A device may fill several slots (functional runs on one GPU).
         self.devices: Optional[List[int]] = None
         self.last_tile_slots: Optional[List[int]] = None    # the slot that decoded each tile in the last call
+        # decoder only (preload.py: --mdtile-vae-seam-blend): cross-fade every tile border over this many image px per side, out of the
+        # padding crop_valid_region throws away (mdtile_vae_assemble_blend).  Every finished tile then lives until the assembly (at 8K /
+        # tile 256 about 16 x 59 MB).  0: upstream's edge-to-edge paste, nothing below changes.
+        self.seam_blend: int = 0
 
     def __call__(self, x):
         original_device = next(self.net.parameters()).device
@@ -471,16 +527,17 @@ class VAEHook:
             b0 = b1
         return out
 
-    def _live_plan(self, steps: List[Step], in_bbox, out_bbox):
+    def _live_plan(self, steps: List[Step], in_bbox, out_bbox, grow=(0, 0, 0, 0)):
         """(windows, narrowed input bbox) of one decoder tile for _run_tile_rec / crop_store -- ({}, in_bbox) when live-window narrowing does
-        not apply (switched off, encoder)."""
+        not apply (switched off, encoder).  grow (left, right, top, bottom; latent px): the valid rectangle grown by what the cross-faded
+        assembly reads beyond the out box (seam_blend), clamped to the tile -- narrowing is exact for the rectangle it is given."""
         if not (LIVE_WINDOW and self.is_decoder):
             return {}, tuple(in_bbox)
         x1, x2, y1, y2 = in_bbox
         ox1, ox2, oy1, oy2 = out_bbox
         if any(v % 8 for v in (ox1, ox2, oy1, oy2)):
             return {}, tuple(in_bbox)
-        valid = (oy1 // 8 - y1, ox1 // 8 - x1, oy2 // 8 - y1, ox2 // 8 - x1)
+        valid = (max(oy1 // 8 - y1 - grow[2], 0), max(ox1 // 8 - x1 - grow[0], 0), min(oy2 // 8 - y1 + grow[3], y2 - y1), min(ox2 // 8 - x1 + grow[1], x2 - x1))
         windows, (ry0, rx0, ry1, rx1) = live_windows(steps, (y2 - y1, x2 - x1), valid)
         return windows, (x1 + rx0, x1 + rx1, y1 + ry0, y1 + ry1)
 
@@ -604,6 +661,16 @@ class VAEHook:
             self.nan_flags = []
             self.live = {}          # tile -> (windows of its upsample convs, the input bbox of what is left of it): live_windows
             self.interrupted = False
+            self.seam = None        # (band, rows, cols) when this call's tiles are kept for mdtile_vae_assemble_blend (VAEHook.seam_blend)
+
+        def seam_grow(self, i: int):
+            """Latent px by which tile i's valid rectangle grows on (left, right, top, bottom): ceil(band / 8) where it has a neighbour."""
+            if self.seam is None:
+                return (0, 0, 0, 0)
+            band, rows, cols = self.seam
+            r, c = divmod(i, cols)
+            g = -(-band // 8)
+            return (g if c > 0 else 0, g if c < cols - 1 else 0, g if r > 0 else 0, g if r < rows - 1 else 0)
 
         def gather(self, i: int) -> Tensor:
             """The input of tile i, cut out of z."""
@@ -635,7 +702,7 @@ class VAEHook:
                  for i, (var, mean) in zip(norm_ord, frozen)]
         if use_rec:
             for i in lane.mine:
-                lane.live[i] = self._live_plan(steps, lane.in_bboxes[i], lane.out_bboxes[i])
+                lane.live[i] = self._live_plan(steps, lane.in_bboxes[i], lane.out_bboxes[i], lane.seam_grow(i))
         if use_rec and TILE_BATCH > 1:
             # Tiles of one shape go through the sweep TOGETHER (stacked along the batch axis, TILE_BATCH at a time).  Upstream
             # walks them one by one (:578-642); with frozen statistics they are independent, so the result is the same -- but
@@ -802,6 +869,16 @@ class VAEHook:
         slots = self._slots(dev)
         if slots and world > 1:
             raise RuntimeError("[Tiled VAE]: VAEHook.devices (one process, several devices) and a process-per-GPU shard cannot be combined")
+        seam = None
+        if self.seam_blend and self.is_decoder and len(in_bboxes) > 1:
+            if world > 1:
+                raise RuntimeError("[Tiled VAE]: VAEHook.seam_blend (cross-faded tile borders) and a process-per-GPU shard (VAEHook.shard) cannot "
+                                   "be combined: the root would need its neighbours' padding")
+            grid, why = seam_grid(in_bboxes, out_bboxes, height * 8, width * 8, int(self.seam_blend), True)
+            if grid is None:
+                print(f"[Tiled VAE]: seam blend of {self.seam_blend} px does not fit this tile grid ({why}); tiles are pasted edge to edge")
+            else:
+                seam = (int(self.seam_blend), *grid)
 
         frozen = None
         if self.fast_mode:
@@ -827,7 +904,9 @@ class VAEHook:
                 lane_steps = steps if k == 0 else self._slot_program(d.index)
                 lane_frozen = frozen if k == 0 or frozen is None else [(v.to(d), m.to(d)) for v, m in frozen]
                 mine = [i for i, o in enumerate(owner) if o == (k if slots else rank)]
-                lanes.append(VAEHook._Lane(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, mine, lane_steps, lane_frozen, keep_tiles=bool(slots)))
+                lanes.append(VAEHook._Lane(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, mine, lane_steps, lane_frozen,
+                                           keep_tiles=bool(slots) or seam is not None))
+                lanes[-1].seam = seam
         if all_frozen:
             sweeps = [(lane, self._sweep_frozen(lane)) for lane in lanes]
             while sweeps:                                # one chunk of every lane per round: no device waits while another's list is issued
@@ -856,7 +935,16 @@ class VAEHook:
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(lane.device))
                     torch.cuda.current_stream(dev).wait_event(ev)
-            if kept:
+            seam = lanes[0].seam
+            if kept and seam is not None and (interrupted or len(kept) != len(owner)):
+                print(f"[Tiled VAE]: interrupted with {len(kept)} of {len(owner)} tiles finished; no seam blend, the finished tiles are pasted edge to edge")
+                seam = None
+            if kept and seam is not None:
+                # (the lanes finish their tiles in their own order: row-major again, as the grid wants them)
+                kept.sort(key=lambda t: (t[2][2], t[2][0]))
+                result = torch.empty(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
+                self.engine.vae_assemble_blend(kept, seam[1], seam[2], result, seam[0], self.is_decoder)
+            elif kept:
                 result = torch.zeros(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
                 self.engine.vae_assemble(kept, result, self.is_decoder)
             flags = [f.to(dev) for lane in lanes for f in lane.nan_flags]
@@ -958,6 +1046,10 @@ class Script(scripts.Script):
         decoder.forward = VAEHook(decoder, decoder_tile_size, is_decoder=True, fast_decoder=fast_decoder,
                                   fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)
         decoder.forward.devices = None if slots is None else list(slots)
+        seam_px = _cmd_line_seam_blend()
+        if seam_px is not None:                 # the decoder only: the encoder's 4 latent px of padding leave no ramp worth having
+            decoder.forward.seam_blend = seam_px
+            p.extra_generation_params["Tiled VAE seam blend"] = seam_px
         encoder = vae.encoder
         if not hasattr(encoder, "original_forward"):
             encoder.original_forward = encoder.forward

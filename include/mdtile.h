@@ -103,8 +103,9 @@ int mdtile_plan_bboxes(const mdtile_plan* plan, int* xywh);
  *   cols = ceil(w / (tw - ov));  x_c = (int)(c * (double)w / cols);  tile c covers the columns (x_c + i) mod w, i in [0, tw)
  *   the origin stride w / cols is at most tw - ov: cyclic neighbours overlap by at least ov everywhere, the seam included
  *   effective tw >= w: NULL + mdtile_last_error (a tile would meet itself)
+ * It is mdtile_plan_create_wrap(..., wrap_x = 1, wrap_y = 0) under its first name.
  * mdtile_plan_info / mdtile_plan_bboxes work on such a plan; a box reports x_c, so x_c + tw may exceed w.  mdtile_plan_wrap_x: 1 for such a plan, else 0.
- * mdtile_weight_map_add_grid, mdtile_gather, mdtile_gather_all and mdtile_blend take a wrap-x plan (kernels of their own, csrc/wrap.hip): column
+ * mdtile_weight_map_add_grid, mdtile_gather, mdtile_gather_all and mdtile_blend take a wrap-x plan (the per-axis kernels of csrc/wrap.hip): column
  * indices mod w, the covering tiles summed in ascending tile index -- at a seam pixel tile column 0 before column cols-1 -- so results equal the
  * sequential `+=` loop over the tile list bit for bit.  REFUSED on a wrap-x plan (MDTILE_E_ARG, the text names the reason): num_regions > 0, any
  * MDTILE_BLEND_* flag, a row band, mdtile_gather_range, mdtile_blend_finalize, the packed destination of mdtile_gather_all, mdtile_blend_dispatch. */
@@ -114,7 +115,7 @@ int mdtile_plan_wrap_x(const mdtile_plan* plan);
  *   tile and overlap clamp, batching and tile order (row-major, y outer): as mdtile_plan_create(clamp = 1)
  *   a wrapped axis uses the circle rule of the wrap-x columns: rows = ceil(h / (th - ov));  y_r = (int)(r * (double)h / rows);  tile row r covers
  *   the rows (y_r + i) mod h, i in [0, th); a box reports y_r, so y_r + th may exceed h.  An unwrapped axis keeps the plain origins.
- *   (wrap_x, wrap_y) = (1, 0): exactly the plan of mdtile_plan_create_wrap_x.   (0, 0): NULL + mdtile_last_error (use mdtile_plan_create).
+ *   (wrap_x, wrap_y) = (1, 0): the plan of mdtile_plan_create_wrap_x, as specified above.   (0, 0): NULL + mdtile_last_error (use mdtile_plan_create).
  *   effective tw >= w on a wrapped x, th >= h on a wrapped y: NULL + mdtile_last_error, the text names the axis.
  * mdtile_plan_wrap_x / mdtile_plan_wrap_y: 1 when that axis of the plan wraps, else 0.
  * Everything said above of a wrap-x plan holds for a plan with wrap_y: the same calls take it (both indices mod the canvas, the covering tiles

@@ -142,14 +142,12 @@ struct mdtile_plan {
     //   rowinfo[y]   = { first | count << 16 of the tile rows covering y,               ys[first], ys[first+1], ys[first+2] }
     int4 *d_colquad, *d_rowinfo;
     int nc_max, nr_max;       // most tile columns covering one 4-px quad / most tile rows covering one canvas row (blend kernel dispatch)
-    // mdtile_plan_create_wrap_x: the canvas is closed in x.  xs[c] + tw may pass w (tile c covers the columns (xs[c] + i) mod w); the covering
-    // tile columns of a canvas column / of a quad are a CYCLIC run: colrange[x] and colquad[x/4].x hold first | count << 16 with `first` the
-    // run's start on the circle (first + count may pass cols: the run goes on at column 0); colquad's .y .z .w are unused.  Rows as above.
-    int wrap_x;
-    // mdtile_plan_create_wrap with wrap_y: the canvas is closed in y as well (a torus) or in y alone.  ys[r] + th may pass h (tile row r covers
-    // the rows (ys[r] + i) mod h); rowrange[y] and rowinfo[y].x hold the CYCLIC run of the row list, as above; rowinfo's .y .z .w are unused.
-    // With wrap_x == 0 the columns are plain (origins_1d) and their runs never pass cols.
-    int wrap_y;
+    // mdtile_plan_create_wrap: the canvas is closed in x (wrap_x), in y (wrap_y) or in both (a torus).  On a wrapped x axis xs[c] + tw may pass
+    // w (tile c covers the columns (xs[c] + i) mod w) and the covering tile columns of a canvas column / of a quad are a CYCLIC run: colrange[x]
+    // and colquad[x/4].x hold first | count << 16 with `first` the run's start on the circle (first + count may pass cols: the run goes on at
+    // column 0).  Likewise ys[r] + th, rowrange[y] and rowinfo[y].x on a wrapped y axis.  An axis that does not wrap keeps the plain origins
+    // (origins_1d) and its runs never pass the end of the list.  Whenever either flag is set the .y .z .w of BOTH records are unused (zero).
+    int wrap_x, wrap_y;
 };
 
 namespace mdt {

@@ -7,8 +7,8 @@
 
 namespace mdt {
 
-// ---- wrap.hip: wrap-x, wrap-y and torus plans (mdtile_plan_create_wrap_x / mdtile_plan_create_wrap); the public entry points hand such a plan
-// (mdt::plan_wraps) to these launchers
+// ---- wrap.hip: wrap-x, wrap-y and torus plans (mdtile_plan_create_wrap), one kernel set for all three; the public entry points hand such a
+// plan (mdt::plan_wraps) to these launchers
 int wrap_weight_map(const struct ::mdtile_plan* plan, const float* d_tile_w, float* d_weights, hipStream_t s);
 int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi,
                 hipStream_t s);

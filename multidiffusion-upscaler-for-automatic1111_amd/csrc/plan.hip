@@ -150,9 +150,9 @@ extern "C" mdtile_plan* mdtile_plan_create(int w, int h, int tile_w, int tile_h,
     return p;
 }
 
-// ---- the canvas closed in x (panoramas) ---------------------------------------------------------------------------
-// start and length of the cyclic run of set members (the covering tile columns of a canvas column or quad: the tiles whose origin lies on the
-// arc of tw columns that ends at it); all members -> (0, n)
+// ---- the canvas closed in x (panoramas), in y, or in both (seamless textures: a torus) ---------------------------------------------------
+// start and length of the cyclic run of set members (the covering tiles of a canvas coordinate or quad: on a wrapped axis the tiles whose
+// origin lies on the arc of `tile` coordinates that ends at it); all members -> (0, n).  A plain axis gives a run that never passes n.
 static int cyclic_run(const std::vector<char>& member) {
     const int n = (int)member.size();
     int cnt = 0, first = 0;
@@ -163,84 +163,8 @@ static int cyclic_run(const std::vector<char>& member) {
     return first | (cnt << 16);
 }
 
-extern "C" mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs) {
-    if (w <= 0 || h <= 0 || tile_w <= 0 || tile_h <= 0 || tile_bs <= 0 || w > 65535 || h > 65535) {
-        mdt::set_error("mdtile_plan_create_wrap_x: bad arguments w=%d h=%d tile=%dx%d bs=%d", w, h, tile_w, tile_h, tile_bs);
-        return nullptr;
-    }
-    // the clamp of mdtile_plan_create(clamp = 1)
-    const int tw = tile_w < w ? tile_w : w, th = tile_h < h ? tile_h : h;
-    const int mn = tile_w < tile_h ? tile_w : tile_h;
-    int ov = overlap < mn - 4 ? overlap : mn - 4;
-    if (ov < 0) ov = 0;
-    if (tw >= w) {
-        mdt::set_error("mdtile_plan_create_wrap_x: tile width %d >= canvas width %d: a tile would meet itself across the seam", tw, w);
-        return nullptr;
-    }
-    if (tw - ov == 0 || th - ov == 0) {
-        mdt::set_error("mdtile_plan_create_wrap_x: overlap %d equals the canvas-clamped tile %dx%d (division by zero upstream)", ov, tw, th);
-        return nullptr;
-    }
-    // columns on the circle: stride w / cols <= tw - ov, so cyclic neighbours overlap by >= ov everywhere, the seam included
-    const int cols = (int)std::ceil((double)w / (double)(tw - ov));
-    std::vector<int> xs(cols), ys, rr;
-    for (int c = 0; c < cols; ++c) xs[c] = (int)((double)c * (double)w / (double)cols);
-    origins_1d(h, th, ov, ys);
-    if (xs.size() > 32767 || ys.size() > 32767) {
-        mdt::set_error("mdtile_plan_create_wrap_x: too many tiles");
-        return nullptr;
-    }
-    cover_ranges(h, th, ys, rr);
-
-    mdtile_plan* p = new mdtile_plan();
-    p->wrap_x = 1;
-    p->w = w; p->h = h; p->tw = tw; p->th = th; p->ov = ov;
-    p->cols = cols; p->rows = (int)ys.size(); p->T = p->cols * p->rows;
-    p->num_batches = (p->T + tile_bs - 1) / tile_bs;
-    p->tile_bs = (p->T + p->num_batches - 1) / p->num_batches;
-    // the block layout of mdtile_plan_create, so that mdt::plan_upload serves both kinds: [xs | ys | colrange | rowrange | pad | colquad | rowinfo]
-    const int W4 = (w + 3) / 4;
-    const size_t head = xs.size() + ys.size() + (size_t)w + rr.size();
-    p->quad_off = (head + 3) & ~(size_t)3;
-    p->table_len = p->quad_off + 4 * (size_t)W4 + 4 * (size_t)h;
-    p->h_table = new int[p->table_len]();
-    int* q = p->h_table;
-    p->h_xs = q; memcpy(q, xs.data(), xs.size() * sizeof(int)); q += xs.size();
-    p->h_ys = q; memcpy(q, ys.data(), ys.size() * sizeof(int)); q += ys.size();
-    int* cr = q; q += w;
-    memcpy(q, rr.data(), rr.size() * sizeof(int));
-    int* cq = p->h_table + p->quad_off;
-    p->nc_max = p->nr_max = 0;
-    std::vector<char> member(cols), qmember(cols);
-    for (int xq = 0; xq < W4; ++xq) {
-        std::fill(qmember.begin(), qmember.end(), 0);
-        for (int j = 0; j < 4 && 4 * xq + j < w; ++j) {
-            const int x = 4 * xq + j;
-            for (int c = 0; c < cols; ++c) {
-                member[c] = ((x - xs[c] + w) % w) < tw;
-                qmember[c] = qmember[c] || member[c];
-            }
-            cr[x] = cyclic_run(member);
-        }
-        cq[4 * xq] = cyclic_run(qmember);
-        if ((cq[4 * xq] >> 16) > p->nc_max) p->nc_max = cq[4 * xq] >> 16;
-    }
-    int* ri = cq + 4 * (size_t)W4;
-    for (int y = 0; y < h; ++y) {
-        const int f = rr[y] & 0xffff;
-        ri[4 * y + 0] = rr[y];
-        if ((rr[y] >> 16) > p->nr_max) p->nr_max = rr[y] >> 16;
-        for (int k = 0; k < 3; ++k) ri[4 * y + 1 + k] = f + k < (int)ys.size() ? ys[f + k] : 0;
-    }
-    p->d_xs = p->d_ys = p->d_colrange = p->d_rowrange = nullptr;
-    p->d_colquad = p->d_rowinfo = nullptr;
-    return p;
-}
-
-extern "C" int mdtile_plan_wrap_x(const mdtile_plan* p) { return p && p->wrap_x ? 1 : 0; }
-
-// ---- the canvas closed in y, or in both axes (seamless textures: a torus) ---------------------------------------------
-// origins of one axis: on the circle when it wraps (the rule of the wrap-x columns), origins_1d when it does not
+// origins of one axis: on the circle when it wraps (stride extent / n <= tile - ov, so cyclic neighbours overlap by >= ov everywhere, the seam
+// included), origins_1d when it does not
 static void axis_origins(int extent, int tile, int ov, bool wrap, std::vector<int>& out) {
     if (!wrap) return origins_1d(extent, tile, ov, out);
     const int n = (int)std::ceil((double)extent / (double)(tile - ov));
@@ -253,12 +177,33 @@ static inline bool axis_covers(int p, int org, int tile, int extent, bool wrap) 
     return wrap ? ((p - org + extent) % extent) < tile : (org <= p && p < org + tile);
 }
 
+// the run tables of one axis: range[p] = the run of the tiles that cover coordinate p, rec[4 * g] (the .x of a 16-byte record) = the run of
+// the tiles that cover ANY coordinate of group g of `group` consecutive ones (4: the column quads; 1: the rows, whose record repeats range[p]).
+// Returns the longest run of a record.
+static int axis_runs(const std::vector<int>& org, int tile, int extent, bool wrap, int group, int* range, int* rec) {
+    const int n = (int)org.size();
+    std::vector<char> member(n), any(n);
+    int longest = 0;
+    for (int g = 0; g * group < extent; ++g) {
+        std::fill(any.begin(), any.end(), 0);
+        for (int p = g * group; p < (g + 1) * group && p < extent; ++p) {
+            for (int i = 0; i < n; ++i) {
+                member[i] = axis_covers(p, org[i], tile, extent, wrap);
+                any[i] = any[i] || member[i];
+            }
+            range[p] = cyclic_run(member);
+        }
+        rec[4 * g] = cyclic_run(any);
+        if ((rec[4 * g] >> 16) > longest) longest = rec[4 * g] >> 16;
+    }
+    return longest;
+}
+
 extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int wrap_x, int wrap_y) {
     if (!wrap_x && !wrap_y) {
         mdt::set_error("mdtile_plan_create_wrap: neither axis wraps: the plain grid is mdtile_plan_create");
         return nullptr;
     }
-    if (!wrap_y) return mdtile_plan_create_wrap_x(w, h, tile_w, tile_h, overlap, tile_bs);
     if (w <= 0 || h <= 0 || tile_w <= 0 || tile_h <= 0 || tile_bs <= 0 || w > 65535 || h > 65535) {
         mdt::set_error("mdtile_plan_create_wrap: bad arguments w=%d h=%d tile=%dx%d bs=%d", w, h, tile_w, tile_h, tile_bs);
         return nullptr;
@@ -272,7 +217,7 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int ti
         mdt::set_error("mdtile_plan_create_wrap: x axis: tile width %d >= canvas width %d: a tile would meet itself across the seam", tw, w);
         return nullptr;
     }
-    if (th >= h) {
+    if (wrap_y && th >= h) {
         mdt::set_error("mdtile_plan_create_wrap: y axis: tile height %d >= canvas height %d: a tile would meet itself across the seam", th, h);
         return nullptr;
     }
@@ -282,7 +227,7 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int ti
     }
     std::vector<int> xs, ys;
     axis_origins(w, tw, ov, wrap_x != 0, xs);
-    axis_origins(h, th, ov, true, ys);
+    axis_origins(h, th, ov, wrap_y != 0, ys);
     if (xs.size() > 32767 || ys.size() > 32767) {
         mdt::set_error("mdtile_plan_create_wrap: too many tiles");
         return nullptr;
@@ -291,7 +236,7 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int ti
 
     mdtile_plan* p = new mdtile_plan();
     p->wrap_x = wrap_x ? 1 : 0;
-    p->wrap_y = 1;
+    p->wrap_y = wrap_y ? 1 : 0;
     p->w = w; p->h = h; p->tw = tw; p->th = th; p->ov = ov;
     p->cols = cols; p->rows = rows; p->T = cols * rows;
     p->num_batches = (p->T + tile_bs - 1) / tile_bs;
@@ -305,35 +250,20 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int ti
     p->h_xs = p->h_table; memcpy(p->h_xs, xs.data(), xs.size() * sizeof(int));
     p->h_ys = p->h_xs + cols; memcpy(p->h_ys, ys.data(), ys.size() * sizeof(int));
     int* cr = p->h_ys + rows;
-    int* rr = cr + w;
     int* cq = p->h_table + p->quad_off;
-    int* ri = cq + 4 * (size_t)W4;
-    p->nc_max = p->nr_max = 0;
-    std::vector<char> member(cols), qmember(cols);
-    for (int xq = 0; xq < W4; ++xq) {
-        std::fill(qmember.begin(), qmember.end(), 0);
-        for (int j = 0; j < 4 && 4 * xq + j < w; ++j) {
-            const int x = 4 * xq + j;
-            for (int c = 0; c < cols; ++c) {
-                member[c] = axis_covers(x, xs[c], tw, w, wrap_x != 0);
-                qmember[c] = qmember[c] || member[c];
-            }
-            cr[x] = cyclic_run(member);
-        }
-        cq[4 * xq] = cyclic_run(qmember);
-        if ((cq[4 * xq] >> 16) > p->nc_max) p->nc_max = cq[4 * xq] >> 16;
-    }
-    std::vector<char> rmember(rows);
-    for (int y = 0; y < h; ++y) {
-        for (int r = 0; r < rows; ++r) rmember[r] = axis_covers(y, ys[r], th, h, true);
-        rr[y] = ri[4 * y] = cyclic_run(rmember);
-        if ((rr[y] >> 16) > p->nr_max) p->nr_max = rr[y] >> 16;
-    }
+    p->nc_max = axis_runs(xs, tw, w, wrap_x != 0, 4, cr, cq);
+    p->nr_max = axis_runs(ys, th, h, wrap_y != 0, 1, cr + w, cq + 4 * (size_t)W4);
     p->d_xs = p->d_ys = p->d_colrange = p->d_rowrange = nullptr;
     p->d_colquad = p->d_rowinfo = nullptr;
     return p;
 }
 
+// the canvas closed in x alone, under its first name
+extern "C" mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs) {
+    return mdtile_plan_create_wrap(w, h, tile_w, tile_h, overlap, tile_bs, 1, 0);
+}
+
+extern "C" int mdtile_plan_wrap_x(const mdtile_plan* p) { return p && p->wrap_x ? 1 : 0; }
 extern "C" int mdtile_plan_wrap_y(const mdtile_plan* p) { return p && p->wrap_y ? 1 : 0; }
 
 namespace mdt {

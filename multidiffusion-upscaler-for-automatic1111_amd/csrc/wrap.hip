@@ -1,18 +1,17 @@
-// Horizontal wrap-around (panoramas): weight map, tile gather and overlap blend for a plan whose canvas is closed in x
-// (mdtile_plan_create_wrap_x).  Tile column c covers the canvas columns (xs[c] + i) mod W, i in [0, tw); the formulation is the
-// gather of blend.hip -- one thread owns its output pixels and walks the tiles that cover them -- so closing the canvas only changes WHICH
-// tile columns cover a canvas column: a cyclic run of the plan's column list instead of a plain range.  Nothing scatters across the seam.
+// Wrap-around (panoramas, vertical strips, seamless textures): weight map, tile gather and overlap blend for a plan whose canvas is closed in x,
+// in y or in both (mdtile_plan_create_wrap).  Each axis is on a circle: tile column c covers the canvas columns
+// (xs[c] + i) mod W, i in [0, tw), tile row r the canvas rows (ys[r] + i) mod H, i in [0, th).  The formulation is the gather of blend.hip -- one
+// thread owns its output pixels and walks the tiles that cover them -- so closing the canvas only changes WHICH tile columns / rows cover a
+// canvas column / row: a cyclic run of the plan's column / row list instead of a plain range.  Nothing scatters across a seam.
 //
-// Order: the covering tiles are summed in ASCENDING tile index (rows outer, columns inner), which is the order of the sequential `+=` loop over
-// the tile list; at a seam pixel tile column 0 therefore comes before column cols - 1.  Per-term operations and epilogues are those of k_blend's
-// generic walk (blend.hip): Mixture of Diffusers w = tile_w * rescale[y, x], term out * w; MultiDiffusion weights > 1 ? buf / weights : buf.
-// fp32 accumulation from +0.0, -ffp-contract=off: results equal the sequential loop bit for bit.
+// An axis that does not wrap (wrap_x = 0 or wrap_y = 0; the x-only panorama is the case wrap_y = 0) is the specialisation that needs no code of
+// its own: a plain run never passes the end of its list and a plain tile never passes the edge, so the same arithmetic on the circle serves it.
 //
-// The canvas closed in y too (mdtile_plan_create_wrap, DESIGN.md 3.13: a torus, or a ring in y alone): the k_torus_* kernels below stand beside
-// the wrap-x ones, which are untouched.  Tile row r covers the canvas rows (ys[r] + i) mod H; the covering tile rows of a canvas row are a
-// cyclic run of the row list as well, walked in ascending index like the columns, so the order stays that of the tile list.  The columns of
-// such a plan are cyclic or plain (wrap_x = 0): a plain run never passes `cols` and a plain tile never passes the edge, so the same
-// arithmetic on the circle serves both.
+// Order: the covering tiles are summed in ASCENDING tile index (rows outer, columns inner; a cyclic run is walked as [0, head) then
+// [first, ...)), which is the order of the sequential `+=` loop over the tile list; at a seam pixel tile column 0 therefore comes before column
+// cols - 1, and tile row 0 before row rows - 1.  Per-term operations and epilogues are those of k_blend's generic walk (blend.hip): Mixture of
+// Diffusers w = tile_w * rescale[y, x], term out * w; MultiDiffusion weights > 1 ? buf / weights : buf.  fp32 accumulation from +0.0,
+// -ffp-contract=off: results equal the sequential loop bit for bit.
 //
 // Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
 // mdtile_blend_finalize -- wrap-around is not combined with regions or with the multi-GPU partial path.
@@ -22,37 +21,37 @@ using namespace mdt;
 
 namespace {
 
-// the cyclic run (first | count << 16 over `cols` tile columns) walked in ascending column index: [0, head) then [first, first + count - head)
-struct ColRun {
+// the cyclic run (first | count << 16 over a list of `n` tile columns or rows) walked in ascending index: [0, head) then [first, first + count - head)
+struct CyclicRun {
     int first, count, head;
-    __device__ __forceinline__ ColRun(int packed, int cols) {
+    __device__ __forceinline__ CyclicRun(int packed, int n) {
         first = packed & 0xffff;
         count = packed >> 16;
-        head = first + count > cols ? first + count - cols : 0;
+        head = first + count > n ? first + count - n : 0;
     }
-    __device__ __forceinline__ int col(int k) const { return k < head ? k : first + (k - head); }
+    __device__ __forceinline__ int at(int k) const { return k < head ? k : first + (k - head); }
 };
 
-// canvas column x relative to a tile origin xo, on the circle of W columns: in [0, W); covered by the tile iff < tw
-__device__ __forceinline__ int rel_x(int x, int xo, int W) {
-    const int d = x - xo;
-    return d < 0 ? d + W : d;
+// canvas coordinate p relative to a tile origin o, on the circle of `extent` coordinates: in [0, extent); covered by the tile iff < its size
+__device__ __forceinline__ int rel(int p, int o, int extent) {
+    const int d = p - o;
+    return d < 0 ? d + extent : d;
 }
 
-// weights[p] += sum over the covering tiles, ascending tile index, of tile_w[...] (or 1.0)
-__global__ __launch_bounds__(256) void k_wrap_weight_grid(int W, int H, int tw, int cols, const int* __restrict__ xs, const int* __restrict__ ys,
-                                                          const int* __restrict__ colrange, const int* __restrict__ rowrange,
-                                                          const float* __restrict__ tile_w, float* __restrict__ weights) {
+// weights[p] += sum over the covering tiles, ascending tile index (rows outer, columns inner), of tile_w[...] (or 1.0)
+__global__ __launch_bounds__(256) void k_wrap_weight_grid(int W, int H, int tw, int cols, int rows, const int* __restrict__ xs,
+                                                          const int* __restrict__ ys, const int* __restrict__ colrange,
+                                                          const int* __restrict__ rowrange, const float* __restrict__ tile_w,
+                                                          float* __restrict__ weights) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= W * H) return;
     const int y = idx / W, x = idx - y * W;
-    const ColRun run(colrange[x], cols);
-    const int rr = rowrange[y], r0 = rr & 0xffff, nr = rr >> 16;
+    const CyclicRun run(colrange[x], cols), rrun(rowrange[y], rows);
     float s = 0.0f;
-    for (int r = r0; r < r0 + nr; ++r) {
-        const int ty = y - ys[r];
+    for (int kr = 0; kr < rrun.count; ++kr) {
+        const int ty = rel(y, ys[rrun.at(kr)], H);
         for (int k = 0; k < run.count; ++k) {
-            const int tx = rel_x(x, xs[run.col(k)], W);
+            const int tx = rel(x, xs[run.at(k)], W);
             s += tile_w ? tile_w[ty * tw + tx] : 1.0f;
         }
     }
@@ -68,7 +67,7 @@ struct WrapGatherParams {
 };
 static_assert(sizeof(WrapGatherParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
-// x_tile[i*N + n, c, ty, tx] = x_in[n, c, y_i + ty, (x_i + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = tile
+// x_tile[i*N + n, c, ty, tx] = x_in[n, c, (y_i + ty) mod H, (x_i + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = tile
 template <typename T>
 __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     const int tw4 = (P.tw + 3) >> 2;
@@ -78,10 +77,12 @@ __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     const int plane = blockIdx.y, n = plane / P.C, c = plane - n * P.C;
     const int t = P.t_lo + blockIdx.z;
     const int r = t / P.cols, cc = t - r * P.cols;
-    const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + P.ys[r] + ty) * P.W;
+    int sy = P.ys[r] + ty;                // ys < H and ty < th <= H (th == H only on plain rows, ys = 0): one subtraction brings it back onto the canvas
+    if (sy >= P.H) sy -= P.H;
+    const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + sy) * P.W;
     const int b = t / P.tile_bs, i = t - b * P.tile_bs;
     T* dst = reinterpret_cast<T*>(P.batch[b]) + (((size_t)i * P.N + n) * P.C + c) * ((size_t)P.th * P.tw) + (size_t)ty * P.tw + tx0;
-    int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw < W: one subtraction brings it back onto the canvas
+    int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw <= W (tw == W only on plain columns, xs = 0): likewise
     if (sx >= P.W) sx -= P.W;
     const int nvalid = P.tw - tx0 < 4 ? P.tw - tx0 : 4;
     if (nvalid == 4 && sx + 3 < P.W) {    // the four source columns are consecutive in memory
@@ -103,6 +104,7 @@ struct WrapBlendParams {
     const float *weights, *tile_w, *rescale;
     void* out;
     const void* batch[MDTILE_MAX_BATCHES];
+    int rows;                 // behind the pointers: the argument layout the per-axis kernel was measured with (docs/history/results_log.md)
 };
 static_assert(sizeof(WrapBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
@@ -124,9 +126,10 @@ template <> __device__ __forceinline__ void load4_aligned<__hip_bfloat16>(const 
 }
 
 // One thread owns one quad (4 consecutive canvas columns of one row; rows start at x = 0, so a quad never straddles the seam) for PP planes.
-// A TILE's row segment may straddle it: per candidate tile the quad is either one contiguous piece of the tile row (tile-relative x0 .. x0 + 3
-// all below tw) -- vector loads when that piece is also aligned in memory -- or it is cut by a tile edge / the seam: per-element loads of the
-// covered pixels only.
+// The tile rows that cover the canvas row come from rowinfo[y].x and the tile columns that cover the quad from colquad[xq].x, both as cyclic
+// runs; a canvas row is one row of every tile that covers it (tile-relative row rel(y, ys[r], H)).  A TILE's row segment may straddle the seam:
+// per candidate tile the quad is either one contiguous piece of the tile row (tile-relative x0 .. x0 + 3 all below tw) -- vector loads when
+// that piece is also aligned in memory -- or it is cut by a tile edge / the seam: per-element loads of the covered pixels only.
 template <typename T, int METHOD, int PP>
 __global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
     const int W4 = (P.W + 3) >> 2;
@@ -144,8 +147,7 @@ __global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
 
-    const ColRun run(P.colquad[xq].x, P.cols);
-    const int rq = P.rowinfo[y].x, r0 = rq & 0xffff, nr = rq >> 16;
+    const CyclicRun run(P.colquad[xq].x, P.cols), rrun(P.rowinfo[y].x, P.rows);
     float resc[4] = {0.f, 0.f, 0.f, 0.f};
     if (METHOD == MDTILE_METHOD_MOD) {
 #pragma unroll
@@ -153,14 +155,15 @@ __global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
             if (j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
     }
 
-    for (int r = r0; r < r0 + nr; ++r) {                   // ascending tile index: rows outer, columns inner
-        const int ty = y - P.ys[r];
+    for (int kr = 0; kr < rrun.count; ++kr) {              // ascending tile index: rows outer, columns inner
+        const int r = rrun.at(kr);
+        const int ty = rel(y, P.ys[r], P.H);               // < th: rowinfo holds exactly the rows that cover y
+        const size_t roff = (size_t)ty * P.tw;             // the tile row inside a [th, tw] plane (and inside the tile-weight map)
         for (int k = 0; k < run.count; ++k) {
-            const int c = run.col(k);
+            const int c = run.at(k);
             const int t = r * P.cols + c;
             const int b = t / P.tile_bs, i = t - b * P.tile_bs;
-            const int tx = rel_x(x0, P.xs[c], P.W);
-            const size_t roff = (size_t)ty * P.tw;        // the tile row inside a [th, tw] plane (and inside the tile-weight map)
+            const int tx = rel(x0, P.xs[c], P.W);
             const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * P.N * P.C + p0) * tile_elems + roff;
             // one contiguous piece of the tile row, at an address aligned for the vector load in this plane and (tile_elems % 4 == 0) in the others
             const bool whole = nvalid == 4 && tx + 3 < P.tw;
@@ -241,201 +244,13 @@ void launch_wrap_blend_planes(const WrapBlendParams& P, int method, hipStream_t 
     else launch_wrap_blend<T, 1>(P, method, s);
 }
 
-// ---- the canvas closed in y as well (or in y alone) --------------------------------------------------------------------------------------------
-// ColRun over the row list: the cyclic run of tile rows that cover a canvas row, in ascending row index
-using RowRun = ColRun;
-
-// canvas row y relative to a tile origin yo, on the circle of H rows: in [0, H); covered by the tile iff < th
-__device__ __forceinline__ int rel_y(int y, int yo, int H) { return rel_x(y, yo, H); }
-
-// weights[p] += sum over the covering tiles, ascending tile index (rows outer, columns inner), of tile_w[...] (or 1.0)
-__global__ __launch_bounds__(256) void k_torus_weight_grid(int W, int H, int tw, int cols, int rows, const int* __restrict__ xs,
-                                                           const int* __restrict__ ys, const int* __restrict__ colrange,
-                                                           const int* __restrict__ rowrange, const float* __restrict__ tile_w,
-                                                           float* __restrict__ weights) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= W * H) return;
-    const int y = idx / W, x = idx - y * W;
-    const ColRun run(colrange[x], cols);
-    const RowRun rrun(rowrange[y], rows);
-    float s = 0.0f;
-    for (int kr = 0; kr < rrun.count; ++kr) {
-        const int ty = rel_y(y, ys[rrun.col(kr)], H);
-        for (int k = 0; k < run.count; ++k) {
-            const int tx = rel_x(x, xs[run.col(k)], W);
-            s += tile_w ? tile_w[ty * tw + tx] : 1.0f;
-        }
-    }
-    weights[idx] += s;
-}
-
-// x_tile[i*N + n, c, ty, tx] = x_in[n, c, (y_i + ty) mod H, (x_i + tx) mod W].  grid as k_wrap_gather
-template <typename T>
-__global__ __launch_bounds__(256) void k_torus_gather(const WrapGatherParams P) {
-    const int tw4 = (P.tw + 3) >> 2;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= tw4 * P.th) return;
-    const int ty = idx / tw4, tx0 = (idx - ty * tw4) << 2;
-    const int plane = blockIdx.y, n = plane / P.C, c = plane - n * P.C;
-    const int t = P.t_lo + blockIdx.z;
-    const int r = t / P.cols, cc = t - r * P.cols;
-    int sy = P.ys[r] + ty;                // ys < H and ty < th < H: one subtraction brings it back onto the canvas
-    if (sy >= P.H) sy -= P.H;
-    const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + sy) * P.W;
-    const int b = t / P.tile_bs, i = t - b * P.tile_bs;
-    T* dst = reinterpret_cast<T*>(P.batch[b]) + (((size_t)i * P.N + n) * P.C + c) * ((size_t)P.th * P.tw) + (size_t)ty * P.tw + tx0;
-    int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw <= W (tw == W only on plain columns, xs = 0): one subtraction
-    if (sx >= P.W) sx -= P.W;
-    const int nvalid = P.tw - tx0 < 4 ? P.tw - tx0 : 4;
-    if (nvalid == 4 && sx + 3 < P.W) {    // the four source columns are consecutive in memory
-        float v[4];
-        load4<T>(srow + sx, v);
-        store4<T>(dst, v);
-    } else {
-        for (int j = 0; j < nvalid; ++j) {
-            const int x = sx + j < P.W ? sx + j : sx + j - P.W;
-            dst[j] = srow[x];
-        }
-    }
-}
-
-struct TorusBlendParams {
-    WrapBlendParams b;
-    int rows;
-};
-static_assert(sizeof(TorusBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
-
-// k_wrap_blend with the tile rows on the circle as well: one thread owns one quad of one canvas row for PP planes; the tile rows that cover the
-// canvas row come from rowinfo[y].x as a cyclic run and are walked in ascending row index ([0, head) then [first, rows)), the tile-relative
-// row is rel_y(y, ys[r], H).  A canvas row is one row of every tile that covers it, so the column walk, the vector / element choice, the
-// per-term operations and the epilogues are those of k_wrap_blend.
-template <typename T, int METHOD, int PP>
-__global__ __launch_bounds__(256) void k_torus_blend(const TorusBlendParams Q) {
-    const WrapBlendParams& P = Q.b;
-    const int W4 = (P.W + 3) >> 2;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= W4 * P.H) return;
-    const int y = idx / W4, xq = idx - y * W4;
-    const int x0 = xq << 2;
-    const int p0 = blockIdx.y * PP;                        // the host guarantees N*C % PP == 0
-    const int nvalid = P.W - x0 < 4 ? P.W - x0 : 4;
-    const size_t tile_elems = (size_t)P.th * P.tw;
-
-    float acc[PP][4];
-#pragma unroll
-    for (int pp = 0; pp < PP; ++pp)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
-
-    const ColRun run(P.colquad[xq].x, P.cols);
-    const RowRun rrun(P.rowinfo[y].x, Q.rows);
-    float resc[4] = {0.f, 0.f, 0.f, 0.f};
-    if (METHOD == MDTILE_METHOD_MOD) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
-    }
-
-    for (int kr = 0; kr < rrun.count; ++kr) {              // ascending tile index: rows outer, columns inner
-        const int r = rrun.col(kr);
-        const int ty = rel_y(y, P.ys[r], P.H);             // < th: rowinfo holds exactly the rows that cover y
-        const size_t roff = (size_t)ty * P.tw;             // the tile row inside a [th, tw] plane (and inside the tile-weight map)
-        for (int k = 0; k < run.count; ++k) {
-            const int c = run.col(k);
-            const int t = r * P.cols + c;
-            const int b = t / P.tile_bs, i = t - b * P.tile_bs;
-            const int tx = rel_x(x0, P.xs[c], P.W);
-            const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * P.N * P.C + p0) * tile_elems + roff;
-            // one contiguous piece of the tile row, at an address aligned for the vector load in this plane and (tile_elems % 4 == 0) in the others
-            const bool whole = nvalid == 4 && tx + 3 < P.tw;
-            if (whole && (reinterpret_cast<uintptr_t>(row + tx) & (4 * sizeof(T) - 1)) == 0 && (tile_elems & 3) == 0) {
-                float wg[4] = {1.f, 1.f, 1.f, 1.f};
-                if (METHOD == MDTILE_METHOD_MOD) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) wg[j] = P.tile_w[roff + tx + j] * resc[j];
-                }
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp) {
-                    float v[4];
-                    load4_aligned<T>(row + (size_t)pp * tile_elems + tx, v);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v[j] * wg[j];
-                        else acc[pp][j] += v[j];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int txj = tx + j;                      // tx < W, j < 4: one subtraction
-                    if (txj >= P.W) txj -= P.W;
-                    if (j >= nvalid || txj >= P.tw) continue;
-                    float wgt = 1.0f;
-                    if (METHOD == MDTILE_METHOD_MOD) wgt = P.tile_w[roff + txj] * resc[j];
-#pragma unroll
-                    for (int pp = 0; pp < PP; ++pp) {
-                        const float v = to_f32<T>(row[(size_t)pp * tile_elems + txj]);
-                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
-                        else acc[pp][j] += v;
-                    }
-                }
-            }
-        }
-    }
-
-    // MD normalisation: x = where(weights > 1, buf / weights, buf)
-    if (METHOD == MDTILE_METHOD_MD) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j >= nvalid) continue;
-            const float w = P.weights[(size_t)y * P.W + x0 + j];
-            if (w > 1.0f) {
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
-            }
-        }
-    }
-
-#pragma unroll
-    for (int pp = 0; pp < PP; ++pp) {
-        T* dst = reinterpret_cast<T*>(P.out) + ((size_t)(p0 + pp) * P.H + y) * P.W + x0;
-        if (nvalid == 4) store4<T>(dst, acc[pp]);
-        else {
-            dst[0] = from_f32<T>(acc[pp][0]);
-            if (nvalid > 1) dst[1] = from_f32<T>(acc[pp][1]);
-            if (nvalid > 2) dst[2] = from_f32<T>(acc[pp][2]);
-        }
-    }
-}
-
-template <typename T, int PP>
-void launch_torus_blend(const TorusBlendParams& Q, int method, hipStream_t s) {
-    dim3 grid(cdiv((long long)Q.b.H * ((Q.b.W + 3) / 4), 256), (Q.b.N * Q.b.C) / PP), block(256);
-    if (method == MDTILE_METHOD_MD) hipLaunchKernelGGL((k_torus_blend<T, MDTILE_METHOD_MD, PP>), grid, block, 0, s, Q);
-    else hipLaunchKernelGGL((k_torus_blend<T, MDTILE_METHOD_MOD, PP>), grid, block, 0, s, Q);
-}
-
-// planes per thread: the rule of launch_wrap_blend_planes
-template <typename T>
-void launch_torus_blend_planes(const TorusBlendParams& Q, int method, hipStream_t s) {
-    const int planes = Q.b.N * Q.b.C;
-    const long long work = (long long)Q.b.H * ((Q.b.W + 3) / 4) * planes;
-    if (planes % 4 == 0 && work / 4 >= 131072) launch_torus_blend<T, 4>(Q, method, s);
-    else if (planes % 2 == 0 && work / 2 >= 131072) launch_torus_blend<T, 2>(Q, method, s);
-    else launch_torus_blend<T, 1>(Q, method, s);
-}
-
 }  // namespace
 
 int mdt::wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_weights, hipStream_t s) {
     if (int rc = plan_upload(p)) return rc;
     const int n = p->w * p->h;
-    if (p->wrap_y)
-        hipLaunchKernelGGL(k_torus_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, s, p->w, p->h, p->tw, p->cols, p->rows, p->d_xs, p->d_ys,
-                           p->d_colrange, p->d_rowrange, d_tile_w, d_weights);
-    else
-        hipLaunchKernelGGL(k_wrap_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, s, p->w, p->h, p->tw, p->cols, p->d_xs, p->d_ys, p->d_colrange,
-                           p->d_rowrange, d_tile_w, d_weights);
+    hipLaunchKernelGGL(k_wrap_weight_grid, dim3(cdiv(n, 256)), dim3(256), 0, s, p->w, p->h, p->tw, p->cols, p->rows, p->d_xs, p->d_ys, p->d_colrange,
+                       p->d_rowrange, d_tile_w, d_weights);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -459,18 +274,10 @@ int mdt::wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* 
     P.t_lo = t_lo; P.xs = p->d_xs; P.ys = p->d_ys; P.x_in = d_x_in;
     for (int b = 0; b < nptrs; ++b) P.batch[b] = ptrs[b];
     dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, t_hi - t_lo), block(256);
-    if (p->wrap_y) {
-        switch (dtype) {
-            case MDTILE_DT_F32: hipLaunchKernelGGL(k_torus_gather<float>, grid, block, 0, s, P); break;
-            case MDTILE_DT_F16: hipLaunchKernelGGL(k_torus_gather<__half>, grid, block, 0, s, P); break;
-            default: hipLaunchKernelGGL(k_torus_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
-        }
-    } else {
-        switch (dtype) {
-            case MDTILE_DT_F32: hipLaunchKernelGGL(k_wrap_gather<float>, grid, block, 0, s, P); break;
-            case MDTILE_DT_F16: hipLaunchKernelGGL(k_wrap_gather<__half>, grid, block, 0, s, P); break;
-            default: hipLaunchKernelGGL(k_wrap_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
-        }
+    switch (dtype) {
+        case MDTILE_DT_F32: hipLaunchKernelGGL(k_wrap_gather<float>, grid, block, 0, s, P); break;
+        case MDTILE_DT_F16: hipLaunchKernelGGL(k_wrap_gather<__half>, grid, block, 0, s, P); break;
+        default: hipLaunchKernelGGL(k_wrap_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
     }
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
@@ -501,25 +308,14 @@ int mdt::wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void
     if (int rc = plan_upload(p)) return rc;
     WrapBlendParams P;
     memset(&P, 0, sizeof(P));
-    P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
+    P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.rows = p->rows; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
     P.xs = p->d_xs; P.ys = p->d_ys; P.colquad = p->d_colquad; P.rowinfo = p->d_rowinfo;
     P.weights = a->d_weights; P.tile_w = a->d_tile_w; P.rescale = a->d_rescale; P.out = a->d_x_out;
     for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
-    if (p->wrap_y) {
-        TorusBlendParams Q;
-        Q.b = P;
-        Q.rows = p->rows;
-        switch (a->dtype) {
-            case MDTILE_DT_F32: launch_torus_blend_planes<float>(Q, a->method, s); break;
-            case MDTILE_DT_F16: launch_torus_blend_planes<__half>(Q, a->method, s); break;
-            default: launch_torus_blend_planes<__hip_bfloat16>(Q, a->method, s); break;
-        }
-    } else {
-        switch (a->dtype) {
-            case MDTILE_DT_F32: launch_wrap_blend_planes<float>(P, a->method, s); break;
-            case MDTILE_DT_F16: launch_wrap_blend_planes<__half>(P, a->method, s); break;
-            default: launch_wrap_blend_planes<__hip_bfloat16>(P, a->method, s); break;
-        }
+    switch (a->dtype) {
+        case MDTILE_DT_F32: launch_wrap_blend_planes<float>(P, a->method, s); break;
+        case MDTILE_DT_F16: launch_wrap_blend_planes<__half>(P, a->method, s); break;
+        default: launch_wrap_blend_planes<__hip_bfloat16>(P, a->method, s); break;
     }
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;

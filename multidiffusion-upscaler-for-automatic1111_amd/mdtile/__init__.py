@@ -286,10 +286,10 @@ def dtype_code(dt: torch.dtype) -> int:
 # ---------------------------------------------------------------------------------------------------------------------
 class Plan:
     """Grid plan == split_bboxes + init_grid_bbox (tile_utils/utils.py:160-177, abstractdiffusion.py:173-186).
-    wrap_x: the canvas is closed in x (panoramas, mdtile_plan_create_wrap_x): tile columns lie on a circle, a box's x + w may pass the canvas
+    wrap_x: the canvas is closed in x (panoramas, mdtile_plan_create_wrap): tile columns lie on a circle, a box's x + w may pass the canvas
     width (its columns are taken mod w), clamp is always on.  A tile as wide as the canvas raises MdtileError.
-    wrap_y: the same for the rows (mdtile_plan_create_wrap); with wrap_x the canvas is a torus (seamless textures).  A box's y + h may pass the
-    canvas height; a tile as tall as the canvas raises MdtileError."""
+    wrap_y: the same for the rows; with wrap_x the canvas is a torus (seamless textures).  A box's y + h may pass the canvas height; a tile as
+    tall as the canvas raises MdtileError."""
 
     def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True, wrap_x: bool = False,
                  wrap_y: bool = False):
@@ -298,10 +298,8 @@ class Plan:
         if (self.wrap_x or self.wrap_y) and not clamp:
             axes = "wrap_x=True" if not self.wrap_y else "wrap_y=True"
             raise MdtileError(f"Plan({axes}) always clamps tile and overlap (clamp=False is not available)")
-        if self.wrap_y:
-            self._h = L.mdtile_plan_create_wrap(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(self.wrap_x), 1)
-        elif self.wrap_x:
-            self._h = L.mdtile_plan_create_wrap_x(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs))
+        if self.wrap_x or self.wrap_y:
+            self._h = L.mdtile_plan_create_wrap(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(self.wrap_x), int(self.wrap_y))
         else:
             self._h = L.mdtile_plan_create(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(clamp))
         if not self._h:

@@ -1,5 +1,5 @@
-"""Vertical wrap-around and the torus on the GPU (the k_torus_* kernels of csrc/wrap.hip), BITWISE against the numpy restatement
-tests/torus_ref.py: plan, weight maps, gather, the MultiDiffusion / Mixture-of-Diffusers blend in fp32, fp16 and bf16, the summation order at a
+"""Vertical wrap-around and the torus on the GPU (the per-axis kernels of csrc/wrap.hip), BITWISE against the numpy restatement
+tests/wrap_ref.py: plan, weight maps, gather, the MultiDiffusion / Mixture-of-Diffusers blend in fp32, fp16 and bf16, the summation order at a
 seam, special values, the refused calls, the delegates and the Tiled VAE hook with the options set.  No tolerance appears in this file; half
 types follow tests/test_gpu_blend_matrix.py (inputs and tile outputs rounded to the dtype, the fp32 restatement evaluated on those values,
 rounded once).
@@ -7,22 +7,19 @@ rounded once).
 Every case runs N = 2, C = 4.  The small canvases take the launcher's one-plane-per-thread form, the two larger ones its 2- and 4-plane forms."""
 import ctypes
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import blend_oracle as bo
 from hostsim import stub_host as sh
 
-import torus_ref as tr
+import wrap_ref as tr
+from wrap_common import (DT, NAN, N, C, SPECIALS, assert_bitwise as _assert_bitwise, tile_fn as _tile_fn, identity as _identity,
+                         on_device as _on_device, maps as _maps, make_delegate, evaluate_delegate, gpu_vae_hook, set_options as _set_options)
 
 pytestmark = pytest.mark.gpu
 
-DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-NAN = float("nan")
-N, C = 2, 4
 CASES = tr.CASES
 # the blend also runs aligned64 with every batch tensor one element into its storage: the vector path must be skipped
 BLEND_CASES = list(CASES) + ["aligned64_misaligned"]
@@ -30,32 +27,6 @@ BLEND_CASES = list(CASES) + ["aligned64_misaligned"]
 
 def _base(case):
     return case[:-len("_misaligned")] if case.endswith("_misaligned") else case
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _assert_bitwise(got, ref, what):
-    """The NaN pattern first, then the bits of everything else."""
-    got = got.detach().cpu()
-    assert got.dtype == ref.dtype and got.shape == ref.shape, f"{what}: {got.dtype} {tuple(got.shape)} vs {ref.dtype} {tuple(ref.shape)}"
-    nan = torch.isnan(ref)
-    assert torch.equal(torch.isnan(got), nan), f"{what}: NaN pattern differs ({int(torch.isnan(got).sum())} vs {int(nan.sum())} NaNs)"
-    gb, rb = _bits(got), _bits(ref)
-    z = torch.zeros((), dtype=gb.dtype)
-    bad = torch.where(nan, z, gb) != torch.where(nan, z, rb)
-    if bad.any():
-        i = tuple(bad.nonzero()[0].tolist())
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ bitwise; first at {i}: got {got[i].item()!r}, want {ref[i].item()!r}")
-
-
-def _tile_fn(t):
-    return bo.synthetic_denoiser(t.float()).to(t.dtype)
-
-
-def _identity(t):
-    return t
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,7 +53,7 @@ def _canvas(case, dtype, special=False):
     torch.manual_seed(len(_base(case)) + 11)
     x = torch.randn(N, C, g.H, g.W)
     if special:
-        vals = torch.tensor([0.0, -0.0, float("inf"), float("-inf"), NAN, 1e-40, -1e-40, 1.4e-45, -1.4e-45, 3e-8, 65504.0, 1.17549435e-38, 3.0e38, -3.0e38])
+        vals = torch.tensor(SPECIALS)
         for i, c in enumerate(_edges(g.xs, g.tw, g.W)):        # columns of specials, one value per row ...
             x[:, :, :, c] = vals[(torch.arange(g.H) + i) % len(vals)][None, None, :]
         for i, r in enumerate(_edges(g.ys, g.th, g.H)):        # ... and rows of them, one value per column, shifted from row to row
@@ -98,28 +69,6 @@ def _tiles(case, dt, special=False):
     fn = _identity if special else _tile_fn
     outs = [fn(torch.from_numpy(tr.gather(g, x.float().numpy(), b)).to(dtype)) for b in range(len(g.batches))]
     return x, outs
-
-
-def _on_device(t, cuda, misaligned):
-    if not misaligned:
-        return t.to(cuda)
-    store = torch.zeros(t.numel() + 16, dtype=t.dtype, device=cuda)
-    v = store[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == v.element_size() and v.is_contiguous()
-    return v
-
-
-def _maps(E, plan, cuda):
-    """Device maps of both methods: uniform weight sum; Gaussian tile weight, its weight sum, the reciprocal."""
-    g = SimpleNamespace()
-    g.weights = torch.zeros(plan.h, plan.w, device=cuda)
-    E.weight_map_add_grid(plan, None, g.weights)
-    g.tile_w = E.gaussian_weights(plan.tile_w, plan.tile_h, cuda)
-    g.gsum = torch.zeros(plan.h, plan.w, device=cuda)
-    E.weight_map_add_grid(plan, g.tile_w, g.gsum)
-    g.rescale = E.reciprocal(g.gsum)
-    return g
 
 
 # ---- gather and weight maps ------------------------------------------------------------------------------------------------
@@ -262,14 +211,6 @@ def test_refused_calls_write_nothing(plugin, cuda, case):
 
 
 # ---- the plugin with the options set -------------------------------------------------------------------------------------------
-def _set_options(shared, wrap_x, wrap_y):
-    for name, on in (("mdtile_wrap_x", wrap_x), ("mdtile_wrap_y", wrap_y)):
-        if on:
-            setattr(shared.cmd_opts, name, True)
-        elif hasattr(shared.cmd_opts, name):
-            delattr(shared.cmd_opts, name)
-
-
 @pytest.fixture
 def options():
     """set(wrap_x, wrap_y) on the stub host's command line; both options are gone again afterwards."""
@@ -289,26 +230,12 @@ def test_delegate_with_the_options_bitwise(plugin, cuda, options, method, case):
     g = _grid(case)
     W, H, tw, th, ov, wx, wy, bs = CASES[case]
     shared = options(bool(wx), bool(wy))
-    cls = plugin.multidiffusion.MultiDiffusion if method == "md" else plugin.mixtureofdiffusers.MixtureOfDiffusers
-    p = sh.make_processing(W * 8, H * 8)
-    d = cls(p, sh.kdiff_sampler())
-    d.init_grid_bbox(tw, th, ov, bs)
-    d.init_done()
-    if d.pbar is not None:
-        d.pbar.close()
-    d.update_pbar = lambda: None
+    d, p = make_delegate(plugin, method, W, H, tw, th, ov, bs)
     assert d.plan.wrap_y and d.plan.wrap_x == bool(wx) and d.plan.bboxes == list(g.boxes)
     assert p.extra_generation_params["Tiled Diffusion wrap y"] is True and ("Tiled Diffusion wrap x" in p.extra_generation_params) == bool(wx)
     x, outs = _tiles(case, "f32")
-    tiles = torch.cat(outs, dim=0).numpy()
-    if method == "md":
-        out = d.sample_one_step(x.to(cuda), None, lambda xt, b: _tile_fn(xt), None)
-        ref = tr.blend(g, "md", tiles, N, d.weights.cpu().numpy()[0, 0])
-    else:
-        shared.sd_model.apply_model_original_md = lambda x_, t_, c_: _tile_fn(x_)
-        cond = {"c_crossattn": [torch.zeros(N, 77, 768, device=cuda)], "c_concat": [torch.zeros(N, 5, 1, 1, device=cuda)]}
-        out = d.apply_model_hijack(x.to(cuda), torch.zeros(N, device=cuda), cond)
-        ref = tr.blend(g, "mod", tiles, N, None, d.get_tile_weights().cpu().numpy(), d.rescale_factor.cpu().numpy()[0, 0])
+    out, map_args = evaluate_delegate(d, method, x, shared, cuda)
+    ref = tr.blend(g, method, torch.cat(outs, dim=0).numpy(), N, *map_args)
     _assert_bitwise(out, torch.from_numpy(ref), f"delegate {method} {case}")
 
 
@@ -317,11 +244,7 @@ def test_delegate_with_the_options_bitwise(plugin, cuda, options, method, case):
 def test_vae_hook_wraps_rows_by_its_tile_pad(plugin, cuda, options, is_decoder, both):
     """Tiled VAE with the option(s): the result is the plain hook's on the input padded by hand with the rows of the other edge (11 latent px
     for the decoder, 32 image px for the encoder) -- columns first, then rows, on the torus -- cropped by 8 P / P / 8 per side: torch.equal."""
-    from hostsim import ldm_decoder as ld
-    net = (ld.make_decoder(0, small=True) if is_decoder else ld.make_encoder(0, small=True)).to(cuda)
-    net.original_forward = net.forward
-    ts, P = (16, 11) if is_decoder else (64, 32)
-    hook = plugin.tilevae.VAEHook(net, ts, is_decoder=is_decoder, fast_decoder=True, fast_encoder=True, color_fix=False)
+    hook, P = gpu_vae_hook(plugin, cuda, is_decoder)
     torch.manual_seed(5)
     z = torch.randn(1, 4, 40, 24, device=cuda) if is_decoder else torch.randn(1, 3, 320, 192, device=cuda)
     hand = torch.cat([z[..., -P:], z, z[..., :P]], dim=-1) if both else z

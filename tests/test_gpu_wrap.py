@@ -1,26 +1,22 @@
-"""Horizontal wrap-around on the GPU (csrc/wrap.hip), BITWISE against the numpy restatement tests/wrap_ref.py: plan, weight
-maps, gather, the MultiDiffusion / Mixture-of-Diffusers blend in fp32, fp16 and bf16, special values, the refused calls, and the Tiled VAE
-hook with the option set.  No tolerance appears in this file; half types follow tests/test_gpu_blend_matrix.py (inputs and tile outputs
-rounded to the dtype, the fp32 restatement evaluated on those values, rounded once).
+"""Horizontal wrap-around on the GPU (the per-axis kernels of csrc/wrap.hip on plain rows), BITWISE against the numpy
+restatement tests/wrap_ref.py: plan, weight maps, gather, the MultiDiffusion / Mixture-of-Diffusers blend in fp32, fp16 and bf16, special
+values, the refused calls, and the Tiled VAE hook with the option set.  No tolerance appears in this file; half types follow
+tests/test_gpu_blend_matrix.py (inputs and tile outputs rounded to the dtype, the fp32 restatement evaluated on those values, rounded once).
 
 Every case runs N = 2, C = 4.  The small canvases take the launcher's one-plane-per-thread form, the two larger ones its 2- and 4-plane forms."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import blend_oracle as bo
 from hostsim import stub_host as sh
 
 import wrap_ref as wr
+from wrap_common import (DT, NAN, N, C, SPECIALS, assert_bitwise as _assert_bitwise, tile_fn as _tile_fn, identity as _identity,
+                         on_device as _on_device, maps as _maps, make_delegate, evaluate_delegate, gpu_vae_hook, set_options)
 
 pytestmark = pytest.mark.gpu
-
-DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-NAN = float("nan")
-N, C = 2, 4
 
 # id -> (W, H, requested tile_w, tile_h, overlap, tile_bs, misaligned batches).  The overlap is clamped to min(requested tile sizes) - 4, so the
 # 48 x 12 tiles at overlap 44 are requested as 48 x 48 on a canvas 12 rows high.
@@ -44,31 +40,6 @@ CASES = {
 }
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def _assert_bitwise(got, ref, what):
-    got = got.detach().cpu()
-    assert got.dtype == ref.dtype and got.shape == ref.shape, f"{what}: {got.dtype} {tuple(got.shape)} vs {ref.dtype} {tuple(ref.shape)}"
-    nan = torch.isnan(ref)
-    assert torch.equal(torch.isnan(got), nan), f"{what}: NaN pattern differs ({int(torch.isnan(got).sum())} vs {int(nan.sum())} NaNs)"
-    gb, rb = _bits(got), _bits(ref)
-    z = torch.zeros((), dtype=gb.dtype)
-    bad = torch.where(nan, z, gb) != torch.where(nan, z, rb)
-    if bad.any():
-        i = tuple(bad.nonzero()[0].tolist())
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ bitwise; first at {i}: got {got[i].item()!r}, want {ref[i].item()!r}")
-
-
-def _tile_fn(t):
-    return bo.synthetic_denoiser(t.float()).to(t.dtype)
-
-
-def _identity(t):
-    return t
-
-
 @functools.lru_cache(maxsize=None)
 def _grid(case):
     W, H, tw, th, ov, bs, _ = CASES[case]
@@ -90,7 +61,7 @@ def _canvas(case, dtype, special=False):
     torch.manual_seed(len(case) + 7)
     x = torch.randn(N, C, g.H, g.W)
     if special:
-        vals = torch.tensor([0.0, -0.0, float("inf"), float("-inf"), NAN, 1e-40, -1e-40, 1.4e-45, -1.4e-45, 3e-8, 65504.0, 1.17549435e-38, 3.0e38, -3.0e38])
+        vals = torch.tensor(SPECIALS)
         cols = sorted({c % g.W for x0 in g.xs for c in (x0 - 1, x0, x0 + 1, x0 + 3, x0 + 4, x0 + g.tw - 1, x0 + g.tw)} | {0, 1, g.W - 1, g.W - 2})
         for i, c in enumerate(cols):                    # columns of specials on every tile edge and on both sides of the seam, one value per row
             x[:, :, :, c] = vals[(torch.arange(g.H) + i) % len(vals)][None, None, :]
@@ -106,28 +77,6 @@ def _tiles(case, dt, special=False):
     fn = _identity if special else _tile_fn
     outs = [fn(torch.from_numpy(wr.gather(g, x.float().numpy(), b)).to(dtype)) for b in range(len(g.batches))]
     return x, outs
-
-
-def _on_device(t, cuda, misaligned):
-    if not misaligned:
-        return t.to(cuda)
-    store = torch.zeros(t.numel() + 16, dtype=t.dtype, device=cuda)
-    v = store[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == v.element_size() and v.is_contiguous()
-    return v
-
-
-def _maps(E, plan, cuda):
-    """Device maps of both methods and their host copies: uniform weight sum; Gaussian tile weight, its weight sum, the reciprocal."""
-    g = SimpleNamespace()
-    g.weights = torch.zeros(plan.h, plan.w, device=cuda)
-    E.weight_map_add_grid(plan, None, g.weights)
-    g.tile_w = E.gaussian_weights(plan.tile_w, plan.tile_h, cuda)
-    g.gsum = torch.zeros(plan.h, plan.w, device=cuda)
-    E.weight_map_add_grid(plan, g.tile_w, g.gsum)
-    g.rescale = E.reciprocal(g.gsum)
-    return g
 
 
 # ---- gather and weight maps ------------------------------------------------------------------------------------------------
@@ -253,38 +202,24 @@ def test_refused_calls_write_nothing(plugin, cuda):
 @pytest.fixture
 def wrap_option():
     _, shared = sh.host()
-    shared.cmd_opts.mdtile_wrap_x = True
+    set_options(shared, True, False)
     try:
         yield shared
     finally:
-        del shared.cmd_opts.mdtile_wrap_x
+        set_options(shared, False, False)
 
 
 @pytest.mark.parametrize("method", ["md", "mod"])
 def test_delegate_with_the_option_bitwise(plugin, cuda, wrap_option, method):
     """One model evaluation through MultiDiffusion / MixtureOfDiffusers with --mdtile-wrap-x: the delegate builds the wrap-x plan and its
     result is the restatement's."""
-    E, g = plugin.engine, _grid("odd37")
+    g = _grid("odd37")
     W, H, tw, th, ov, bs, _ = CASES["odd37"]
-    cls = plugin.multidiffusion.MultiDiffusion if method == "md" else plugin.mixtureofdiffusers.MixtureOfDiffusers
-    p = sh.make_processing(W * 8, H * 8)
-    d = cls(p, sh.kdiff_sampler())
-    d.init_grid_bbox(tw, th, ov, bs)
-    d.init_done()
-    if d.pbar is not None:
-        d.pbar.close()
-    d.update_pbar = lambda: None
+    d, p = make_delegate(plugin, method, W, H, tw, th, ov, bs)
     assert d.plan.wrap_x and p.extra_generation_params["Tiled Diffusion wrap x"] is True
     x, outs = _tiles("odd37", "f32")
-    tiles = torch.cat(outs, dim=0).numpy()
-    if method == "md":
-        out = d.sample_one_step(x.to(cuda), None, lambda xt, b: _tile_fn(xt), None)
-        ref = wr.blend(g, "md", tiles, N, d.weights.cpu().numpy()[0, 0])
-    else:
-        wrap_option.sd_model.apply_model_original_md = lambda x_, t_, c_: _tile_fn(x_)
-        cond = {"c_crossattn": [torch.zeros(N, 77, 768, device=cuda)], "c_concat": [torch.zeros(N, 5, 1, 1, device=cuda)]}
-        out = d.apply_model_hijack(x.to(cuda), torch.zeros(N, device=cuda), cond)
-        ref = wr.blend(g, "mod", tiles, N, None, d.get_tile_weights().cpu().numpy(), d.rescale_factor.cpu().numpy()[0, 0])
+    out, map_args = evaluate_delegate(d, method, x, wrap_option, cuda)
+    ref = wr.blend(g, method, torch.cat(outs, dim=0).numpy(), N, *map_args)
     _assert_bitwise(out, torch.from_numpy(ref), f"delegate {method}")
 
 
@@ -292,21 +227,14 @@ def test_delegate_with_the_option_bitwise(plugin, cuda, wrap_option, method):
 def test_vae_hook_wraps_by_its_tile_pad(plugin, cuda, wrap_option, is_decoder):
     """Tiled VAE with the option: the result is the plain hook's on the input padded by hand with the columns of the other edge (11 latent px
     for the decoder, 32 image px for the encoder), cropped by 8 P / P / 8 columns per side -- bit for bit."""
-    from hostsim import ldm_decoder as ld
-    net = (ld.make_decoder(0, small=True) if is_decoder else ld.make_encoder(0, small=True)).to(cuda)
-    net.original_forward = net.forward
-    ts, P = (16, 11) if is_decoder else (64, 32)
-    hook = plugin.tilevae.VAEHook(net, ts, is_decoder=is_decoder, fast_decoder=True, fast_encoder=True, color_fix=False)
+    hook, P = gpu_vae_hook(plugin, cuda, is_decoder)
     torch.manual_seed(5)
     z = torch.randn(1, 4, 24, 56, device=cuda) if is_decoder else torch.randn(1, 3, 192, 448, device=cuda)
     with torch.no_grad():
         got = hook(z)
-        del wrap_option.cmd_opts.mdtile_wrap_x
-        try:
-            padded = hook(torch.cat([z[..., -P:], z, z[..., :P]], dim=-1))
-            plain = hook(z)
-        finally:
-            wrap_option.cmd_opts.mdtile_wrap_x = True
+        set_options(wrap_option, False, False)
+        padded = hook(torch.cat([z[..., -P:], z, z[..., :P]], dim=-1))
+        plain = hook(z)
     cut = 8 * P if is_decoder else P // 8
     want = padded[..., cut:padded.shape[-1] - cut]
     assert got.shape == plain.shape == want.shape

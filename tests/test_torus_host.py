@@ -1,5 +1,5 @@
 """Vertical wrap-around and the torus without a GPU: the plan of mdtile_plan_create_wrap against the numpy restatement
-tests/torus_ref.py, its refusals, the --mdtile-wrap-y option, the script wiring on the stub host (plan choice, per-axis fallback, the region
+tests/wrap_ref.py, its refusals, the --mdtile-wrap-y option, the script wiring on the stub host (plan choice, per-axis fallback, the region
 refusal, infotext, the extended copy's rows and corner) and the Tiled VAE hook's pad-and-crop in y on the torch doubles of the engine."""
 import argparse
 import ctypes
@@ -18,8 +18,9 @@ for _p in (ROOT, PLUGIN, os.path.join(ROOT, "tests")):
         sys.path.insert(0, _p)
 
 from hostsim import stub_host as sh      # noqa: E402
-import torus_ref as tr                   # noqa: E402
-import wrap_ref as wr                    # noqa: E402
+import wrap_ref as tr                    # noqa: E402
+from wrap_common import (host, wired, delegate as _delegate, load_preload, take as _take, cpu_vae_hook as _hook,      # noqa: E402,F401
+                         pad_rows as _pad_rows, pad_cols as _pad_cols)
 
 
 # ---- plan --------------------------------------------------------------------------------------------------------------------
@@ -65,7 +66,7 @@ def test_plan_matches_the_restatement(built_lib, case):
     if wx:
         assert max(x + g.tw for x in g.xs) > W and _cover(g.xs, g.tw, W).min() >= 1
     else:
-        assert list(g.xs) == wr.plain_origins(W, g.tw, g.ov) and max(x + g.tw for x in g.xs) == W
+        assert list(g.xs) == tr.plain_origins(W, g.tw, g.ov) and max(x + g.tw for x in g.xs) == W
 
 
 def test_the_cases_are_what_the_issue_lists():
@@ -99,7 +100,7 @@ def test_wrap_x_alone_is_the_wrap_x_plan(built_lib, geom):
     b = _raw(E, L.mdtile_plan_create_wrap_x(*geom))
     assert a == b and a[2:] == (1, 0)
     g = tr.grid(*geom, True, False)
-    assert g == wr.grid(*geom) and a[1] == list(g.boxes)
+    assert g == tr.grid(*geom) and a[1] == list(g.boxes)
     plan = E.Plan(*geom, wrap_x=True)
     assert plan.wrap_x and not plan.wrap_y and plan.bboxes == a[1]
     plain = E.Plan(*geom)
@@ -140,32 +141,10 @@ def test_plan_refusals(built_lib):
 
 
 # ---- the option --------------------------------------------------------------------------------------------------------------
-def _clear(shared):
-    for name in ("mdtile_wrap_x", "mdtile_wrap_y"):
-        if hasattr(shared.cmd_opts, name):
-            delattr(shared.cmd_opts, name)
-
-
-@pytest.fixture
-def host(built_lib):
-    """(plugin, shared) on the CPU stub host."""
-    sh.install("cpu")
-    sh.set_device("cpu")
-    pl = sh.load_plugin()
-    _, shared = sh.host()
-    _clear(shared)
-    yield pl, shared
-    _clear(shared)
-
-
 def test_preload_option(host):
     pl, shared = host
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("mdtile_preload", os.path.join(PLUGIN, "preload.py"))
-    preload = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(preload)
     parser = argparse.ArgumentParser()
-    preload.preload(parser)
+    load_preload().preload(parser)
     assert parser.parse_args([]).mdtile_wrap_y is False
     ns = parser.parse_args(["--mdtile-wrap-y"])
     assert ns.mdtile_wrap_y is True and ns.mdtile_wrap_x is False
@@ -182,33 +161,6 @@ def test_preload_option(host):
 
 
 # ---- script wiring -----------------------------------------------------------------------------------------------------------
-def _gather_rects_double(x_in, rects_xy, w, h, repeat=1, tile_major=True):
-    """mdtile.gather_rects in torch (the engine's contract, mdtile/__init__.py): rectangles INSIDE x_in, or an error as the kernel's host check gives."""
-    H, W = x_in.shape[-2:]
-    for (x, y) in rects_xy:
-        assert 0 <= x and x + w <= W and 0 <= y and y + h <= H, f"rect ({x},{y},{w},{h}) outside {W}x{H}"
-    cat = torch.cat([x_in[:, :, y:y + h, x:x + w] for (x, y) in rects_xy], dim=0)
-    return cat.repeat_interleave(repeat, dim=0) if tile_major else cat.repeat([repeat, 1, 1, 1])
-
-
-@pytest.fixture
-def wired(host, monkeypatch):
-    pl, shared = host
-    monkeypatch.setattr(pl.engine, "weight_map_add_grid", lambda plan, tile_w, weights: None)
-    monkeypatch.setattr(pl.engine, "gather_rects", _gather_rects_double)
-    return pl, shared
-
-
-def _delegate(pl, W, H, tile_w, tile_h, ov, bs=4, method="md"):
-    cls = pl.multidiffusion.MultiDiffusion if method == "md" else pl.mixtureofdiffusers.MixtureOfDiffusers
-    p = sh.make_processing(W * 8, H * 8)
-    d = cls(p, sh.kdiff_sampler())
-    if method == "mod":
-        d.get_weight = lambda w, h: torch.ones(h, w)
-    d.init_grid_bbox(tile_w, tile_h, ov, bs)
-    return d, p
-
-
 def _info(p):
     return getattr(p, "extra_generation_params", None) or {}
 
@@ -239,7 +191,7 @@ def test_plan_choice_infotext_and_fallback(wired, capsys):
     d, p = _delegate(pl, 40, 24, 24, 24, 16)
     out = capsys.readouterr().out
     assert out.count("[Tiled Diffusion]") == 1 and "wrap-y" in out and "wrap-x" not in out
-    assert d.wrap_x and not d.wrap_y and d.wrap_ext_y == 0 and d.plan.bboxes == list(wr.grid(40, 24, 24, 24, 16, 4).boxes)
+    assert d.wrap_x and not d.wrap_y and d.wrap_ext_y == 0 and d.plan.bboxes == list(tr.grid(40, 24, 24, 24, 16, 4).boxes)
     assert _info(p)["Tiled Diffusion wrap x"] is True and "Tiled Diffusion wrap y" not in _info(p)
     # ... and the other way round: a tile as wide as the canvas drops wrap-x only
     d, p = _delegate(pl, 24, 40, 24, 24, 16)
@@ -290,13 +242,6 @@ def test_regions_are_refused(wired):
     d, _ = _delegate(pl, 40, 40, 24, 24, 16)
     with pytest.raises(RuntimeError, match="mdtile-wrap-x / --mdtile-wrap-y.*custom regions"):
         d.init_custom_bbox(settings, True, False)
-
-
-def _take(src, box, scale=1):
-    """The tile of `box` cut from src with both indices mod the source's size."""
-    x, y, w, h = (v * scale for v in box)
-    a = src.numpy()
-    return a[:, :, ((y + np.arange(h)) % a.shape[-2])[:, None], (x + np.arange(w)) % a.shape[-1]]
 
 
 def test_extended_copy_gains_rows_after_columns(wired):
@@ -380,22 +325,6 @@ def test_controlnet_and_stablesr_slices_of_seam_tiles(wired, kdiff):
 
 
 # ---- Tiled VAE ---------------------------------------------------------------------------------------------------------------
-def _hook(pl, net, ts, is_decoder):
-    import torch_engine as te
-    net.original_forward = net.forward
-    hook = pl.tilevae.VAEHook(net, ts, is_decoder=is_decoder, fast_decoder=True, fast_encoder=True, color_fix=False)
-    hook.engine, hook._pack, hook._sp_ops = te.TorchEngine(), te.TorchConv, te.TorchSeqParOps()
-    return hook
-
-
-def _pad_rows(z, P):
-    return torch.cat([z[..., -P:, :], z, z[..., :P, :]], dim=-2)
-
-
-def _pad_cols(z, P):
-    return torch.cat([z[..., -P:], z, z[..., :P]], dim=-1)
-
-
 # (decoder?, tile size, input shape): tiled paths, H and W both above two pads
 VAE_CASES = [(True, 16, (1, 4, 40, 24)), (False, 64, (1, 3, 200, 136))]
 

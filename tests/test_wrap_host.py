@@ -18,13 +18,40 @@ for _p in (ROOT, PLUGIN, os.path.join(ROOT, "tests")):
 
 from hostsim import stub_host as sh      # noqa: E402
 import wrap_ref as wr                    # noqa: E402
+from wrap_common import host, wired, delegate, load_preload, take as _take, cpu_vae_hook as _hook, pad_cols      # noqa: E402,F401
 
 # (W, H, requested tile_w, tile_h, overlap, tile_bs): the GPU cases of tests/test_gpu_wrap.py and a 1024-wide panorama
 GEOMETRIES = [(37, 20, 16, 12, 6, 4), (64, 16, 32, 32, 8, 2), (50, 12, 48, 48, 44, 4), (40, 24, 24, 24, 16, 2), (64, 24, 32, 32, 16, 3),
               (1024, 1024, 128, 128, 8, 8)]
+# The restatement pinned to literal numbers: geometry -> (xs, ys, min and max of the uniform weight map).  Computed once with the x-only
+# restatement this module used before tests/wrap_ref.py took the per-axis form (which then agreed with it bit for bit on weight maps, gather
+# and both blends for every geometry below).  The last three rows: the canvases of tests/test_gpu_wrap.py's 2- and 4-plane cases and of the
+# script-wiring tests.
+FROZEN = {
+    (37, 20, 16, 12, 6, 4): ((0, 9, 18, 27), (0, 4, 8), 1, 6),
+    (64, 16, 32, 32, 8, 2): ((0, 21, 42), (0,), 1, 2),
+    (50, 12, 48, 48, 44, 4): ((0, 3, 7, 11, 15, 19, 23, 26, 30, 34, 38, 42, 46), (0,), 12, 13),
+    (40, 24, 24, 24, 16, 2): ((0, 8, 16, 24, 32), (0,), 3, 3),
+    (64, 24, 32, 32, 16, 3): ((0, 16, 32, 48), (0,), 2, 2),
+    (1024, 1024, 128, 128, 8, 8): ((0, 113, 227, 341, 455, 568, 682, 796, 910), (0, 112, 224, 336, 448, 560, 672, 784, 896), 1, 4),
+    (512, 256, 96, 96, 48, 8): ((0, 46, 93, 139, 186, 232, 279, 325, 372, 418, 465), (0, 40, 80, 120, 160), 2, 9),
+    (1024, 256, 128, 128, 8, 8): ((0, 113, 227, 341, 455, 568, 682, 796, 910), (0, 64, 128), 1, 4),
+    (256, 64, 96, 96, 48, 4): ((0, 42, 85, 128, 170, 213), (0,), 2, 3),
+}
 
 
 # ---- plan --------------------------------------------------------------------------------------------------------------------
+def test_the_restatement_is_what_the_x_only_one_gave():
+    """Origins and coverage counts of every wrap-x geometry against literal numbers, so that the per-axis restatement is not pinned to itself."""
+    assert set(GEOMETRIES) <= set(FROZEN)
+    for geom, (xs, ys, lo, hi) in FROZEN.items():
+        g = wr.grid(*geom)
+        assert g == wr.grid(*geom, True, False) and (g.xs, g.ys) == (xs, ys), geom
+        m = wr.weight_map(g)
+        assert (m.min(), m.max()) == (lo, hi), geom
+        assert max(y + g.th for y in g.ys) == g.H, "plain rows: the last tile row is flush with the bottom edge"
+
+
 @pytest.mark.parametrize("geom", GEOMETRIES, ids=lambda g: "x".join(map(str, g)))
 def test_plan_matches_the_restatement(built_lib, geom):
     E = built_lib
@@ -69,26 +96,10 @@ def test_plan_refuses_a_tile_as_wide_as_the_canvas(built_lib):
 
 
 # ---- the option --------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def host(built_lib):
-    """(plugin, shared) on the CPU stub host, with the engine calls a delegate makes at init / per batch replaced by torch doubles."""
-    sh.install("cpu")
-    sh.set_device("cpu")
-    pl = sh.load_plugin()
-    _, shared = sh.host()
-    yield pl, shared
-    if hasattr(shared.cmd_opts, "mdtile_wrap_x"):
-        del shared.cmd_opts.mdtile_wrap_x
-
-
 def test_preload_option(host):
     pl, shared = host
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("mdtile_preload", os.path.join(PLUGIN, "preload.py"))
-    preload = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(preload)
     parser = argparse.ArgumentParser()
-    preload.preload(parser)
+    load_preload().preload(parser)
     assert parser.parse_args([]).mdtile_wrap_x is False
     assert parser.parse_args(["--mdtile-wrap-x"]).mdtile_wrap_x is True
     A = pl.abstractdiffusion.AbstractDiffusion
@@ -101,31 +112,8 @@ def test_preload_option(host):
 
 
 # ---- script wiring -----------------------------------------------------------------------------------------------------------
-def _gather_rects_double(x_in, rects_xy, w, h, repeat=1, tile_major=True):
-    """mdtile.gather_rects in torch (the engine's contract, mdtile/__init__.py): rectangles INSIDE x_in, or an error as the kernel's host check gives."""
-    H, W = x_in.shape[-2:]
-    for (x, y) in rects_xy:
-        assert 0 <= x and x + w <= W and 0 <= y and y + h <= H, f"rect ({x},{y},{w},{h}) outside {W}x{H}"
-    cat = torch.cat([x_in[:, :, y:y + h, x:x + w] for (x, y) in rects_xy], dim=0)
-    return cat.repeat_interleave(repeat, dim=0) if tile_major else cat.repeat([repeat, 1, 1, 1])
-
-
-@pytest.fixture
-def wired(host, monkeypatch):
-    pl, shared = host
-    monkeypatch.setattr(pl.engine, "weight_map_add_grid", lambda plan, tile_w, weights: None)
-    monkeypatch.setattr(pl.engine, "gather_rects", _gather_rects_double)
-    return pl, shared
-
-
 def _delegate(pl, W, H, tile, ov, bs=4, method="md"):
-    cls = pl.multidiffusion.MultiDiffusion if method == "md" else pl.mixtureofdiffusers.MixtureOfDiffusers
-    p = sh.make_processing(W * 8, H * 8)
-    d = cls(p, sh.kdiff_sampler())
-    if method == "mod":
-        d.get_weight = lambda w, h: torch.ones(h, w)
-    d.init_grid_bbox(tile, tile, ov, bs)
-    return d, p
+    return delegate(pl, W, H, tile, tile, ov, bs, method)
 
 
 def test_wrap_plan_only_with_the_option(wired, capsys):
@@ -192,15 +180,10 @@ def test_regions_are_refused(wired):
     assert d.enable_custom_bbox and len(d.custom_bboxes) == 1
 
 
-def _take(src, box, scale=1):
-    x, y, w, h = (v * scale for v in box)
-    return np.take(src.numpy()[:, :, y:y + h, :], x + np.arange(w), axis=-1, mode="wrap")
-
-
 @pytest.mark.parametrize("method", ["md", "mod"])
 def test_icond_slices_of_seam_tiles(wired, method):
     """img2img's image conditioning follows the tiles: repeat_cond_dict (MultiDiffusion) and the per-tile slice_icond (Mixture of Diffusers)
-    cut a tile that spans the seam from the extended copy -- equal to np.take(..., mode='wrap') of the source."""
+    cut a tile that spans the seam from the extended copy -- equal to the source indexed mod its size."""
     pl, shared = wired
     shared.cmd_opts.mdtile_wrap_x = True
     d, _ = _delegate(pl, 40, 24, 24, 16, bs=2, method=method)
@@ -255,14 +238,6 @@ def test_controlnet_and_stablesr_slices_of_seam_tiles(wired, kdiff):
 
 
 # ---- Tiled VAE ---------------------------------------------------------------------------------------------------------------
-def _hook(pl, net, ts, is_decoder):
-    import torch_engine as te
-    net.original_forward = net.forward
-    hook = pl.tilevae.VAEHook(net, ts, is_decoder=is_decoder, fast_decoder=True, fast_encoder=True, color_fix=False)
-    hook.engine, hook._pack, hook._sp_ops = te.TorchEngine(), te.TorchConv, te.TorchSeqParOps()
-    return hook
-
-
 # (decoder?, tile size, input shape, tiled?): padded inputs above and below the "tiny" threshold of the unchanged path
 VAE_CASES = [(True, 16, (1, 4, 24, 56), True), (True, 64, (1, 4, 24, 40), False), (False, 64, (1, 3, 136, 200), True), (False, 256, (1, 3, 96, 128), False)]
 
@@ -279,7 +254,7 @@ def test_vae_hook_pads_by_its_tile_pad_and_crops(host, capsys, is_decoder, ts, s
     z = torch.randn(*shape)
     with torch.no_grad():
         capsys.readouterr()
-        padded = hook(torch.cat([z[..., -P:], z, z[..., :P]], dim=-1))
+        padded = hook(pad_cols(z, P))
         assert ("tiny" in capsys.readouterr().out) == (not tiled)
         plain = hook(z)
         shared.cmd_opts.mdtile_wrap_x = True

@@ -60,6 +60,7 @@ int plan_upload(const struct ::mdtile_plan* plan);  // mirror the plan's lookup 
 
 static inline hipStream_t as_stream(mdtile_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // fp32 <-> storage type
 template <typename T> __device__ __forceinline__ float to_f32(T v);

@@ -2,6 +2,8 @@
 // written here and nowhere else.  The defining files include this header and define these functions by their qualified names
 // (`int mdt::conv_rec_launch(...)`), which only compiles against a matching declaration: a signature that drifts is a compile error.
 // (conv_rec2_launch and the probes-only conv_recd_* take the kernels' ConvRParams: conv_rec_common.h declares them next to it.)
+// The two 3x3 conv families take their launch as ONE struct with named fields (HandoverConvCall, RecConvCall); inside the defining files every
+// matrix-core family picks its kernel in one function that returns the function pointer, and launches it in one statement.
 #pragma once
 #include "common.h"
 
@@ -14,6 +16,9 @@ int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const
                 hipStream_t s);
 int wrap_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                int num_regions, hipStream_t s);
+
+// ---- plan.hip
+int device_cus();      // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached
 
 // ---- vae_conv_bf16x3.hip
 bool conv_bf16x3_eligible(int cout, int cin, int ksize);
@@ -28,10 +33,23 @@ int conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipSt
 bool conv_bf16x3_gn_supported(int cout, int cin, int ksize, int up);
 bool conv_bf16x3_stats_supported(int cout, int cin, int ksize, int up);
 size_t conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W);
-int conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part = nullptr, int w16 = 0);
-int conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
-                             hipStream_t s);
+// One hand-over 3x3 conv (fp32 NCHW in and out) as a C entry point (vae_conv.hip) hands it to conv_bf16x3_launch.  Host side only: the kernels
+// take ConvBParams.
+struct HandoverConvCall {
+    const float* x = nullptr;        // fp32 input
+    const void* w_rec = nullptr;     // split-bf16 record image of the weights (direct records, then the sub-pixel ones); w16: the fp16 plane
+    const float* bias = nullptr;
+    const float* res = nullptr;      // fp32 residual or null
+    float* y = nullptr;              // fp32 output
+    const float* coef = nullptr;     // fused GroupNorm + SiLU on the input, (a, s) per image and channel, or null (direct stride-1 kernels only)
+    double* d_part = nullptr;        // statistics of the output from the epilogue: the per-block partials (128-cout blocks with coef only)
+    int B = 0, cin = 0, cout = 0, H = 0, W = 0;      // H, W: OUTPUT size
+    int up = 0;                      // nearest-2x in front of the conv (sub-pixel kernels)
+    int stride = 1;                  // 2: ldm's Downsample, conv over pad(x, right 1, bottom 1); no residual, no coef
+    int Hin = 0, Win = 0;            // stride 2 only: the input size (H = (Hin - 2) / 2 + 1 does not determine it); else derived from H, W, up
+    int w16 = 0;                     // MDTILE_PRECISION_F16: w_rec is the fp16 weight plane -> the fp16 kernels (coef required, never up / stride 2)
+};
+int conv_bf16x3_launch(const HandoverConvCall& c, hipStream_t s);
 
 // ---- vae_conv1x1_bf16x3.hip
 bool conv1x1_bf16x3_eligible(int cout, int cin);

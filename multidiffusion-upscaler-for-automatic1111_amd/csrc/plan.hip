@@ -5,7 +5,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "launchers.h"
 
 namespace mdt {
 static thread_local char g_err[512] = "";
@@ -18,6 +18,17 @@ void set_error(const char* fmt, ...) {
 }  // namespace mdt
 
 extern "C" int mdtile_version(void) { return MDTILE_VERSION; }
+
+int mdt::device_cus() {
+    static const int n = [] {
+        int dev = 0, cus = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+            cus = prop.multiProcessorCount;
+        return cus;
+    }();
+    return n;
+}
 
 // ---- arithmetic of the matrix-core kernels: split-bf16 ("bf16x3") by default, exact fp32 MFMA or single bf16 on request ----
 // g_precision bits: 1 = convs on exact fp32, 2 = attention on exact fp32 (MDTILE_CONV_MODE / MDTILE_ATTN_MODE presets, either or both),

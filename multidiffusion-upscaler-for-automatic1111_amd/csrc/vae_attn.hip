@@ -218,6 +218,10 @@ static bool attn_takes_bf16x3(int C, int flags) { return !(flags & MDTILE_ATTN_E
 
 extern "C" int mdtile_vae_attn_takes_channel_major(int C, int flags) { return attn_takes_bf16x3(C, flags) ? 1 : 0; }
 
+// the exact-fp32 kernel of C = 128 / 256 / 512 (checked by the caller)
+using AttnExactKernel = void (*)(const float*, const float*, const float*, float*, int, float);
+static AttnExactKernel attn_exact_kernel(int C) { return C == 512 ? k_attn<4> : C == 256 ? k_attn<2> : k_attn<1>; }
+
 extern "C" int mdtile_vae_attn(const float* d_q, const float* d_k, const float* d_v, float* d_out, int B, int C, int T, float scale,
                                int flags, void* d_ws, mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_q && d_k && d_v && d_out, "mdtile_vae_attn: null argument");
@@ -230,9 +234,7 @@ extern "C" int mdtile_vae_attn(const float* d_q, const float* d_k, const float* 
     }
     MDT_CHECK_ARG(!(flags & MDTILE_ATTN_V_CHANNEL_MAJOR), "mdtile_vae_attn: the exact-fp32 kernel takes v token-major");
     dim3 grid((T + BM - 1) / BM, B), block(256);
-    if (C == 512) hipLaunchKernelGGL(k_attn<4>, grid, block, 0, s, d_q, d_k, d_v, d_out, T, scale);
-    else if (C == 256) hipLaunchKernelGGL(k_attn<2>, grid, block, 0, s, d_q, d_k, d_v, d_out, T, scale);
-    else hipLaunchKernelGGL(k_attn<1>, grid, block, 0, s, d_q, d_k, d_v, d_out, T, scale);
+    hipLaunchKernelGGL(attn_exact_kernel(C), grid, block, 0, s, d_q, d_k, d_v, d_out, T, scale);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

@@ -189,18 +189,15 @@ __global__ __launch_bounds__(256) void k_attn_combine(const float* __restrict__ 
 
 bool mdt::attn_bf16x3_eligible(int C) { return C == 128 || C == 256 || C == 512; }
 
+// The main kernel of a launch from (one-term arithmetic, C); C is one of attn_bf16x3_eligible (the C entry points have checked it)
+using AttnKernel = void (*)(const u32x4*, const u32x4*, const u32x4*, float*, int, int, int, int, float, int, float*, float*);
+static AttnKernel attn_kernel(bool one, int C) {
+    if (one) return C == 512 ? k_attn_bf16x1<512> : C == 256 ? k_attn_bf16x1<256> : k_attn_bf16x1<128>;
+    return C == 512 ? k_attn_bf16x3<512> : C == 256 ? k_attn_bf16x3<256> : k_attn_bf16x3<128>;
+}
+
 // Key-range split factor: 1 block per CU (133 KB LDS), so the launch runs in ceil(blocks / CUs) rounds; pick the smallest
 // nsplit <= 4 whose round occupancy is within 3 % of the best.  MDTILE_ATTN_SPLIT=n forces it.
-static int attn_num_cus() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-        return cus;
-    }();
-    return n;
-}
 static int attn_nsplit(int B, int Tq, int Tk) {
     static const int forced = [] { const char* e = probe_env("MDTILE_ATTN_SPLIT"); return e ? atoi(e) : 0; }();
     const int nkb = (Tk + 127) / 128;
@@ -213,8 +210,8 @@ static int attn_nsplit(int B, int Tq, int Tk) {
     const long long blocks = (Tq + 127) / 128;
     // launches that fill the chip several times over: 4 key ranges per query block keep the Q working set of an XCD
     // (32 / nsplit query blocks x C x 512 B) inside its L2 -- see the block mapping in k_attn_bf16x3
-    if (blocks >= 2 * attn_num_cus() && nkb >= 32) return 4;
-    const int cus = attn_num_cus();
+    const int cus = device_cus();
+    if (blocks >= 2 * cus && nkb >= 32) return 4;
     double eff[5], best = 0.0;
     for (int s = 1; s <= 4; ++s) {
         const long long rounds = (blocks * s + cus - 1) / cus;
@@ -262,15 +259,8 @@ int mdt::attn_bf16x3_launch(const float* d_q, const float* d_k, const float* d_v
     MDT_LAUNCH_CHECK();
     const int nq8 = (Tq128 / BQ + 7) / 8 * 8;
     dim3 grid(nq8 * ns, B), block(512);
-#define MDT_ATTN_LAUNCH(KN, CC) hipLaunchKernelGGL((KN<CC>), grid, block, 0, s, Qr, Kr, Vr, d_out, Tq, Tq128, Tk, Tk128, scale, ns, part, pstat)
-    if (mfma_single_term() || mode_f16()) {      // MDTILE_PRECISION_BF16, and the attention of MDTILE_PRECISION_F16: one bf16 MFMA per product
-        if (C == 512) MDT_ATTN_LAUNCH(k_attn_bf16x1, 512);
-        else if (C == 256) MDT_ATTN_LAUNCH(k_attn_bf16x1, 256);
-        else MDT_ATTN_LAUNCH(k_attn_bf16x1, 128);
-    } else if (C == 512) MDT_ATTN_LAUNCH(k_attn_bf16x3, 512);
-    else if (C == 256) MDT_ATTN_LAUNCH(k_attn_bf16x3, 256);
-    else MDT_ATTN_LAUNCH(k_attn_bf16x3, 128);
-#undef MDT_ATTN_LAUNCH
+    // MDTILE_PRECISION_BF16, and the attention of MDTILE_PRECISION_F16: one bf16 MFMA per product
+    hipLaunchKernelGGL(attn_kernel(mfma_single_term() || mode_f16(), C), grid, block, 0, s, Qr, Kr, Vr, d_out, Tq, Tq128, Tk, Tk128, scale, ns, part, pstat);
     MDT_LAUNCH_CHECK();
     if (ns > 1) {
         dim3 cgrid(cdiv(Tq, 256), C < 64 ? C : 64, B);

@@ -196,8 +196,6 @@ __global__ void k_conv_pack(const float* __restrict__ w, float* __restrict__ wp,
     wp[i] = co < Cout ? w[((size_t)co * Cin + ci) * KS * KS + tap] : 0.0f;  // OIHW, tap = ky*KS + kx
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // ---- conv_in (round 5): 3x3 convs with 3 or 4 input channels (the encoder's first conv 3 -> 128 on the IMAGE tile, the decoder's 4 -> 512 on the
 // latent tile; scripts/tilevae.py:115-137 'conv_in').  K = 27 / 36 leaves the matrix cores nothing to do -- the MFMA kernel above ran it at
 // 14 TFLOP/s, 4.3 ms per 3072^2 encoder tile -- and the op is its OUTPUT stream: 128 planes x 4 B per pixel.  Plain fp32 FMAs (exact fp32 in
@@ -298,29 +296,37 @@ __global__ __launch_bounds__(256) void k_conv3x3_fewcin(const float* __restrict_
 
 static bool conv_fewcin_eligible(int cin, int ksize, int up, int out_layout) { return ksize == 3 && (cin == 3 || cin == 4) && !up && out_layout == 0; }
 
-template <int KS, int KC, int WP, int WC, int RP, int RC, int MINB = 1>
+// S = 2: the stride-2 conv (NCHW output only)
+template <int KS, int KC, int WP, int WC, int RP, int RC, int MINB = 1, int S = 1>
 int launch_conv(ConvParams& P, int out_layout, hipStream_t s) {
     constexpr int BN = WC * RC * 32;
     P.PX = (P.W + 31) / 32;
     P.ptiles = P.PX * ((P.H + 7) / 8);
     P.NCB = (P.CoutP + BN - 1) / BN;
     dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, P.B), block(256);
-    if (out_layout == 1) hipLaunchKernelGGL((k_conv<KS, KC, WP, WC, RP, RC, true, 1, MINB>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_conv<KS, KC, WP, WC, RP, RC, false, 1, MINB>), grid, block, 0, s, P);
+    if (S == 1 && out_layout == 1) hipLaunchKernelGGL((k_conv<KS, KC, WP, WC, RP, RC, true, 1, MINB>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((k_conv<KS, KC, WP, WC, RP, RC, false, S, MINB>), grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
 
-template <int KC, int WP, int WC, int RP, int RC>
-int launch_conv_down2(ConvParams& P, hipStream_t s) {
-    constexpr int BN = WC * RC * 32;
-    P.PX = (P.W + 31) / 32;
-    P.ptiles = P.PX * ((P.H + 7) / 8);
-    P.NCB = (P.CoutP + BN - 1) / BN;
-    dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, P.B), block(256);
-    hipLaunchKernelGGL((k_conv<3, KC, WP, WC, RP, RC, false, 2>), grid, block, 0, s, P);
-    MDT_LAUNCH_CHECK();
-    return MDTILE_OK;
+// the exact-fp32 kernels' view of a conv: output H x W from input Hin x Win
+ConvParams conv_params(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int cin, int cout, int H, int W, int Hin,
+                       int Win, int up) {
+    ConvParams P;
+    P.x = x; P.w = w; P.bias = bias; P.res = res; P.y = y;
+    P.B = B; P.Cin = cin; P.Cout = cout; P.CoutP = round_up(cout, 32); P.H = H; P.W = W;
+    P.Hin = Hin; P.Win = Win; P.up = up;
+    return P;
+}
+
+// conv_in: the kernel from (cin, the PROBES twin's MDTILE_FEWCIN_FORM=1: the round-5 kernel, one copy of the weights, op_sel broadcasts; see above)
+using FewcinKernel = void (*)(const float*, const float*, const float*, const float*, float*, int, int, int, int, int);
+FewcinKernel fewcin_kernel(int cin) {
+    if constexpr (kProbes) {
+        if (const char* e = probe_env("MDTILE_FEWCIN_FORM"); e && atoi(e) == 1) return cin == 3 ? k_conv3x3_fewcin<3, 1> : k_conv3x3_fewcin<4, 1>;
+    }
+    return cin == 3 ? k_conv3x3_fewcin<3> : k_conv3x3_fewcin<4>;
 }
 
 }  // namespace
@@ -371,15 +377,15 @@ extern "C" int mdtile_conv2d(const float* d_x, const float* d_w_packed, const fl
     const int up = (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0;
     MDT_CHECK_ARG(!up || (H % 2 == 0 && W % 2 == 0), "mdtile_conv2d: upsample2x needs even output size, got %dx%d", H, W);
     MDT_CHECK_ARG((size_t)(up ? H / 2 : H) * (up ? W / 2 : W) < (1u << 31), "mdtile_conv2d: input plane of 2^31 or more pixels");
-    ConvParams P;
-    P.x = d_x; P.w = d_w_packed; P.bias = d_bias; P.res = d_residual; P.y = d_y;
-    P.B = B; P.Cin = cin; P.Cout = cout; P.CoutP = round_up(cout, 32); P.H = H; P.W = W;
-    P.Hin = up ? H / 2 : H; P.Win = up ? W / 2 : W; P.up = up;
     hipStream_t s = as_stream(stream);
     // split-bf16 matrix-core path (16/3 x the fp32-MFMA rate, ~1e-5 relative): default for the 3x3 convs it covers
     const bool force_f32 = conv_strict_f32();
-    if (!force_f32 && !(flags & MDTILE_CONV_EXACT_F32) && out_layout == 0 && conv_bf16x3_eligible(cout, cin, ksize))
-        return conv_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, up, nullptr, s);
+    if (!force_f32 && !(flags & MDTILE_CONV_EXACT_F32) && out_layout == 0 && conv_bf16x3_eligible(cout, cin, ksize)) {
+        HandoverConvCall c;
+        c.x = d_x; c.w_rec = d_w_packed + f32_packed_floats(cout, cin, ksize); c.bias = d_bias; c.res = d_residual; c.y = d_y;
+        c.B = B; c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.up = up;
+        return conv_bf16x3_launch(c, s);
+    }
     // 1x1 convs (nin_shortcut, q / k / proj_out): split-bf16 kernel over the flat pixel run
     if (ksize == 1 && !up && !force_f32 && !(flags & MDTILE_CONV_EXACT_F32) && out_layout == 0 && conv1x1_bf16x3_eligible(cout, cin))
         return conv1x1_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout,
@@ -388,19 +394,11 @@ extern "C" int mdtile_conv2d(const float* d_x, const float* d_w_packed, const fl
         const int ncb = (cout + 127) / 128;
         MDT_CHECK_ARG((size_t)B * ncb <= 65535 && (H + 3) / 4 <= 65535, "mdtile_conv2d: conv_in grid too large (B=%d cout=%d H=%d)", B, cout, H);
         dim3 grid((W + 127) / 128, (H + 3) / 4, B * ncb), block(256);
-        if constexpr (kProbes) {      // PROBES twin, MDTILE_FEWCIN_FORM=1: the round-5 kernel (one copy of the weights, op_sel broadcasts; see above)
-            if (const char* e = probe_env("MDTILE_FEWCIN_FORM"); e && atoi(e) == 1) {
-                if (cin == 3) hipLaunchKernelGGL((k_conv3x3_fewcin<3, 1>), grid, block, 0, s, d_x, d_w_packed, d_bias, d_residual, d_y, cout, P.CoutP, ncb, H, W);
-                else hipLaunchKernelGGL((k_conv3x3_fewcin<4, 1>), grid, block, 0, s, d_x, d_w_packed, d_bias, d_residual, d_y, cout, P.CoutP, ncb, H, W);
-                MDT_LAUNCH_CHECK();
-                return MDTILE_OK;
-            }
-        }
-        if (cin == 3) hipLaunchKernelGGL((k_conv3x3_fewcin<3>), grid, block, 0, s, d_x, d_w_packed, d_bias, d_residual, d_y, cout, P.CoutP, ncb, H, W);
-        else hipLaunchKernelGGL((k_conv3x3_fewcin<4>), grid, block, 0, s, d_x, d_w_packed, d_bias, d_residual, d_y, cout, P.CoutP, ncb, H, W);
+        hipLaunchKernelGGL(fewcin_kernel(cin), grid, block, 0, s, d_x, d_w_packed, d_bias, d_residual, d_y, cout, round_up(cout, 32), ncb, H, W);
         MDT_LAUNCH_CHECK();
         return MDTILE_OK;
     }
+    ConvParams P = conv_params(d_x, d_w_packed, d_bias, d_residual, d_y, B, cin, cout, H, W, up ? H / 2 : H, up ? W / 2 : W, up);
     const bool wide = P.CoutP > 64;
     if (ksize == 3) {
         // Block shape of the wide exact-fp32 conv (round 6, probes/convf32_probe.py, profiles/r6l): 8-channel slabs cost 95 KB of LDS and 288
@@ -427,21 +425,31 @@ extern "C" int mdtile_conv2d_gn_supported(int cout, int cin, int ksize, int flag
     return conv_bf16x3_gn_supported(cout, cin, ksize, (flags & MDTILE_CONV_UPSAMPLE2X) ? 1 : 0) ? 1 : 0;
 }
 
+// The call of conv_bf16x3_launch from what the two fused-norm entry points are given.  Checks the arguments they share (`who` names the entry
+// point in the error texts) and picks the weight image.
+static int gn_call(HandoverConvCall& c, const char* who, const float* d_x, const float* d_coef, const float* d_w_packed, const float* d_bias,
+                   const float* d_residual, float* d_y, int B, int cin, int cout, int H, int W, int ksize, int flags) {
+    const int w16 = (flags & MDTILE_CONV_W_F16) ? 1 : 0;
+    MDT_CHECK_ARG(d_x && d_coef && d_w_packed && d_y, "%s: null argument", who);
+    MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && H > 0 && W > 0, "%s: bad shape B=%d cin=%d cout=%d H=%d W=%d", who, B, cin, cout, H, W);
+    MDT_CHECK_ARG(!(w16 && (flags & MDTILE_CONV_EXACT_F32)),
+                  "%s: MDTILE_CONV_W_F16 (fp16 weight plane, one fp16 MFMA per product) contradicts MDTILE_CONV_EXACT_F32 (flags=%d)", who, flags);
+    MDT_CHECK_ARG(!w16 || mode_f16(), "%s: MDTILE_CONV_W_F16 (fp16 weight plane) outside MDTILE_PRECISION_F16 (mode %d)", who, mdtile_get_precision());
+    MDT_CHECK_ARG((size_t)H * W < (1u << 31), "%s: input plane of 2^31 or more pixels", who);
+    c.x = d_x; c.coef = d_coef; c.bias = d_bias; c.res = d_residual; c.y = d_y;
+    // w16: d_w_packed IS the fp16 plane -> the fp16 one-term kernel (the operand is silu(a x + s) by construction)
+    c.w_rec = w16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, ksize);
+    c.B = B; c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.w16 = w16;
+    return MDTILE_OK;
+}
+
 extern "C" int mdtile_conv2d_gn(const float* d_x, const float* d_coef, const float* d_w_packed, const float* d_bias, const float* d_residual,
                                 float* d_y, int B, int cin, int cout, int H, int W, int ksize, int flags, mdtile_stream_t stream) {
-    MDT_CHECK_ARG(d_x && d_coef && d_w_packed && d_y, "mdtile_conv2d_gn: null argument");
-    MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && H > 0 && W > 0, "mdtile_conv2d_gn: bad shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
-    MDT_CHECK_ARG(!((flags & MDTILE_CONV_W_F16) && (flags & MDTILE_CONV_EXACT_F32)),
-                  "mdtile_conv2d_gn: MDTILE_CONV_W_F16 (fp16 weight plane, one fp16 MFMA per product) contradicts MDTILE_CONV_EXACT_F32 (flags=%d)", flags);
+    HandoverConvCall c;
+    if (const int rc = gn_call(c, "mdtile_conv2d_gn", d_x, d_coef, d_w_packed, d_bias, d_residual, d_y, B, cin, cout, H, W, ksize, flags)) return rc;
     MDT_CHECK_ARG(mdtile_conv2d_gn_supported(cout, cin, ksize, flags, 0),
                   "mdtile_conv2d_gn: no fused pre-activation kernel for cout=%d cin=%d ksize=%d flags=%d (use mdtile_gn_apply + mdtile_conv2d)", cout, cin, ksize, flags);
-    MDT_CHECK_ARG((size_t)H * W < (1u << 31), "mdtile_conv2d_gn: input plane of 2^31 or more pixels");
-    if (flags & MDTILE_CONV_W_F16) {      // d_w_packed is the fp16 plane: the fp16 one-term kernel (the operand is silu(a x + s) by construction)
-        MDT_CHECK_ARG(mode_f16(), "mdtile_conv2d_gn: MDTILE_CONV_W_F16 (fp16 weight plane) outside MDTILE_PRECISION_F16 (mode %d)", mdtile_get_precision());
-        return conv_bf16x3_launch(d_x, d_w_packed, d_bias, d_residual, d_y, B, cin, cout, H, W, 0, d_coef, as_stream(stream), nullptr, 1);
-    }
-    return conv_bf16x3_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, 0, d_coef,
-                              as_stream(stream));
+    return conv_bf16x3_launch(c, as_stream(stream));
 }
 
 // ---- statistics of the output from the conv's own epilogue (slow mode: the input of a POOLED GroupNorm) ---------------------------------
@@ -468,20 +476,14 @@ extern "C" int mdtile_conv2d_gn_stats_supported(int cout, int cin, int ksize, in
 extern "C" int mdtile_conv2d_gn_stats(const float* d_x, const float* d_coef, const float* d_w_packed, const float* d_bias, const float* d_residual,
                                       float* d_y, int B, int cin, int cout, int H, int W, int ksize, int flags, int groups, float* d_mean,
                                       float* d_var, void* d_ws, mdtile_stream_t stream) {
-    MDT_CHECK_ARG(d_x && d_coef && d_w_packed && d_y && d_mean && d_var && d_ws, "mdtile_conv2d_gn_stats: null argument");
-    MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && H > 0 && W > 0, "mdtile_conv2d_gn_stats: bad shape B=%d cin=%d cout=%d H=%d W=%d", B, cin, cout, H, W);
-    MDT_CHECK_ARG(!((flags & MDTILE_CONV_W_F16) && (flags & MDTILE_CONV_EXACT_F32)),
-                  "mdtile_conv2d_gn_stats: MDTILE_CONV_W_F16 (fp16 weight plane, one fp16 MFMA per product) contradicts MDTILE_CONV_EXACT_F32 (flags=%d)", flags);
+    MDT_CHECK_ARG(d_mean && d_var && d_ws, "mdtile_conv2d_gn_stats: null argument");
+    HandoverConvCall c;
+    if (const int rc = gn_call(c, "mdtile_conv2d_gn_stats", d_x, d_coef, d_w_packed, d_bias, d_residual, d_y, B, cin, cout, H, W, ksize, flags)) return rc;
     MDT_CHECK_ARG(mdtile_conv2d_gn_stats_supported(cout, cin, ksize, flags, groups),
                   "mdtile_conv2d_gn_stats: no statistics kernel for cout=%d cin=%d ksize=%d flags=%d groups=%d (use mdtile_conv2d_gn + mdtile_gn_stats)", cout, cin, ksize, flags, groups);
-    MDT_CHECK_ARG((size_t)H * W < (1u << 31), "mdtile_conv2d_gn_stats: input plane of 2^31 or more pixels");
-    double* d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
+    double* d_part = c.d_part = reinterpret_cast<double*>(static_cast<char*>(d_ws) + mdtile_gn_stats_ws_size(B, groups));
     hipStream_t s = as_stream(stream);
-    const int w16 = (flags & MDTILE_CONV_W_F16) ? 1 : 0;
-    MDT_CHECK_ARG(!w16 || mode_f16(), "mdtile_conv2d_gn_stats: MDTILE_CONV_W_F16 (fp16 weight plane) outside MDTILE_PRECISION_F16 (mode %d)", mdtile_get_precision());
-    const int rc = conv_bf16x3_launch(d_x, w16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, ksize), d_bias, d_residual, d_y, B, cin, cout, H, W, 0,
-                                      d_coef, s, d_part, w16);
-    if (rc != MDTILE_OK) return rc;
+    if (const int rc = conv_bf16x3_launch(c, s)) return rc;
     const int units = ((W + 31) / 32) * ((H + 7) / 8);
     return conv_stats_finish_launch(d_part, B, cout, (size_t)H * W, units, cout / 128, 32, groups, d_mean, d_var, d_ws, s);
 }
@@ -638,14 +640,15 @@ extern "C" int mdtile_conv2d_down2(const float* d_x, const float* d_w_packed, co
     MDT_CHECK_ARG(B > 0 && B <= 65535 && cin > 0 && cout > 0 && Hin >= 2 && Win >= 2, "mdtile_conv2d_down2: bad shape B=%d cin=%d cout=%d Hin=%d Win=%d",
                   B, cin, cout, Hin, Win);
     MDT_CHECK_ARG((size_t)Hin * Win < (1u << 31), "mdtile_conv2d_down2: input plane of 2^31 or more pixels");
-    if (!conv_strict_f32() && conv_bf16x3_eligible(cout, cin, 3))      // split-bf16 stride-2 kernel (vae_conv_bf16x3.hip, S = 2)
-        return conv_bf16x3_down2_launch(d_x, d_w_packed + f32_packed_floats(cout, cin, 3), d_bias, d_y, B, cin, cout, Hin, Win, as_stream(stream));
-    ConvParams P;
-    P.x = d_x; P.w = d_w_packed; P.bias = d_bias; P.res = nullptr; P.y = d_y;
-    P.B = B; P.Cin = cin; P.Cout = cout; P.CoutP = round_up(cout, 32);
-    P.H = (Hin - 2) / 2 + 1; P.W = (Win - 2) / 2 + 1;
-    P.Hin = Hin; P.Win = Win; P.up = 0;
+    const int H = (Hin - 2) / 2 + 1, W = (Win - 2) / 2 + 1;
     hipStream_t s = as_stream(stream);
-    if (P.CoutP > 64) return launch_conv_down2<8, 2, 2, 4, 2>(P, s);
-    return launch_conv_down2<8, 4, 1, 2, 1>(P, s);
+    if (!conv_strict_f32() && conv_bf16x3_eligible(cout, cin, 3)) {      // split-bf16 stride-2 kernel (vae_conv_bf16x3.hip, S = 2)
+        HandoverConvCall c;
+        c.x = d_x; c.w_rec = d_w_packed + f32_packed_floats(cout, cin, 3); c.bias = d_bias; c.y = d_y;
+        c.B = B; c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.stride = 2; c.Hin = Hin; c.Win = Win;
+        return conv_bf16x3_launch(c, s);
+    }
+    ConvParams P = conv_params(d_x, d_w_packed, d_bias, nullptr, d_y, B, cin, cout, H, W, Hin, Win, 0);
+    if (P.CoutP > 64) return launch_conv<3, 8, 2, 2, 4, 2, 1, 2>(P, 0, s);
+    return launch_conv<3, 8, 4, 1, 2, 1, 1, 2>(P, 0, s);
 }

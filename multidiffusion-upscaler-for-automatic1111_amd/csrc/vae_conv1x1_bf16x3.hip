@@ -126,8 +126,6 @@ __global__ void k_conv1x1_pack_bf16x3(const float* __restrict__ w, u32x4* __rest
     out[i] = __builtin_bit_cast(u32x4, o);
 }
 
-inline int round_up1(int v, int m) { return (v + m - 1) / m * m; }
-
 }  // namespace
 
 bool mdt::conv1x1_bf16x3_eligible(int cout, int cin) { return cin % 32 == 0 && cout >= 32; }
@@ -149,16 +147,28 @@ static bool conv1x1_stream_on() {
 }
 
 size_t mdt::conv1x1_bf16x3_packed_floats(int cout, int cin) {
-    const int MT = conv1x1_mt(cout), NCB = round_up1(cout, MT * 32) / (MT * 32), NP = cin / 32;
+    const int MT = conv1x1_mt(cout), NCB = round_up(cout, MT * 32) / (MT * 32), NP = cin / 32;
     return (size_t)NCB * NP * 2 * 2 * MT * 64 * 4;
 }
 
 int mdt::conv1x1_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
-    const int MT = conv1x1_mt(cout), NCB = round_up1(cout, MT * 32) / (MT * 32), NP = cin / 32;
+    const int MT = conv1x1_mt(cout), NCB = round_up(cout, MT * 32) / (MT * 32), NP = cin / 32;
     const size_t n = (size_t)NCB * NP * 2 * 2 * MT * 64;
     hipLaunchKernelGGL(k_conv1x1_pack_bf16x3, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_oihw, (u32x4*)d_out, cout, cin, MT, NCB, NP);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
+}
+
+// The streaming kernel takes whole blocks of couts (MT = 4: k_conv1x1_stream<2>, 8: <4>) over 16-byte rows of a wide image
+static bool conv1x1_streams(int MT, int cout, size_t HW) { return MT >= 4 && cout % (MT * 32) == 0 && HW % 4 == 0 && HW >= 2048 && conv1x1_stream_on(); }
+
+// The kernel of a launch from (streaming, one-term arithmetic, MT) and the pixel strip of its blocks
+using Conv1Kernel = void (*)(const Conv1Params);
+static Conv1Kernel conv1x1_kernel(bool stream, bool one, int MT, int& strip) {
+    strip = stream ? (MT == 4 ? 512 : 256) : (MT == 4 ? 128 : 256);
+    if (stream) return one ? (MT == 4 ? k_conv1x1_stream1t<2> : k_conv1x1_stream1t<4>) : (MT == 4 ? k_conv1x1_stream<2> : k_conv1x1_stream<4>);
+    if (one) return MT == 8 ? k_conv1x1_bf16x1<8, 256> : MT == 4 ? k_conv1x1_bf16x1<4, 128> : k_conv1x1_bf16x1<2, 256>;
+    return MT == 8 ? k_conv1x1_bf16x3<8, 256> : MT == 4 ? k_conv1x1_bf16x3<4, 128> : k_conv1x1_bf16x3<2, 256>;
 }
 
 int mdt::conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
@@ -166,36 +176,17 @@ int mdt::conv1x1_bf16x3_launch(const float* d_x, const void* d_w_rec, const floa
     // MDTILE_PRECISION_F16: q / k / v / proj_out of the attention (the caller says so: MDTILE_CONV_ATTN_PROJ) run one-term bf16 like the attention
     // itself; every other 1x1 conv (nin_shortcut) reads the raw stream and keeps its three terms
     const bool one = mfma_single_term() || (attn_proj && mode_f16());
+    const int MT = conv1x1_mt(cout);
+    int strip;
+    const Conv1Kernel kernel = conv1x1_kernel(conv1x1_streams(MT, cout, HW), one, MT, strip);
     Conv1Params P;
     P.x = d_x; P.w = (const u32x4*)d_w_rec; P.bias = d_bias; P.res = d_res; P.y = d_y;
     P.B = B; P.Cin = cin; P.Cout = cout; P.HW = HW;
-    const int MT = conv1x1_mt(cout);
-    if (MT >= 4 && cout % (MT * 32) == 0 && HW % 4 == 0 && HW >= 2048 && conv1x1_stream_on()) {
-        const int SPX = MT == 4 ? 512 : 256;
-        P.ptiles = (int)((HW + SPX - 1) / SPX);
-        P.NCB = cout / (MT * 32);
-        P.NP = cin / 32;
-        dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-        if (one) {      // MDTILE_PRECISION_BF16
-            if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream1t<2>, grid, block, 0, s, P);
-            else hipLaunchKernelGGL(k_conv1x1_stream1t<4>, grid, block, 0, s, P);
-        } else if (MT == 4) hipLaunchKernelGGL(k_conv1x1_stream<2>, grid, block, 0, s, P);
-        else hipLaunchKernelGGL(k_conv1x1_stream<4>, grid, block, 0, s, P);
-        MDT_LAUNCH_CHECK();
-        return MDTILE_OK;
-    }
-    const int PXT = MT == 4 ? 128 : 256;
-    P.ptiles = (int)((HW + PXT - 1) / PXT);
-    P.NCB = round_up1(cout, MT * 32) / (MT * 32);
+    P.ptiles = (int)((HW + strip - 1) / strip);
+    P.NCB = round_up(cout, MT * 32) / (MT * 32);
     P.NP = cin / 32;
     dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-    if (one) {
-        if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x1<8, 256>), grid, block, 0, s, P);
-        else if (MT == 4) hipLaunchKernelGGL((k_conv1x1_bf16x1<4, 128>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv1x1_bf16x1<2, 256>), grid, block, 0, s, P);
-    } else if (MT == 8) hipLaunchKernelGGL((k_conv1x1_bf16x3<8, 256>), grid, block, 0, s, P);
-    else if (MT == 4) hipLaunchKernelGGL((k_conv1x1_bf16x3<4, 128>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_conv1x1_bf16x3<2, 256>), grid, block, 0, s, P);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

@@ -225,8 +225,6 @@ __global__ void k_upconv_pack_bf16x3(const float* __restrict__ w, u32x4* __restr
     out[i] = __builtin_bit_cast(u32x4, o);
 }
 
-inline int round_up_i(int v, int m) { return (v + m - 1) / m * m; }
-
 }  // namespace
 
 // shapes the split-bf16 3x3 kernel takes; everything else stays on the exact-fp32 kernel
@@ -238,11 +236,11 @@ static int conv_bf16x3_perm(int cin) { return cin % 32 == 0 ? 1 : 0; }
 
 // record image = [ direct 3x3 records (9 taps) | sub-pixel upsample records (4 parities x 4 merged taps) ]
 size_t mdt::conv_bf16x3_direct_records(int cout, int cin) {
-    const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
+    const int MT = conv_bf16x3_mt(cout), NCB = round_up(cout, MT * 32) / (MT * 32), NK = cin / 16;
     return (size_t)NCB * NK * 3 * 2 * 3 * MT * 64;
 }
 static size_t upconv_records(int cout, int cin) {
-    const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
+    const int MT = conv_bf16x3_mt(cout), NCB = round_up(cout, MT * 32) / (MT * 32), NK = cin / 16;
     return (size_t)2 * NCB * NK * 2 * 2 * 2 * 2 * MT * 64;
 }
 size_t mdt::conv_bf16x3_packed_floats(int cout, int cin) {   // size of the record array in floats (4 per 16-byte record)
@@ -250,7 +248,7 @@ size_t mdt::conv_bf16x3_packed_floats(int cout, int cin) {   // size of the reco
 }
 
 int mdt::conv_bf16x3_pack(const float* d_w_oihw, void* d_out, int cout, int cin, hipStream_t s) {
-    const int MT = conv_bf16x3_mt(cout), NCB = round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16, perm = conv_bf16x3_perm(cin);
+    const int MT = conv_bf16x3_mt(cout), NCB = round_up(cout, MT * 32) / (MT * 32), NK = cin / 16, perm = conv_bf16x3_perm(cin);
     const size_t n = conv_bf16x3_direct_records(cout, cin);
     hipLaunchKernelGGL(k_conv_pack_bf16x3, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_oihw, (u32x4*)d_out, cout, cin, MT, NCB, NK, perm);
     MDT_LAUNCH_CHECK();
@@ -279,10 +277,10 @@ size_t mdt::conv_f16_plane_floats(int cout, int cin) {
 }
 int mdt::conv_f16_pack(const float* d_w_f32img, void* d_out, int cout, int cin, hipStream_t s) {
     const bool narrow = conv_rec_narrow_eligible(cout, cin, 3);
-    const int MT = narrow ? 1 : conv_bf16x3_mt(cout), NCB = narrow ? 1 : round_up_i(cout, MT * 32) / (MT * 32), NK = cin / 16;
+    const int MT = narrow ? 1 : conv_bf16x3_mt(cout), NCB = narrow ? 1 : round_up(cout, MT * 32) / (MT * 32), NK = cin / 16;
     const int perm = narrow ? 1 : conv_bf16x3_perm(cin);
     const size_t n = (size_t)NCB * NK * 3 * 2 * 3 * MT * 64;
-    hipLaunchKernelGGL(k_conv_pack_f16, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_f32img, (u32x4*)d_out, cout, cin, round_up_i(cout, 32), MT, NCB, NK,
+    hipLaunchKernelGGL(k_conv_pack_f16, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, d_w_f32img, (u32x4*)d_out, cout, cin, round_up(cout, 32), MT, NCB, NK,
                        perm);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
@@ -301,84 +299,41 @@ size_t mdt::conv_bf16x3_stats_part_doubles(int B, int cout, int H, int W) {
     return (size_t)B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * (cout / 128) * 64;
 }
 
-int mdt::conv_bf16x3_launch(const float* d_x, const void* d_w_rec, const float* d_bias, const float* d_res, float* d_y, int B, int cin,
-                       int cout, int H, int W, int up, const float* d_coef, hipStream_t s, double* d_part, int w16) {
-    // w16 (MDTILE_PRECISION_F16, fused pre-activation only): d_w_rec is the fp16 weight plane -> k_conv3x3_f16
-    MDT_CHECK_ARG(!w16 || (d_coef && !up), "conv_bf16x3_launch: the fp16 form exists for the fused pre-activation conv only");
-    ConvBParams P;
-    P.perm = conv_bf16x3_perm(cin);
-    P.coef = d_coef;
-    P.gn_part = d_part;
-    P.x = d_x; P.w = (const u32x4*)d_w_rec; P.bias = d_bias; P.res = d_res; P.y = d_y;
-    P.B = B; P.Cin = cin; P.Cout = cout; P.H = H; P.W = W;
-    P.Hin = up ? H / 2 : H; P.Win = up ? W / 2 : W; P.up = up;
-    const int MT = conv_bf16x3_mt(cout);
-    P.NCB = round_up_i(cout, MT * 32) / (MT * 32);
-    P.NK = cin / 16;
-    dim3 block(512);
-    if (up) {   // fused nearest-2x: sub-pixel form (four 2x2 convs on the input grid)
-        P.w = (const u32x4*)d_w_rec + conv_bf16x3_direct_records(cout, cin);
-        P.PX = (P.Win + TW - 1) / TW;
-        P.ptiles = P.PX * ((P.Hin + TH - 1) / TH);
-        dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB * 2, B);
-        if (mfma_single_term()) {
-            if (MT == 4) hipLaunchKernelGGL(k_upconv_bf16x1<4>, grid, block, 0, s, P);
-            else hipLaunchKernelGGL(k_upconv_bf16x1<2>, grid, block, 0, s, P);
-        } else if (MT == 4) hipLaunchKernelGGL(k_upconv_bf16x3<4>, grid, block, 0, s, P);
-        else hipLaunchKernelGGL(k_upconv_bf16x3<2>, grid, block, 0, s, P);
-        MDT_LAUNCH_CHECK();
-        return MDTILE_OK;
-    }
-    P.PX = (W + TW - 1) / TW;
-    P.ptiles = P.PX * ((H + TH - 1) / TH);
-    dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B);
-    MDT_CHECK_ARG(!d_part || (MT == 4 && d_coef && cout % 128 == 0), "conv_bf16x3_launch: no statistics kernel for cout=%d", cout);
-    if (w16) {
-        if (MT == 4 && d_part) hipLaunchKernelGGL((k_conv3x3_f16<4, true, 1, true>), grid, block, 0, s, P);
-        else if (MT == 4) hipLaunchKernelGGL((k_conv3x3_f16<4, true>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_f16<2, true>), grid, block, 0, s, P);
-    } else if (mfma_single_term()) {      // MDTILE_PRECISION_BF16: the one-term forms of the same instantiations
-        if (MT == 4) {
-            if (d_coef && d_part) hipLaunchKernelGGL((k_conv3x3_bf16x1<4, true, 1, true>), grid, block, 0, s, P);
-            else if (d_coef) hipLaunchKernelGGL((k_conv3x3_bf16x1<4, true>), grid, block, 0, s, P);
-            else hipLaunchKernelGGL((k_conv3x3_bf16x1<4, false>), grid, block, 0, s, P);
-        } else {
-            if (d_coef) hipLaunchKernelGGL((k_conv3x3_bf16x1<2, true>), grid, block, 0, s, P);
-            else hipLaunchKernelGGL((k_conv3x3_bf16x1<2, false>), grid, block, 0, s, P);
-        }
-    } else if (MT == 4) {
-        if (d_coef && d_part) hipLaunchKernelGGL((k_conv3x3_bf16x3<4, true, 1, true>), grid, block, 0, s, P);
-        else if (d_coef) hipLaunchKernelGGL((k_conv3x3_bf16x3<4, true>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_bf16x3<4, false>), grid, block, 0, s, P);
-    } else {
-        if (d_coef) hipLaunchKernelGGL((k_conv3x3_bf16x3<2, true>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_bf16x3<2, false>), grid, block, 0, s, P);
-    }
-    MDT_LAUNCH_CHECK();
-    return MDTILE_OK;
+// The kernel of a launch from the seven facts that tell the instantiations apart: upsample, one-term arithmetic (MDTILE_PRECISION_BF16), the fp16
+// weight plane, couts per block (MT x 32), fused pre-activation, statistics, stride.  conv_bf16x3_launch has refused every combination that has no kernel.
+using ConvBKernel = void (*)(const ConvBParams);
+static ConvBKernel conv_b_kernel(int up, bool one, int w16, int MT, bool gn, bool st, int stride) {
+    const bool m4 = MT == 4;
+    if (up) return one ? (m4 ? k_upconv_bf16x1<4> : k_upconv_bf16x1<2>) : (m4 ? k_upconv_bf16x3<4> : k_upconv_bf16x3<2>);
+    if (stride == 2) return one ? (m4 ? k_conv3x3_bf16x1<4, false, 2> : k_conv3x3_bf16x1<2, false, 2>) : (m4 ? k_conv3x3_bf16x3<4, false, 2> : k_conv3x3_bf16x3<2, false, 2>);
+    if (w16) return st ? k_conv3x3_f16<4, true, 1, true> : m4 ? k_conv3x3_f16<4, true> : k_conv3x3_f16<2, true>;
+    if (one) return st ? k_conv3x3_bf16x1<4, true, 1, true> : gn ? (m4 ? k_conv3x3_bf16x1<4, true> : k_conv3x3_bf16x1<2, true>) : (m4 ? k_conv3x3_bf16x1<4, false> : k_conv3x3_bf16x1<2, false>);
+    return st ? k_conv3x3_bf16x3<4, true, 1, true> : gn ? (m4 ? k_conv3x3_bf16x3<4, true> : k_conv3x3_bf16x3<2, true>) : (m4 ? k_conv3x3_bf16x3<4, false> : k_conv3x3_bf16x3<2, false>);
 }
 
-// ldm Downsample (encoder): conv3x3 stride 2 over pad(x, right 1, bottom 1); output (Hin - 2) / 2 + 1 rows / columns
-int mdt::conv_bf16x3_down2_launch(const float* d_x, const void* d_w_rec, const float* d_bias, float* d_y, int B, int cin, int cout, int Hin, int Win,
-                             hipStream_t s) {
+int mdt::conv_bf16x3_launch(const HandoverConvCall& c, hipStream_t s) {
+    const int cin = c.cin, cout = c.cout, up = c.up, down = c.stride == 2, MT = conv_bf16x3_mt(cout);
+    MDT_CHECK_ARG(c.stride == 1 || (down && !up && !c.res && !c.coef), "conv_bf16x3_launch: the stride-2 conv takes no upsample, residual or pre-activation (stride=%d)", c.stride);
+    MDT_CHECK_ARG(!(up && c.coef), "conv_bf16x3_launch: no fused pre-activation in the sub-pixel upsample kernel");
+    // w16 (MDTILE_PRECISION_F16, fused pre-activation only): w_rec is the fp16 weight plane -> k_conv3x3_f16
+    MDT_CHECK_ARG(!c.w16 || (c.coef && !up), "conv_bf16x3_launch: the fp16 form exists for the fused pre-activation conv only");
+    MDT_CHECK_ARG(!c.d_part || (MT == 4 && c.coef && !up && cout % 128 == 0), "conv_bf16x3_launch: no statistics kernel for cout=%d", cout);
+    const ConvBKernel kernel = conv_b_kernel(up, mfma_single_term(), c.w16, MT, c.coef != nullptr, c.d_part != nullptr, c.stride);
     ConvBParams P;
     P.perm = conv_bf16x3_perm(cin);
-    P.coef = nullptr;
-    P.gn_part = nullptr;
-    P.x = d_x; P.w = (const u32x4*)d_w_rec; P.bias = d_bias; P.res = nullptr; P.y = d_y;
-    P.B = B; P.Cin = cin; P.Cout = cout; P.H = (Hin - 2) / 2 + 1; P.W = (Win - 2) / 2 + 1;
-    P.Hin = Hin; P.Win = Win; P.up = 0;
-    const int MT = conv_bf16x3_mt(cout);
-    P.NCB = round_up_i(cout, MT * 32) / (MT * 32);
+    P.coef = c.coef;
+    P.gn_part = c.d_part;
+    // (up: the sub-pixel records, four 2x2 convs on the input grid, follow the direct ones)
+    P.x = c.x; P.w = (const u32x4*)c.w_rec + (up ? conv_bf16x3_direct_records(cout, cin) : 0); P.bias = c.bias; P.res = c.res; P.y = c.y;
+    P.B = c.B; P.Cin = cin; P.Cout = cout; P.H = c.H; P.W = c.W;
+    P.Hin = down ? c.Hin : up ? c.H / 2 : c.H; P.Win = down ? c.Win : up ? c.W / 2 : c.W; P.up = up;
+    P.NCB = round_up(cout, MT * 32) / (MT * 32);
     P.NK = cin / 16;
-    P.PX = (P.W + TW - 1) / TW;
-    P.ptiles = P.PX * ((P.H + TH - 1) / TH);
-    dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB, B), block(512);
-    if (mfma_single_term()) {
-        if (MT == 4) hipLaunchKernelGGL((k_conv3x3_bf16x1<4, false, 2>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_conv3x3_bf16x1<2, false, 2>), grid, block, 0, s, P);
-    } else if (MT == 4) hipLaunchKernelGGL((k_conv3x3_bf16x3<4, false, 2>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_conv3x3_bf16x3<2, false, 2>), grid, block, 0, s, P);
+    // pixel tiles of 8 x 32 on the OUTPUT grid; sub-pixel form: on the INPUT grid, once per row parity
+    P.PX = ((up ? P.Win : c.W) + TW - 1) / TW;
+    P.ptiles = P.PX * (((up ? P.Hin : c.H) + TH - 1) / TH);
+    dim3 grid(((P.ptiles + 7) / 8) * 8 * P.NCB * (up ? 2 : 1), c.B), block(512);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, P);
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

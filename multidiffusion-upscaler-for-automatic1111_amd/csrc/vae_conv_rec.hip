@@ -273,14 +273,7 @@ static int num_cus() {
         const int n = atoi(e);
         if (n >= 8) return n / 8 * 8;
     }
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-        return cus;
-    }();
-    return n;
+    return device_cus();
 }
 
 // Which kernel family takes a launch.  The two-blocks-per-CU kernels (vae_conv_rec2.hip) lose 3-12 % on launches that fill the chip many

@@ -176,9 +176,11 @@ def test_upconv_window_one_term(plugin, cuda, blocks):
 
 
 @pytest.mark.parametrize("B,cin,cout,H,W,up", [(1, 512, 512, 33, 47, False), (2, 256, 128, 20, 70, False), (1, 128, 256, 18, 40, True),
-                                               (1, 512, 512, 21, 33, True)])
+                                               (1, 512, 512, 21, 33, True),
+                                               (2, 32, 64, 9, 33, False),       # 64-cout blocks (k_conv3x3_bf16x1<2, false>): two K-steps, ragged tiles, batch 2
+                                               (2, 32, 64, 9, 33, True)])       # 64-cout blocks of the sub-pixel kernel (k_upconv_bf16x1<2>): 9 x 33 -> 18 x 66
 def test_fp32_handover_conv_one_term(plugin, cuda, B, cin, cout, H, W, up):
-    """k_conv3x3_bf16x1 / k_upconv_bf16x1: fp32 input, split while staging, hi half only."""
+    """k_conv3x3_bf16x1 / k_upconv_bf16x1: fp32 input, split while staging, hi half only.  (H, W: the INPUT size.)"""
     E = plugin.engine
     torch.manual_seed(cin + W)
     conv = torch.nn.Conv2d(cin, cout, 3, 1, 1)
@@ -190,7 +192,55 @@ def test_fp32_handover_conv_one_term(plugin, cuda, B, cin, cout, H, W, up):
     _check_exact(f"fp32 hand-over conv {(B, cin, cout, H, W, up)}", one, three, ref)
 
 
-@pytest.mark.parametrize("B,cin,cout,H,W", [(1, 128, 128, 64, 90), (1, 256, 256, 41, 57), (2, 512, 512, 32, 32)])
+def _coef(B, C, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.cat([torch.rand(B, 1, C, generator=g) * 1.5 + 0.25, torch.randn(B, 1, C, generator=g) * 0.5], dim=1).contiguous()
+
+
+def _activated_hi(E, x, coef):
+    """bf16_rn(silu(a x + s)) exactly as the kernels round it: the hi plane of the activated record image (rec_from_f32 runs the same fp32
+    activation code as the fused staging), read out by a one-term record conv with unit weights -- 1.0 x hi and nothing else per output."""
+    C = x.shape[1]
+    w = torch.zeros(128, C, 3, 3, device=x.device)
+    w[torch.arange(C), torch.arange(C), 1, 1] = 1.0
+    ident = E.PackedConv(w, torch.zeros(128, device=x.device))
+    with E.precision(E.PRECISION_BF16):
+        hi = ident.call_rec(E.rec_from_f32(x, coef), want_f32=True)[0][:, :C]
+        torch.cuda.synchronize()
+    assert torch.equal(hi, hi.to(torch.bfloat16).float())
+    return hi
+
+
+@pytest.mark.parametrize("B,cin,cout,H,W,res,stats", [(2, 32, 128, 9, 33, True, False),      # k_conv3x3_bf16x1<4, true>
+                                                      (1, 32, 64, 9, 33, False, False),      # <2, true>: 64-cout blocks
+                                                      (1, 32, 128, 9, 33, True, True)])      # <4, true, 1, true>: statistics in the epilogue
+def test_fp32_handover_conv_with_pre_gn_one_term(plugin, cuda, B, cin, cout, H, W, res, stats):
+    """The fused GroupNorm + SiLU forms of k_conv3x3_bf16x1: fp32 input, activated in fp32 and rounded to bf16 while staging."""
+    E = plugin.engine
+    torch.manual_seed(cin + cout + W)
+    conv = torch.nn.Conv2d(cin, cout, 3, 1, 1)
+    x, coef = torch.randn(B, cin, H, W).to(cuda), _coef(B, cin, cout + 1).to(cuda)
+    r = torch.randn(B, cout, H, W).to(cuda) if res else None
+    pc = E.PackedConv(conv.weight.detach().to(cuda), conv.bias.detach().to(cuda))
+    assert pc.fuses_pre_gn() and (not stats or pc.leaves_stats(32))
+    ref = F.conv2d(_activated_hi(E, x, coef).double().cpu(), _bf(conv.weight), conv.bias.detach().double(), padding=1)
+    if res:
+        ref = ref + r.double().cpu()
+    with E.precision(E.PRECISION_BF16):
+        if stats:
+            one, (var, mean) = pc.call_stats(x, coef, residual=r)
+        else:
+            one = pc(x, residual=r, pre_gn=coef)
+        torch.cuda.synchronize()
+    three = pc.call_stats(x, coef, residual=r)[0] if stats else pc(x, residual=r, pre_gn=coef)
+    _check_exact(f"fp32 hand-over conv + pre_gn {(B, cin, cout, H, W, res, stats)}", one, three, ref)
+    if stats:
+        v_ref, m_ref = vo.get_var_mean(one.double(), 32)
+        assert _rel(mean, m_ref) < 1e-5 and _rel(var, v_ref) < 1e-5
+
+
+@pytest.mark.parametrize("B,cin,cout,H,W", [(1, 128, 128, 64, 90), (1, 256, 256, 41, 57), (2, 512, 512, 32, 32),
+                                            (2, 32, 64, 19, 67)])      # 64-cout blocks (k_conv3x3_bf16x1<2, false, 2>): 19 x 67 -> 9 x 33, batch 2
 def test_stride2_conv_one_term(plugin, cuda, B, cin, cout, H, W):
     E = plugin.engine
     torch.manual_seed(cin + H)
@@ -204,7 +254,9 @@ def test_stride2_conv_one_term(plugin, cuda, B, cin, cout, H, W):
 
 
 @pytest.mark.parametrize("B,cin,cout,H,W,res", [(1, 512, 512, 64, 64, True), (1, 256, 128, 48, 48, False), (2, 128, 256, 40, 60, True),
-                                                (1, 256, 128, 10, 12, False)])
+                                                (1, 256, 128, 10, 12, False),
+                                                (1, 64, 256, 5, 7, True),        # small-image kernel, 256-cout blocks (k_conv1x1_bf16x1<8, 256>), ragged pixel tile
+                                                (2, 64, 64, 5, 7, False)])       # ... 64-cout blocks (<2, 256>), batch 2
 def test_conv1x1_one_term(plugin, cuda, B, cin, cout, H, W, res):
     """k_conv1x1_stream1t (HW >= 2048) and k_conv1x1_bf16x1 (the small-image kernel)."""
     E = plugin.engine

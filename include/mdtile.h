@@ -227,6 +227,36 @@ int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, int C, int 
 int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args, const float* d_partial,
                           const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Tile skipping (img2img inpainting): run only the grid tiles a mask touches.  Nothing upstream corresponds to it.
+ *
+ * mdtile_tile_activity: d_mask fp32 [planes, H, W], d_active int32[T] on the device.  active[t] = 1 iff some element of
+ *   mask[:, y_t:y_t+th, x_t:x_t+tw] is not equal to zero, tested as !(v == 0.0f): NaN, denormals, negatives and fractions count, +0.0 and -0.0
+ *   do not; else 0.  One launch writes every entry (no pre-clearing).  Plain plans only (a wrap or sparse plan: MDTILE_E_ARG).
+ * mdtile_plan_create_subset: h_active = T host ints (non-zero = active).  The result is a SPARSE plan: the parent's geometry (w, h, tile, overlap,
+ *   cols, rows, origins, covering tables -- copied: the parent may be destroyed first) plus two device tables, slot[t] = rank of tile t among the
+ *   active tiles in ascending tile index or -1, and the list of active tile indices.  Batching is the usual rule on the active count Ta:
+ *   num_batches = ceil(Ta / tile_bs), tile_bs := ceil(Ta / num_batches).  NULL + mdtile_last_error for Ta == 0, a wrap plan or a sparse plan as
+ *   parent, num_batches > MDTILE_MAX_BATCHES.  Ta == T is allowed.  Destroyed with mdtile_plan_destroy.
+ * mdtile_plan_active: returns Ta and fills ids[Ta] (ascending parent tile indices; ids may be NULL); 0 on a plan that is not sparse.
+ * On a sparse plan mdtile_plan_info reports num_tiles = Ta with the new num_batches / tile_bs (cols, rows: the parent's) and mdtile_plan_bboxes
+ *   lists the Ta active boxes in ascending parent index.  mdtile_gather / mdtile_gather_all fill the COMPACT batches: active tile number s (its
+ *   slot) occupies rows (s mod tile_bs) * N ... of batch s / tile_bs; each tile's values are as on the parent.
+ * mdtile_blend_sparse: batch_out[b] = model output of compact batch b; d_fill [N,C,H,W] of args->dtype, required.  A pixel is LIVE iff every grid
+ *   tile of the parent that covers it is active.  At a live pixel the output equals, bit for bit, what mdtile_blend writes there on the parent
+ *   plan given the same outputs for the active tiles (covering tiles in ascending tile index, fp32 accumulation from +0.0, MoD term
+ *   out * (tile_w * rescale[y,x]), MD epilogue weights > 1 ? buf / weights : buf, rounded once; d_weights / d_rescale are the PARENT's full maps).
+ *   At any other pixel the output is the bit pattern of d_fill[n,c,y,x] and no tile output is read for it.  args->flags must be 0,
+ *   row_lo = row_hi = 0; there are no regions.
+ * REFUSED on a sparse plan (MDTILE_E_ARG, the text names the reason): mdtile_blend, mdtile_blend_finalize, mdtile_blend_dispatch,
+ *   mdtile_gather_range, mdtile_weight_map_add_grid (the weight maps belong to the parent).
+ * -------------------------------------------------------------------------------------------------------- */
+int mdtile_tile_activity(const mdtile_plan* plan, const float* d_mask, int planes, int* d_active, mdtile_stream_t stream);
+mdtile_plan* mdtile_plan_create_subset(const mdtile_plan* parent, const int* h_active, int tile_bs);
+int mdtile_plan_active(const mdtile_plan* plan, int* ids);
+int mdtile_blend_sparse(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                        const void* d_fill, mdtile_stream_t stream);
+
 /* Per-region initial noise (scripts/tilediffusion.py:486-529, create_random_tensors_hijack): d_noise [N,C,H,W] fp32 is the job's
  * noise, updated in place.  regions[i].out = the region's own noise [1,C,h,w] fp32 (drawn by the host with the region's CPU
  * seed, shared by all N samples), .mode = MDTILE_REGION_BG / _FG, .weight unused.  Per layer: sum + hit count over the regions

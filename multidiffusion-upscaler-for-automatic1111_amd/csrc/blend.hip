@@ -828,6 +828,7 @@ int fill_params(BlendParams& P, const mdtile_plan* p, const mdtile_blend_args* a
 
 extern "C" int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                             const mdtile_region* regions, int num_regions, mdtile_stream_t stream) {
+    MDT_CHECK_ARG(!(plan && plan_sparse(plan)), "mdtile_blend: refused on a sparse plan: it leaves tiles out, the blend for it is mdtile_blend_sparse");
     if (plan && plan_wraps(plan)) return wrap_blend(plan, args, batch_out, num_batches, num_regions, as_stream(stream));   // wrap.hip
     BlendParams P;
     int rc = fill_params(P, plan, args, batch_out, num_batches, regions, num_regions);
@@ -843,6 +844,7 @@ extern "C" int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* ar
 extern "C" int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, int C, int flags, int num_batches, int ptrs_aligned16,
                                      int row_lo, int row_hi, int* info8) {
     MDT_CHECK_ARG(plan && info8, "mdtile_blend_dispatch: null argument");
+    MDT_CHECK_ARG(!plan_sparse(plan), "mdtile_blend_dispatch: a sparse plan has one blend kernel of its own (sparse.hip), not k_blend / k_blend_lds");
     MDT_CHECK_ARG(!plan_wraps(plan), "mdtile_blend_dispatch: a %s plan has one blend kernel of its own (wrap.hip), not k_blend / k_blend_lds", wrap_kind(plan));
     MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_blend_dispatch: bad N=%d C=%d", N, C);
     MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_blend_dispatch: bad dtype %d", dtype);
@@ -868,6 +870,7 @@ extern "C" int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, 
 extern "C" int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args, const float* d_partial,
                                      const mdtile_region* regions, int num_regions, mdtile_stream_t stream) {
     BlendParams P;
+    MDT_CHECK_ARG(!(plan && plan_sparse(plan)), "mdtile_blend_finalize: refused on a sparse plan: tile skipping is not combined with the multi-GPU partial path");
     MDT_CHECK_ARG(!(plan && plan_wraps(plan)), "mdtile_blend_finalize: refused on a %s plan: wrap-around is not combined with the multi-GPU partial path",
                   wrap_kind(plan));
     MDT_CHECK_ARG(d_partial, "mdtile_blend_finalize: null partial buffer");
@@ -920,7 +923,8 @@ extern "C" int mdtile_gather(const mdtile_plan* p, int dtype, int N, int C, cons
     void* ptrs[MDTILE_MAX_BATCHES] = {nullptr};
     ptrs[batch_id] = d_x_tile;
     int t_lo = batch_id * p->tile_bs;
-    int t_hi = t_lo + p->tile_bs < p->T ? t_lo + p->tile_bs : p->T;
+    int t_hi = t_lo + p->tile_bs < plan_tiles(p) ? t_lo + p->tile_bs : plan_tiles(p);
+    if (plan_sparse(p)) return sparse_gather(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, as_stream(stream));   // sparse.hip: active slots
     if (plan_wraps(p)) return wrap_gather(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, as_stream(stream));   // wrap.hip
     return gather_common(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, 0, as_stream(stream));
 }
@@ -928,6 +932,11 @@ extern "C" int mdtile_gather(const mdtile_plan* p, int dtype, int N, int C, cons
 extern "C" int mdtile_gather_all(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs,
                                  int num_batches, mdtile_stream_t stream) {
     MDT_CHECK_ARG(p && batch_ptrs, "mdtile_gather_all: null argument");
+    if (plan_sparse(p)) {   // sparse.hip; the compact batches of the active tiles, no packed destination
+        MDT_CHECK_ARG(num_batches == p->num_batches, "mdtile_gather_all: %d batches given, the sparse plan has %d (it has no packed form)", num_batches,
+                      p->num_batches);
+        return sparse_gather(p, dtype, N, C, d_x_in, batch_ptrs, num_batches, 0, p->Ta, as_stream(stream));
+    }
     if (plan_wraps(p)) {   // wrap.hip; no packed destination there
         MDT_CHECK_ARG(num_batches == p->num_batches, "mdtile_gather_all: %d batches given, the %s plan has %d (it has no packed form)", num_batches,
                       wrap_kind(p), p->num_batches);
@@ -943,6 +952,7 @@ extern "C" int mdtile_gather_all(const mdtile_plan* p, int dtype, int N, int C, 
 extern "C" int mdtile_gather_range(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* d_packed, int tile_lo,
                                    int tile_hi, mdtile_stream_t stream) {
     MDT_CHECK_ARG(p && d_packed, "mdtile_gather_range: null argument");
+    MDT_CHECK_ARG(!plan_sparse(p), "mdtile_gather_range: refused on a sparse plan: tile skipping is not combined with the multi-GPU path (tile ranges, packed buffers)");
     MDT_CHECK_ARG(!plan_wraps(p), "mdtile_gather_range: refused on a %s plan: wrap-around is not combined with the multi-GPU path (tile ranges, packed buffers)",
                   wrap_kind(p));
     MDT_CHECK_ARG(tile_lo >= 0 && tile_hi <= p->T && tile_lo <= tile_hi, "mdtile_gather_range: bad tile range [%d,%d) of %d", tile_lo, tile_hi, p->T);

@@ -149,6 +149,12 @@ struct mdtile_plan {
     // column 0).  Likewise ys[r] + th, rowrange[y] and rowinfo[y].x on a wrapped y axis.  An axis that does not wrap keeps the plain origins
     // (origins_1d) and its runs never pass the end of the list.  Whenever either flag is set the .y .z .w of BOTH records are unused (zero).
     int wrap_x, wrap_y;
+    // mdtile_plan_create_subset: a SPARSE plan is the parent's geometry and tables above (T stays the parent's cols * rows)
+    // plus two tables behind rowinfo in the same block: slot[T] = rank of tile t among the active tiles in ascending index, or -1, and
+    // active[Ta] = the active tile indices.  num_batches / tile_bs batch the Ta active tiles.  Ta == 0: not a sparse plan.
+    int Ta;
+    size_t slot_off;          // offset (ints) of slot inside the block; active follows it
+    int *d_slot, *d_active;   // device mirror (mdt::plan_upload)
 };
 
 namespace mdt {
@@ -156,4 +162,8 @@ namespace mdt {
 static inline bool plan_wraps(const ::mdtile_plan* p) { return p->wrap_x || p->wrap_y; }
 // what an error text calls such a plan
 static inline const char* wrap_kind(const ::mdtile_plan* p) { return !p->wrap_y ? "wrap-x" : p->wrap_x ? "wrap-x + wrap-y (torus)" : "wrap-y"; }
+// a plan of the active tiles only (mdtile_plan_create_subset): sparse.hip's kernels take it, and what they do not do is refused by name
+static inline bool plan_sparse(const ::mdtile_plan* p) { return p->Ta > 0; }
+// the tiles a plan hands to the model: the active ones of a sparse plan, else all
+static inline int plan_tiles(const ::mdtile_plan* p) { return p->Ta > 0 ? p->Ta : p->T; }
 }  // namespace mdt

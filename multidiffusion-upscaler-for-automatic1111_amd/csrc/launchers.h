@@ -17,6 +17,11 @@ int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const
 int wrap_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                int num_regions, hipStream_t s);
 
+// ---- sparse.hip: sparse plans (mdtile_plan_create_subset), the tiles an inpaint mask touches; the public gather entry points hand such a plan
+// (mdt::plan_sparse) to sparse_gather, which fills the compact batches of the active slots [s_lo, s_hi)
+int sparse_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi,
+                  hipStream_t s);
+
 // ---- plan.hip
 int device_cus();      // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached
 

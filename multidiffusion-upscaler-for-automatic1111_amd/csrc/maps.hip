@@ -99,6 +99,7 @@ extern "C" int mdtile_feather_mask(int w, int h, double ratio, float* d_out, mdt
 
 extern "C" int mdtile_weight_map_add_grid(const mdtile_plan* p, const float* d_tile_w, float* d_weights, mdtile_stream_t stream) {
     MDT_CHECK_ARG(p && d_weights, "mdtile_weight_map_add_grid: null argument");
+    MDT_CHECK_ARG(!plan_sparse(p), "mdtile_weight_map_add_grid: refused on a sparse plan: the weight maps belong to the parent plan (every tile counts)");
     if (plan_wraps(p)) return wrap_weight_map(p, d_tile_w, d_weights, as_stream(stream));   // wrap.hip
     if (int rc = plan_upload(p)) return rc;
     int n = p->w * p->h;

@@ -277,6 +277,60 @@ extern "C" mdtile_plan* mdtile_plan_create_wrap_x(int w, int h, int tile_w, int 
 extern "C" int mdtile_plan_wrap_x(const mdtile_plan* p) { return p && p->wrap_x ? 1 : 0; }
 extern "C" int mdtile_plan_wrap_y(const mdtile_plan* p) { return p && p->wrap_y ? 1 : 0; }
 
+// ---- the tiles an inpaint mask touches ------------------------------------------------------------------------------------
+// The parent's geometry and covering tables, copied (the parent may be destroyed first), plus slot[T] and active[Ta] behind them.
+extern "C" mdtile_plan* mdtile_plan_create_subset(const mdtile_plan* parent, const int* h_active, int tile_bs) {
+    if (!parent || !h_active || tile_bs <= 0) {
+        mdt::set_error("mdtile_plan_create_subset: bad arguments (null parent / flags, or tile_bs=%d)", tile_bs);
+        return nullptr;
+    }
+    if (mdt::plan_wraps(parent)) {
+        mdt::set_error("mdtile_plan_create_subset: the parent is a %s plan: tile skipping is not combined with wrap-around", mdt::wrap_kind(parent));
+        return nullptr;
+    }
+    if (mdt::plan_sparse(parent)) {
+        mdt::set_error("mdtile_plan_create_subset: the parent is a sparse plan itself: take the subset of the full plan");
+        return nullptr;
+    }
+    int Ta = 0;
+    for (int t = 0; t < parent->T; ++t) Ta += h_active[t] ? 1 : 0;
+    if (Ta == 0) {
+        mdt::set_error("mdtile_plan_create_subset: no active tile (Ta == 0 of %d): there is nothing to run", parent->T);
+        return nullptr;
+    }
+    const int nb = (Ta + tile_bs - 1) / tile_bs;
+    if (nb > MDTILE_MAX_BATCHES) {
+        mdt::set_error("mdtile_plan_create_subset: %d batches > MDTILE_MAX_BATCHES=%d (a sparse plan has no packed form: raise the tile batch size)", nb,
+                       MDTILE_MAX_BATCHES);
+        return nullptr;
+    }
+    mdtile_plan* p = new mdtile_plan(*parent);
+    p->Ta = Ta;
+    p->num_batches = nb;
+    p->tile_bs = (Ta + nb - 1) / nb;
+    p->slot_off = parent->table_len;                       // a multiple of 4 ints: quad_off is, and both record tables are
+    p->table_len = p->slot_off + (size_t)parent->T + (size_t)Ta;
+    p->h_table = new int[p->table_len]();
+    memcpy(p->h_table, parent->h_table, parent->table_len * sizeof(int));
+    p->h_xs = p->h_table;
+    p->h_ys = p->h_table + p->cols;
+    int* slot = p->h_table + p->slot_off;
+    int* active = slot + p->T;
+    for (int t = 0, s = 0; t < p->T; ++t) {
+        slot[t] = h_active[t] ? s : -1;
+        if (h_active[t]) active[s++] = t;
+    }
+    p->d_xs = p->d_ys = p->d_colrange = p->d_rowrange = p->d_slot = p->d_active = nullptr;   // its own device mirror, made on first use
+    p->d_colquad = p->d_rowinfo = nullptr;
+    return p;
+}
+
+extern "C" int mdtile_plan_active(const mdtile_plan* p, int* ids) {
+    if (!p || !mdt::plan_sparse(p)) return 0;
+    if (ids) memcpy(ids, p->h_table + p->slot_off + p->T, (size_t)p->Ta * sizeof(int));
+    return p->Ta;
+}
+
 namespace mdt {
 int plan_upload(const mdtile_plan* cp) {
     mdtile_plan* p = const_cast<mdtile_plan*>(cp);
@@ -292,6 +346,10 @@ int plan_upload(const mdtile_plan* cp) {
     p->d_xs = d; p->d_ys = d + p->cols; p->d_colrange = p->d_ys + p->rows; p->d_rowrange = p->d_colrange + p->w;
     p->d_colquad = reinterpret_cast<int4*>(d + p->quad_off);          // hipMalloc is 256-B aligned, quad_off % 4 == 0
     p->d_rowinfo = p->d_colquad + (p->w + 3) / 4;
+    if (plan_sparse(p)) {
+        p->d_slot = d + p->slot_off;
+        p->d_active = p->d_slot + p->T;
+    }
     return MDTILE_OK;
 }
 }  // namespace mdt
@@ -305,13 +363,21 @@ extern "C" void mdtile_plan_destroy(mdtile_plan* p) {
 
 extern "C" int mdtile_plan_info(const mdtile_plan* p, int* info8) {
     MDT_CHECK_ARG(p && info8, "mdtile_plan_info: null argument");
-    info8[0] = p->cols; info8[1] = p->rows; info8[2] = p->T; info8[3] = p->num_batches;
+    info8[0] = p->cols; info8[1] = p->rows; info8[2] = mdt::plan_tiles(p); info8[3] = p->num_batches;
     info8[4] = p->tile_bs; info8[5] = p->tw; info8[6] = p->th; info8[7] = p->ov;
     return MDTILE_OK;
 }
 
 extern "C" int mdtile_plan_bboxes(const mdtile_plan* p, int* xywh) {
     MDT_CHECK_ARG(p && xywh, "mdtile_plan_bboxes: null argument");
+    if (mdt::plan_sparse(p)) {   // the active boxes, ascending parent index
+        const int* active = p->h_table + p->slot_off + p->T;
+        for (int s = 0; s < p->Ta; ++s) {
+            int* o = xywh + 4 * s;
+            o[0] = p->h_xs[active[s] % p->cols]; o[1] = p->h_ys[active[s] / p->cols]; o[2] = p->tw; o[3] = p->th;
+        }
+        return MDTILE_OK;
+    }
     for (int r = 0; r < p->rows; ++r)
         for (int c = 0; c < p->cols; ++c) {
             int* o = xywh + 4 * (r * p->cols + c);

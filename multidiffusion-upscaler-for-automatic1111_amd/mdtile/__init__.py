@@ -93,6 +93,10 @@ _SIGNATURES = {
     "mdtile_blend": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_blend_dispatch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _IP]),
     "mdtile_blend_finalize": (c_int, [c_void_p, POINTER(_BlendArgs), c_void_p, POINTER(_Region), c_int, c_void_p]),
+    "mdtile_tile_activity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mdtile_plan_create_subset": (c_void_p, [c_void_p, _IP, c_int]),
+    "mdtile_plan_active": (c_int, [c_void_p, _IP]),
+    "mdtile_blend_sparse": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
@@ -289,7 +293,12 @@ class Plan:
     wrap_x: the canvas is closed in x (panoramas, mdtile_plan_create_wrap): tile columns lie on a circle, a box's x + w may pass the canvas
     width (its columns are taken mod w), clamp is always on.  A tile as wide as the canvas raises MdtileError.
     wrap_y: the same for the rows; with wrap_x the canvas is a torus (seamless textures).  A box's y + h may pass the canvas height; a tile as
-    tall as the canvas raises MdtileError."""
+    tall as the canvas raises MdtileError.
+    sparse: a plan of the tiles an inpaint mask touches (Plan.subset): the parent's geometry, `active_ids` = the parent tile indices it runs,
+    bboxes / batches / num_tiles / num_batches / tile_bs of those tiles only; `parent_tiles` = the parent's tile count."""
+
+    sparse = False
+    active_ids: Tuple[int, ...] = ()
 
     def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, clamp: bool = True, wrap_x: bool = False,
                  wrap_y: bool = False):
@@ -309,11 +318,42 @@ class Plan:
         (self.cols, self.rows, self.num_tiles, self.num_batches, self.tile_bs, self.tile_w, self.tile_h,
          self.overlap) = list(info)
         self.w, self.h = int(w), int(h)
+        self.parent_tiles = self.num_tiles
+        self._read_boxes()
+
+    def _read_boxes(self):
+        L = lib()
         buf = (c_int * (4 * self.num_tiles))()
         _check(L.mdtile_plan_bboxes(self._h, buf), "mdtile_plan_bboxes")
         flat = list(buf)
         self.bboxes = [tuple(flat[4 * i:4 * i + 4]) for i in range(self.num_tiles)]  # (x, y, w, h), upstream order
         self.batches = [self.bboxes[i * self.tile_bs:(i + 1) * self.tile_bs] for i in range(self.num_batches)]
+
+    def subset(self, active: Sequence[int], tile_bs: int) -> "Plan":
+        """The sparse plan of the tiles with a non-zero flag in `active` (one flag per tile, as tile_activity returns them), batched by
+        `tile_bs`: gather / gather_all fill its compact batches and blend_sparse blends them.  Raises MdtileError when no tile is active, on a
+        wrap-around or sparse parent and beyond MAX_BATCHES batches.  The result does not depend on this plan staying alive."""
+        L = lib()
+        if len(active) != self.parent_tiles:
+            raise MdtileError(f"Plan.subset: {len(active)} flags for {self.parent_tiles} tiles")
+        flags = (c_int * max(1, len(active)))(*[1 if a else 0 for a in active])
+        h = L.mdtile_plan_create_subset(self._h, flags, int(tile_bs))
+        if not h:
+            raise MdtileError("mdtile_plan_create_subset: " + L.mdtile_last_error().decode(errors="replace"))
+        sub = Plan.__new__(Plan)
+        sub._h = h
+        sub.sparse, sub.wrap_x, sub.wrap_y = True, False, False
+        sub.w, sub.h, sub.parent_tiles = self.w, self.h, self.parent_tiles
+        info = (c_int * 8)()
+        _check(L.mdtile_plan_info(h, info), "mdtile_plan_info")
+        (sub.cols, sub.rows, sub.num_tiles, sub.num_batches, sub.tile_bs, sub.tile_w, sub.tile_h, sub.overlap) = list(info)
+        ids = (c_int * sub.num_tiles)()
+        n = L.mdtile_plan_active(h, ids)
+        if n != sub.num_tiles:
+            raise MdtileError(f"mdtile_plan_active: {n} active tiles, mdtile_plan_info reports {sub.num_tiles}")
+        sub.active_ids = tuple(ids)
+        sub._read_boxes()
+        return sub
 
     @property
     def handle(self):
@@ -323,6 +363,19 @@ class Plan:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
             _lib.mdtile_plan_destroy(h)
+
+
+def tile_activity(plan: Plan, mask: torch.Tensor) -> List[int]:
+    """Per tile of the (plain) plan: 1 when some element of mask[:, y:y+h, x:x+w] is not equal to zero (NaN counts, -0.0 does not), else 0.
+    mask: fp32 [P, H, W] (or [H, W]) on the device.  One launch and one device-to-host copy of num_tiles ints."""
+    _dev_tensor(mask, "mask", torch.float32)
+    if mask.dim() == 2:
+        mask = mask.unsqueeze(0)
+    if mask.dim() != 3 or tuple(mask.shape[-2:]) != (plan.h, plan.w):
+        raise MdtileError(f"tile_activity: mask {tuple(mask.shape)} is not [planes, {plan.h}, {plan.w}]")
+    flags = torch.empty(plan.parent_tiles, dtype=torch.int32, device=mask.device)
+    _check(lib().mdtile_tile_activity(plan.handle, _p(mask), int(mask.shape[0]), _p(flags), _stream()), "mdtile_tile_activity")
+    return flags.cpu().tolist()
 
 
 # ---- maps ------------------------------------------------------------------------------------------------------------
@@ -798,6 +851,33 @@ def blend(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C:
     """One fused launch replacing the scatter/normalise/feather op sequence of sample_one_step / apply_model_hijack."""
     return BlendCall(plan, method, batch_out, N, C, weights=weights, tile_w=tile_w, rescale=rescale, regions=regions, out=out, dtype=dtype,
                      device=device, partial=partial, tile_range=tile_range, row_range=row_range, packed=packed)()
+
+
+def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, fill: torch.Tensor, weights=None, tile_w=None,
+                 rescale=None, out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
+    """The blend of a sparse plan (Plan.subset): batch_out = the model outputs of its compact batches.  Where every covering tile of the parent
+    is active the result is blend()'s on the parent, bit for bit; everywhere else it is `fill` ([N, C, H, W], the outputs' dtype), bit for bit.
+    weights / rescale are the parent's full maps."""
+    if not plan.sparse:
+        raise MdtileError("blend_sparse needs a sparse plan (Plan.subset); the blend of a full plan is blend()")
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    _dev_tensor(fill, "fill", dtype)
+    assert tuple(fill.shape) == (N, C, plan.h, plan.w), f"fill {tuple(fill.shape)}"
+    if out is None:
+        out = torch.empty((N, C, plan.h, plan.w), dtype=dtype, device=device)
+    _dev_tensor(out, "out", dtype)
+    for nm, t in (("weights", weights), ("tile_w", tile_w), ("rescale", rescale)):
+        if t is not None:
+            _dev_tensor(t, nm, torch.float32)
+    a = _BlendArgs(method, dtype_code(dtype), N, C, 0, 0, 0, 0, 0, _p(weights).value, _p(tile_w).value, _p(rescale).value, out.data_ptr())
+    ptrs = (c_void_p * max(1, len(batch_out)))(*[t.data_ptr() for t in batch_out])
+    _check(lib().mdtile_blend_sparse(plan.handle, ctypes.byref(a), ptrs, len(batch_out), _p(fill), _stream()), "mdtile_blend_sparse")
+    return out
 
 
 class StreamCopyCall:

@@ -31,3 +31,9 @@ def preload(parser):
         help="Tiled VAE decoder: cross-fade neighbouring tiles over PX image pixels per side of a tile border (1-88; 16-32 is a sensible range), out "
              "of the padding that is otherwise decoded and thrown away, instead of pasting the tiles edge to edge. Every decoded tile is kept "
              "until the image is assembled. Default: not set, edge to edge.")
+    parser.add_argument(
+        "--mdtile-inpaint-skip", action="store_true",
+        help="img2img inpainting with Tiled Diffusion (MultiDiffusion, Mixture of Diffusers): run the model only on the grid tiles that the job's "
+             "latent mask touches. Relies on the host replacing the model output by the init latent wherever the mask is zero, as the webui's "
+             "CFGDenoiser does; the masked area comes out bit-identical. Not applied with region control, wrap-around, Noise Inversion's own "
+             "evaluations or DemoFusion. Default: off, every tile runs.")

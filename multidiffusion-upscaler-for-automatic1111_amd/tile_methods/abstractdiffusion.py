@@ -39,6 +39,9 @@ except Exception:  # pragma: no cover
 
 class AbstractDiffusion:
 
+    # why get_noise never skips tiles (--mdtile-inpaint-skip)
+    NOISE_INVERSION_FULL = "Noise Inversion's own evaluations (get_noise) stay full-canvas"
+
     def __init__(self, p, sampler):
         self.method = type(self).__name__
         self.p = p
@@ -75,6 +78,11 @@ class AbstractDiffusion:
         self.wrap_y = False
         self.wrap_ext_y = 0
         self._wrap_copies: Dict[str, tuple] = {}
+        # --mdtile-inpaint-skip: decided on the job's first full-size evaluation (inpaint_skip), when the host has computed p.nmask
+        self.skip_mode: Optional[str] = None         # None = not decided yet | "full" | "sparse" | "empty" (the mask touches no tile)
+        self.sparse_plan: Optional[mdtile.Plan] = None
+        self.sparse_batched_bboxes: List[List[BBox]] = []
+        self._skip_notes: set = set()
 
         # region prompt control
         self.enable_custom_bbox = False
@@ -200,8 +208,15 @@ class AbstractDiffusion:
         """--mdtile-wrap-y (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_wrap_y", False))
 
+    @staticmethod
+    def inpaint_skip_requested() -> bool:
+        """--mdtile-inpaint-skip (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_inpaint_skip", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
+        self.requested_tile_bs = int(tile_bs)
+        self.skip_mode, self.sparse_plan, self.sparse_batched_bboxes = None, None, []      # a new grid: the mask is read again
         # clamps (tile <= canvas; overlap <= min(requested tile) - 4), origins and batching all happen in the plan
         self.wrap_x = False
         if self.wrap_x_requested():
@@ -254,6 +269,75 @@ class AbstractDiffusion:
         ext = ext.contiguous()
         self._wrap_copies[slot] = (t, t._version, ext)
         return ext
+
+    # ---- --mdtile-inpaint-skip: only the tiles the job's latent mask touches ------------------------------------------------------------
+    def _skip_note(self, reason: str):
+        """One line per job and reason why every tile runs although the option is set."""
+        if reason not in self._skip_notes:
+            self._skip_notes.add(reason)
+            print(f"[Tiled Diffusion] --mdtile-inpaint-skip not applied: {reason}; every tile runs.")
+
+    def _inpaint_mask(self) -> Optional[Tensor]:
+        """p.nmask as fp32 [P, H, W] on the device, or None (with the reason noted) when the job has no mask of the latent's size."""
+        m = getattr(self.p, "nmask", None)
+        if not isinstance(m, Tensor):
+            self._skip_note("the job has no inpaint mask (p.nmask)")
+            return None
+        if m.dim() == 4 and m.shape[0] == 1:
+            m = m[0]
+        if m.dim() == 2:
+            m = m.unsqueeze(0)
+        if m.dim() != 3 or tuple(m.shape[-2:]) != (self.h, self.w):
+            self._skip_note(f"the mask has size {tuple(getattr(self.p, 'nmask').shape)}, not [{self.h}, {self.w}] / [P, {self.h}, {self.w}] / "
+                            f"[1, P, {self.h}, {self.w}]")
+            return None
+        return m.to(device=devices.device, dtype=torch.float32).contiguous()
+
+    def inpaint_skip(self, own_evaluation: Optional[str] = None) -> str:
+        """How this full-size evaluation runs: "full" (every tile), "sparse" (self.sparse_plan / self.sparse_batched_bboxes: the tiles the mask
+        touches) or "empty" (it touches none: the model is not called).  Decided once per job, on the first evaluation that asks -- the host
+        computes p.nmask after the delegate is built.  own_evaluation: an evaluation that always runs full-canvas names itself here."""
+        if not self.inpaint_skip_requested():
+            return "full"
+        if own_evaluation is not None:
+            self._skip_note(own_evaluation)
+            return "full"
+        if self.skip_mode is None:
+            self.skip_mode = self._decide_inpaint_skip()
+        return self.skip_mode
+
+    def _decide_inpaint_skip(self) -> str:
+        if self.enable_custom_bbox or not self.draw_background or not self.enable_grid_bbox or self.plan is None:
+            self._skip_note("custom regions (region prompt control) are enabled")
+            return "full"
+        if self.wrap_x or self.wrap_y:
+            self._skip_note("the canvas wraps around (--mdtile-wrap-x / --mdtile-wrap-y)")
+            return "full"
+        mask = self._inpaint_mask()
+        if mask is None:
+            return "full"
+        active = mdtile.tile_activity(self.plan, mask)
+        Ta, T = sum(1 for a in active if a), len(active)
+        print(f"[Tiled Diffusion] inpaint mask touches {Ta} of {T} tiles")
+        if Ta == T:
+            return "full"
+        if Ta == 0:
+            if self.pbar is not None:       # no model call will be made
+                self.pbar.close()
+                self.pbar = None
+            return "empty"
+        batches = -(-Ta // max(1, self.requested_tile_bs))
+        if batches > mdtile.MAX_BATCHES:      # a sparse plan has no packed form; the full path packs any number of batches into one buffer
+            self._skip_note(f"the {Ta} touched tiles make {batches} batches at tile batch size {self.requested_tile_bs}, more than the "
+                            f"{mdtile.MAX_BATCHES} a sparse plan carries (raise the tile batch size)")
+            return "full"
+        self.sparse_plan = self.plan.subset(active, self.requested_tile_bs)
+        self.sparse_batched_bboxes = [[BBox(*b) for b in batch] for batch in self.sparse_plan.batches]
+        self.total_bboxes = self.sparse_plan.num_batches      # the progress bar follows the calls actually made
+        if self.pbar is not None:
+            self.pbar.total = self.total_bboxes * state.sampling_steps
+            self.pbar.refresh()
+        return "sparse"
 
     def _refuse_wrap_x_with(self, what: str):
         if self.wrap_x or self.wrap_y:
@@ -443,10 +527,12 @@ class AbstractDiffusion:
     def _hint_on_device(self, hint: Tensor) -> Tensor:
         return hint if hint.device.type == "cuda" else hint.to(devices.device)
 
-    def switch_controlnet_tensors(self, batch_id: int, x_batch_size: int, tile_batch_size: int, is_denoise: bool = False):
+    def switch_controlnet_tensors(self, batch_id: int, x_batch_size: int, tile_batch_size: int, is_denoise: bool = False,
+                                  batched_bboxes: Optional[List[List[BBox]]] = None):
+        """batched_bboxes: the box list whose batch `batch_id` is switched in (default: the grid's; with tile skipping the active batches)."""
         if not self.enable_controlnet or not self.org_control_tensor_batch:
             return
-        bboxes = self.batched_bboxes[batch_id]
+        bboxes = (self.batched_bboxes if batched_bboxes is None else batched_bboxes)[batch_id]
         rects = [(b.x * opt_f, b.y * opt_f) for b in bboxes]
         w, h = bboxes[0].w * opt_f, bboxes[0].h * opt_f
         for k, (param, hint) in enumerate(zip(self.control_params, self.org_control_tensor_batch)):
@@ -485,10 +571,10 @@ class AbstractDiffusion:
         if self._stablesr_live():
             self.stablesr_script.stablesr_model.latent_image = self.stablesr_tensor
 
-    def switch_stablesr_tensors(self, batch_id: int):
+    def switch_stablesr_tensors(self, batch_id: int, batched_bboxes: Optional[List[List[BBox]]] = None):
         if not self._stablesr_live():
             return
-        bboxes = self.batched_bboxes[batch_id]
+        bboxes = (self.batched_bboxes if batched_bboxes is None else batched_bboxes)[batch_id]
         t = self.extended_x(self.stablesr_tensor, "stablesr").contiguous()
         self.stablesr_script.stablesr_model.latent_image = mdtile.gather_rects(t, [(b.x, b.y) for b in bboxes], bboxes[0].w, bboxes[0].h)
 

@@ -33,6 +33,8 @@ class DemoFusion(AbstractDiffusion):
     def __init__(self, p, *args, **kwargs):
         super().__init__(p, *args, **kwargs)
         assert p.sampler_name != "UniPC", "Demofusion is not compatible with UniPC!"
+        if self.inpaint_skip_requested():      # one delegate per job: said once
+            self._skip_note("DemoFusion runs its own window schedule")
         self.jitter_range = 0
         self.window_size = None
         self.sig = 0.0

@@ -80,10 +80,16 @@ class MixtureOfDiffusers(AbstractDiffusion):
             return shared.sd_model.apply_model_original_md(x_in, t_in, c_in)
         x_in = x_in.contiguous()
 
+        # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
+        skip = self.inpaint_skip(self.NOISE_INVERSION_FULL if noise_inverse_step >= 0 else None)
+        if skip == "empty":
+            return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
+        plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
+
         tile_outs: List[Tensor] = []
         if self.draw_background:
-            x_tiles = mdtile.gather_all(self.plan, x_in)                 # K2, one launch
-            for batch_id, bboxes in enumerate(self.batched_bboxes):
+            x_tiles = mdtile.gather_all(plan, x_in)                      # K2, one launch
+            for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
                 n = len(bboxes)
@@ -97,8 +103,8 @@ class MixtureOfDiffusers(AbstractDiffusion):
                 else:
                     print(">> [WARN] not supported, make an issue on github!!")
                     c_tile = c_in
-                self.switch_controlnet_tensors(batch_id, N, n, is_denoise=True)
-                self.switch_stablesr_tensors(batch_id)
+                self.switch_controlnet_tensors(batch_id, N, n, is_denoise=True, batched_bboxes=batched_bboxes)
+                self.switch_stablesr_tensors(batch_id, batched_bboxes)
                 out = shared.sd_model.apply_model_original_md(x_tiles[batch_id], t_tile, c_tile)
                 tile_outs.append(out.to(x_in.dtype).contiguous())
                 self.update_pbar()
@@ -122,6 +128,10 @@ class MixtureOfDiffusers(AbstractDiffusion):
                 with devices.autocast():
                     extra_networks.deactivate(self.p, bbox.extra_network_data)
 
+        if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
+            self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MOD, tile_outs, N, C, fill=x_in, tile_w=self.get_tile_weights(),
+                                                rescale=self.rescale_factor)
+            return self.x_buffer
         # K4 + K6 + K7 in one launch; pixels nobody paints stay 0, as upstream
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights() if tile_outs else None,
                                      rescale=self.rescale_factor, regions=self.region_specs(region_outs),

@@ -103,12 +103,14 @@ class MultiDiffusion(AbstractDiffusion):
         return self.make_cond_dict(cond_in, tcond, icond, vcond)
 
     # ---- the hot path ----------------------------------------------------------------------------------------------
-    def sample_one_step(self, x_in: Tensor, org_func: Callable, repeat_func: Callable, custom_func: Callable) -> Tensor:
+    def sample_one_step(self, x_in: Tensor, org_func: Callable, repeat_func: Callable, custom_func: Callable,
+                        own_evaluation: str = None) -> Tensor:
         """One hijacked model evaluation over the whole latent.
             x_in        [N, C, H, W] current latent (N = cond + uncond copies)
             org_func    untiled forward (used when the size does not match, e.g. the hires pass)
             repeat_func forward for one tile batch  [bs*N, C, th, tw] -> same shape
             custom_func forward for one custom region
+            own_evaluation  set by a caller whose evaluations always run every tile (--mdtile-inpaint-skip does not apply): its reason
         """
         N, C, H, W = x_in.shape
         if (H, W) != (self.h, self.w):
@@ -116,14 +118,20 @@ class MultiDiffusion(AbstractDiffusion):
             return org_func(x_in)
         x_in = x_in.contiguous()
 
+        # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
+        skip = self.inpaint_skip(own_evaluation)
+        if skip == "empty":
+            return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
+        plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
+
         tile_outs: List[Tensor] = []
         if self.draw_background:
-            x_tiles = mdtile.gather_all(self.plan, x_in)                 # K2: every tile batch, one launch
-            for batch_id, bboxes in enumerate(self.batched_bboxes):
+            x_tiles = mdtile.gather_all(plan, x_in)                      # K2: every tile batch, one launch
+            for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
-                self.switch_controlnet_tensors(batch_id, N, len(bboxes))
-                self.switch_stablesr_tensors(batch_id)
+                self.switch_controlnet_tensors(batch_id, N, len(bboxes), batched_bboxes=batched_bboxes)
+                self.switch_stablesr_tensors(batch_id, batched_bboxes)
                 out = repeat_func(x_tiles[batch_id], bboxes)
                 tile_outs.append(out.to(x_in.dtype).contiguous())
                 self.update_pbar()
@@ -142,6 +150,9 @@ class MultiDiffusion(AbstractDiffusion):
                     extra_networks.deactivate(self.p, bbox.extra_network_data)
             self.update_pbar()
 
+        if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
+            self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in, weights=self.weights)
+            return self.x_buffer
         # K3 + K5 + K6 + K7 in one launch
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MD, tile_outs, N, C, weights=self.weights,
                                      regions=self.region_specs(region_outs), dtype=x_in.dtype, device=x_in.device)
@@ -162,4 +173,4 @@ class MultiDiffusion(AbstractDiffusion):
             icond = self.slice_icond(self.get_icond(cond_org), bbox)
             return shared.sd_model.apply_model(x, sigma_in, cond=self.make_cond_dict(cond_in, tcond, icond))
 
-        return self.sample_one_step(x_in, org_func, repeat_func, custom_func)
+        return self.sample_one_step(x_in, org_func, repeat_func, custom_func, own_evaluation=self.NOISE_INVERSION_FULL)

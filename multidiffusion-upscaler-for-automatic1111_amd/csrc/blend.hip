@@ -829,22 +829,18 @@ int fill_params(BlendParams& P, const mdtile_plan* p, const mdtile_blend_args* a
 extern "C" int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                             const mdtile_region* regions, int num_regions, mdtile_stream_t stream) {
     MDT_CHECK_ARG(!(plan && plan_sparse(plan)), "mdtile_blend: refused on a sparse plan: it leaves tiles out, the blend for it is mdtile_blend_sparse");
-    if (plan && plan_wraps(plan)) return wrap_blend(plan, args, batch_out, num_batches, num_regions, as_stream(stream));   // wrap.hip
+    if (plan && plan_wraps(plan)) return walk_blend(plan, args, batch_out, num_batches, num_regions, nullptr, as_stream(stream));   // wrap.hip
     BlendParams P;
     int rc = fill_params(P, plan, args, batch_out, num_batches, regions, num_regions);
     if (rc != MDTILE_OK) return rc;
     hipStream_t s = as_stream(stream);
-    switch (args->dtype) {
-        case MDTILE_DT_F32: return launch_blend<float>(P, plan, args->method, false, s);
-        case MDTILE_DT_F16: return launch_blend<__half>(P, plan, args->method, false, s);
-        default: return launch_blend<__hip_bfloat16>(P, plan, args->method, false, s);
-    }
+    return with_dtype(args->dtype, [&](auto* tag) { return launch_blend<std::remove_pointer_t<decltype(tag)>>(P, plan, args->method, false, s); });
 }
 
 extern "C" int mdtile_blend_dispatch(const mdtile_plan* plan, int dtype, int N, int C, int flags, int num_batches, int ptrs_aligned16,
                                      int row_lo, int row_hi, int* info8) {
     MDT_CHECK_ARG(plan && info8, "mdtile_blend_dispatch: null argument");
-    MDT_CHECK_ARG(!plan_sparse(plan), "mdtile_blend_dispatch: a sparse plan has one blend kernel of its own (sparse.hip), not k_blend / k_blend_lds");
+    MDT_CHECK_ARG(!plan_sparse(plan), "mdtile_blend_dispatch: a sparse plan has one blend kernel of its own (wrap.hip), not k_blend / k_blend_lds");
     MDT_CHECK_ARG(!plan_wraps(plan), "mdtile_blend_dispatch: a %s plan has one blend kernel of its own (wrap.hip), not k_blend / k_blend_lds", wrap_kind(plan));
     MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_blend_dispatch: bad N=%d C=%d", N, C);
     MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_blend_dispatch: bad dtype %d", dtype);
@@ -880,19 +876,13 @@ extern "C" int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend
     if (rc != MDTILE_OK) return rc;
     P.partial = d_partial;
     hipStream_t s = as_stream(stream);
-    switch (args->dtype) {
-        case MDTILE_DT_F32: return launch_blend<float>(P, nullptr, args->method, true, s);
-        case MDTILE_DT_F16: return launch_blend<__half>(P, nullptr, args->method, true, s);
-        default: return launch_blend<__hip_bfloat16>(P, nullptr, args->method, true, s);
-    }
+    return with_dtype(args->dtype, [&](auto* tag) { return launch_blend<std::remove_pointer_t<decltype(tag)>>(P, nullptr, args->method, true, s); });
 }
 
 static int gather_common(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs,
                          int t_lo, int t_hi, int packed, hipStream_t s) {
-    MDT_CHECK_ARG(p && d_x_in && ptrs, "mdtile_gather: null argument");
+    if (int rc = gather_check(p, dtype, N, C, d_x_in, ptrs)) return rc;   // wrap.hip
     if (int rc = plan_upload(p)) return rc;
-    MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_gather: bad N=%d C=%d", N, C);
-    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather: bad dtype %d", dtype);
     MDT_CHECK_ARG(t_hi - t_lo <= 65535, "mdtile_gather: too many tiles in one launch");
     if (nptrs > MDTILE_MAX_BATCHES) {
         set_error("mdtile_gather: %d batches > MDTILE_MAX_BATCHES=%d", nptrs, MDTILE_MAX_BATCHES);
@@ -904,11 +894,7 @@ static int gather_common(const mdtile_plan* p, int dtype, int N, int C, const vo
     P.t_lo = t_lo; P.t_hi = t_hi; P.packed = packed; P.xs = p->d_xs; P.ys = p->d_ys; P.x_in = d_x_in;
     for (int b = 0; b < nptrs; ++b) P.batch[b] = ptrs[b];  // holes are fine: only tiles in [t_lo, t_hi) are touched
     dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, t_hi - t_lo), block(256);
-    switch (dtype) {
-        case MDTILE_DT_F32: hipLaunchKernelGGL(k_gather<float>, grid, block, 0, s, P); break;
-        case MDTILE_DT_F16: hipLaunchKernelGGL(k_gather<__half>, grid, block, 0, s, P); break;
-        default: hipLaunchKernelGGL(k_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
-    }
+    with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL(k_gather<std::remove_pointer_t<decltype(tag)>>, grid, block, 0, s, P); });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -924,23 +910,17 @@ extern "C" int mdtile_gather(const mdtile_plan* p, int dtype, int N, int C, cons
     ptrs[batch_id] = d_x_tile;
     int t_lo = batch_id * p->tile_bs;
     int t_hi = t_lo + p->tile_bs < plan_tiles(p) ? t_lo + p->tile_bs : plan_tiles(p);
-    if (plan_sparse(p)) return sparse_gather(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, as_stream(stream));   // sparse.hip: active slots
-    if (plan_wraps(p)) return wrap_gather(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, as_stream(stream));   // wrap.hip
+    if (plan_sparse(p) || plan_wraps(p)) return walk_gather(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, as_stream(stream));   // wrap.hip
     return gather_common(p, dtype, N, C, d_x_in, ptrs, p->num_batches, t_lo, t_hi, 0, as_stream(stream));
 }
 
 extern "C" int mdtile_gather_all(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs,
                                  int num_batches, mdtile_stream_t stream) {
     MDT_CHECK_ARG(p && batch_ptrs, "mdtile_gather_all: null argument");
-    if (plan_sparse(p)) {   // sparse.hip; the compact batches of the active tiles, no packed destination
-        MDT_CHECK_ARG(num_batches == p->num_batches, "mdtile_gather_all: %d batches given, the sparse plan has %d (it has no packed form)", num_batches,
-                      p->num_batches);
-        return sparse_gather(p, dtype, N, C, d_x_in, batch_ptrs, num_batches, 0, p->Ta, as_stream(stream));
-    }
-    if (plan_wraps(p)) {   // wrap.hip; no packed destination there
+    if (plan_sparse(p) || plan_wraps(p)) {   // wrap.hip; every tile, or the compact batches of the active tiles; no packed destination there
         MDT_CHECK_ARG(num_batches == p->num_batches, "mdtile_gather_all: %d batches given, the %s plan has %d (it has no packed form)", num_batches,
-                      wrap_kind(p), p->num_batches);
-        return wrap_gather(p, dtype, N, C, d_x_in, batch_ptrs, num_batches, 0, p->T, as_stream(stream));
+                      plan_sparse(p) ? "sparse" : wrap_kind(p), p->num_batches);
+        return walk_gather(p, dtype, N, C, d_x_in, batch_ptrs, num_batches, 0, plan_tiles(p), as_stream(stream));
     }
     // num_batches == 1 with a plan of more batches means ONE packed [T*N,C,th,tw] destination
     int packed = (num_batches == 1 && p->num_batches != 1) ? 1 : 0;
@@ -979,17 +959,10 @@ extern "C" int mdtile_gather_rect(int dtype, int N, int C, int W, int H, const v
     MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather_rect: bad dtype %d", dtype);
     dim3 grid(cdiv((long long)w * h, 256), N * C), block(256);
     hipStream_t s = as_stream(stream);
-    switch (dtype) {
-        case MDTILE_DT_F32:
-            hipLaunchKernelGGL(k_gather_rect<float>, grid, block, 0, s, (const float*)d_x_in, (float*)d_out, C, W, H, x, y, w, h);
-            break;
-        case MDTILE_DT_F16:
-            hipLaunchKernelGGL(k_gather_rect<__half>, grid, block, 0, s, (const __half*)d_x_in, (__half*)d_out, C, W, H, x, y, w, h);
-            break;
-        default:
-            hipLaunchKernelGGL(k_gather_rect<__hip_bfloat16>, grid, block, 0, s, (const __hip_bfloat16*)d_x_in, (__hip_bfloat16*)d_out, C, W, H, x, y, w, h);
-            break;
-    }
+    with_dtype(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(k_gather_rect<T>, grid, block, 0, s, (const T*)d_x_in, (T*)d_out, C, W, H, x, y, w, h);
+    });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

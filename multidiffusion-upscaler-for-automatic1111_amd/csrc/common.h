@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/mdtile.h"
 
@@ -61,6 +62,17 @@ int plan_upload(const struct ::mdtile_plan* plan);  // mirror the plan's lookup 
 static inline hipStream_t as_stream(mdtile_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// f(tag) with `tag` a null pointer to the storage type of an MDTILE_DT_* code that the caller has checked (0 .. 2):
+//   with_dtype(dtype, [&](auto* tag) { using T = std::remove_pointer_t<decltype(tag)>; ... });
+template <class F>
+auto with_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case MDTILE_DT_F32: return f((float*)nullptr);
+        case MDTILE_DT_F16: return f((__half*)nullptr);
+        default: return f((__hip_bfloat16*)nullptr);
+    }
+}
 
 // fp32 <-> storage type
 template <typename T> __device__ __forceinline__ float to_f32(T v);
@@ -162,7 +174,8 @@ namespace mdt {
 static inline bool plan_wraps(const ::mdtile_plan* p) { return p->wrap_x || p->wrap_y; }
 // what an error text calls such a plan
 static inline const char* wrap_kind(const ::mdtile_plan* p) { return !p->wrap_y ? "wrap-x" : p->wrap_x ? "wrap-x + wrap-y (torus)" : "wrap-y"; }
-// a plan of the active tiles only (mdtile_plan_create_subset): sparse.hip's kernels take it, and what they do not do is refused by name
+// a plan of the active tiles only (mdtile_plan_create_subset): wrap.hip's kernels take it too (a plain parent on the circle; the entry point is
+// in sparse.hip), and what they do not do is refused by name
 static inline bool plan_sparse(const ::mdtile_plan* p) { return p->Ta > 0; }
 // the tiles a plan hands to the model: the active ones of a sparse plan, else all
 static inline int plan_tiles(const ::mdtile_plan* p) { return p->Ta > 0 ? p->Ta : p->T; }

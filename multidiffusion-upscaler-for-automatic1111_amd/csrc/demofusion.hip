@@ -117,17 +117,6 @@ __global__ __launch_bounds__(256) void k_restandardize(const T* __restrict__ x, 
     out[i] = from_f32<T>((to_f32<T>(x[i]) - st[0]) / st[1] * st[3] + st[2]);
 }
 
-template <typename F>
-int by_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case MDTILE_DT_F32: f((float*)nullptr); return MDTILE_OK;
-        case MDTILE_DT_F16: f((__half*)nullptr); return MDTILE_OK;
-        case MDTILE_DT_BF16: f((__hip_bfloat16*)nullptr); return MDTILE_OK;
-    }
-    mdt::set_error("bad dtype %d", dtype);
-    return MDTILE_E_ARG;
-}
-
 }  // namespace
 
 extern "C" int mdtile_window_blend(int dtype, const void* d_tiles, void* d_out, const int* d_window_xy, const int* d_nomx, const int* d_nomy,
@@ -136,12 +125,12 @@ extern "C" int mdtile_window_blend(int dtype, const void* d_tiles, void* d_out, 
     MDT_CHECK_ARG(rows > 0 && cols > 0 && jitter >= 0 && window > 0 && N > 0 && C > 0 && N * C <= 65535 && Hp > 0 && Wp > 0,
                   "mdtile_window_blend: bad shape");
     hipStream_t s = as_stream(stream);
-    int rc = by_dtype(dtype, [&](auto* tag) {
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         hipLaunchKernelGGL(k_window_blend<T>, dim3(cdiv((long long)Hp * Wp, 256), N * C), dim3(256), 0, s, (const T*)d_tiles, (T*)d_out, d_window_xy, d_nomx,
                            d_nomy, rows, cols, jitter, window, N, C, Hp, Wp);
     });
-    if (rc != MDTILE_OK) return rc;
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -161,12 +150,12 @@ extern "C" int mdtile_dilated_gather(int dtype, const void* d_x, const void* d_x
         cl.by[i] = (unsigned char)by;
     }
     hipStream_t s = as_stream(stream);
-    int rc = by_dtype(dtype, [&](auto* tag) {
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         hipLaunchKernelGGL(k_dilated_gather<T>, dim3(cdiv((long long)h0 * w0, 256), C, num_cells * N), dim3(256), 0, s, (const T*)d_x,
                            (const T*)(d_x_filtered ? d_x_filtered : d_x), num_from_x, (T*)d_out, N, C, Hp, Wp, S, jitter, h0, w0, cl);
     });
-    if (rc != MDTILE_OK) return rc;
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -177,12 +166,12 @@ extern "C" int mdtile_demofusion_combine(int dtype, const void* d_x_local, const
     MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535 && Hp > 0 && Wp > 0 && S > 0 && jitter >= 0 && h0 > 0 && w0 > 0, "mdtile_demofusion_combine: bad shape");
     hipStream_t s = as_stream(stream);
     const int end = Wp - jitter;      // upstream takes the end of BOTH axes from the width (:262)
-    int rc = by_dtype(dtype, [&](auto* tag) {
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         hipLaunchKernelGGL(k_demofusion_combine<T>, dim3(cdiv((long long)Hp * Wp, 256), N * C), dim3(256), 0, s, (const T*)d_x_local, (const T*)d_global_out,
                            (T*)d_out, N, C, Hp, Wp, S, jitter, end, h0, w0, mixture, c2);
     });
-    if (rc != MDTILE_OK) return rc;
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -191,11 +180,11 @@ extern "C" int mdtile_depthwise_blur(int dtype, const void* d_x, const float* d_
                                      mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x && d_kernel && d_out && planes > 0 && planes <= 65535 && H > 0 && W > 0 && K > 0 && (K & 1), "mdtile_depthwise_blur: bad arguments");
     hipStream_t s = as_stream(stream);
-    int rc = by_dtype(dtype, [&](auto* tag) {
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         hipLaunchKernelGGL(k_depthwise_blur<T>, dim3(cdiv((long long)H * W, 256), planes), dim3(256), 0, s, (const T*)d_x, d_kernel, (T*)d_out, H, W, K);
     });
-    if (rc != MDTILE_OK) return rc;
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
@@ -203,11 +192,11 @@ extern "C" int mdtile_depthwise_blur(int dtype, const void* d_x, const float* d_
 extern "C" int mdtile_restandardize(int dtype, const void* d_x, const float* d_stats4, void* d_out, size_t n, mdtile_stream_t stream) {
     MDT_CHECK_ARG(d_x && d_stats4 && d_out && n > 0, "mdtile_restandardize: bad arguments");
     hipStream_t s = as_stream(stream);
-    int rc = by_dtype(dtype, [&](auto* tag) {
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         hipLaunchKernelGGL(k_restandardize<T>, dim3(cdiv((long long)n, 256)), dim3(256), 0, s, (const T*)d_x, d_stats4, (T*)d_out, n);
     });
-    if (rc != MDTILE_OK) return rc;
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

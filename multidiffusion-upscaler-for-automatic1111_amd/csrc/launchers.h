@@ -9,18 +9,16 @@
 
 namespace mdt {
 
-// ---- wrap.hip: wrap-x, wrap-y and torus plans (mdtile_plan_create_wrap), one kernel set for all three; the public entry points hand such a
-// plan (mdt::plan_wraps) to these launchers
+// ---- wrap.hip: wrap-x, wrap-y and torus plans (mdtile_plan_create_wrap) and sparse plans (mdtile_plan_create_subset, the tiles an inpaint
+// mask touches), one kernel set for all of them; the public entry points hand such a plan (mdt::plan_wraps, mdt::plan_sparse) to these
+// launchers.  walk_gather fills the batches of the positions [s_lo, s_hi): tiles, or the active slots of a sparse plan.  walk_blend takes
+// d_fill for a sparse plan only.  gather_check: what every mdtile_gather* asks of its arguments.
 int wrap_weight_map(const struct ::mdtile_plan* plan, const float* d_tile_w, float* d_weights, hipStream_t s);
-int wrap_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi,
+int gather_check(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs);
+int walk_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi,
                 hipStream_t s);
-int wrap_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
-               int num_regions, hipStream_t s);
-
-// ---- sparse.hip: sparse plans (mdtile_plan_create_subset), the tiles an inpaint mask touches; the public gather entry points hand such a plan
-// (mdt::plan_sparse) to sparse_gather, which fills the compact batches of the active slots [s_lo, s_hi)
-int sparse_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi,
-                  hipStream_t s);
+int walk_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+               int num_regions, const void* d_fill, hipStream_t s);
 
 // ---- plan.hip
 int device_cus();      // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached

@@ -306,20 +306,11 @@ extern "C" int mdtile_gather_rects(int dtype, int N, int C, int W, int H, const 
     }
     dim3 grid(cdiv((long long)w * h, 256), C, num_rects * N * repeat), block(256);
     hipStream_t s = as_stream(stream);
-    switch (dtype) {
-        case MDTILE_DT_F32:
-            hipLaunchKernelGGL(k_gather_rects<float>, grid, block, 0, s, (const float*)d_x_in, (float*)d_out, N, C, H, W, w, h, repeat, tile_major, R);
-            break;
-        case MDTILE_DT_F16:
-            hipLaunchKernelGGL(k_gather_rects<__half>, grid, block, 0, s, (const __half*)d_x_in, (__half*)d_out, N, C, H, W, w, h, repeat, tile_major, R);
-            break;
-        case MDTILE_DT_BF16:
-            hipLaunchKernelGGL(k_gather_rects<__hip_bfloat16>, grid, block, 0, s, (const __hip_bfloat16*)d_x_in, (__hip_bfloat16*)d_out, N, C, H, W, w, h,
-                               repeat, tile_major, R);
-            break;
-        default:
-            MDT_CHECK_ARG(false, "mdtile_gather_rects: bad dtype %d", dtype);
-    }
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather_rects: bad dtype %d", dtype);
+    with_dtype(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        hipLaunchKernelGGL(k_gather_rects<T>, grid, block, 0, s, (const T*)d_x_in, (T*)d_out, N, C, H, W, w, h, repeat, tile_major, R);
+    });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

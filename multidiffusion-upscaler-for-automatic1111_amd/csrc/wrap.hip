@@ -13,8 +13,13 @@
 // Diffusers w = tile_w * rescale[y, x], term out * w; MultiDiffusion weights > 1 ? buf / weights : buf.  fp32 accumulation from +0.0,
 // -ffp-contract=off: results equal the sequential loop bit for bit.
 //
+// SPARSE plans (mdtile_plan_create_subset; sparse.hip has the entry point and the activity kernel) are gathered and blended by
+// the same two kernels: their parent is always a plain plan, so the arithmetic on the circle serves it as it serves an axis that does not
+// wrap.  What they add -- the gather's `active` table, the blend's liveness pass over `slot`, the skip of tiles that are not active and the
+// `fill` pass-through -- is compiled into k_walk_blend<..., SPARSE = true> only; the wrap-around instantiations hold none of it.
+//
 // Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
-// mdtile_blend_finalize -- wrap-around is not combined with regions or with the multi-GPU partial path.
+// mdtile_blend_finalize -- neither wrap-around nor tile skipping is combined with regions or with the multi-GPU partial path.
 #include "launchers.h"
 
 using namespace mdt;
@@ -60,14 +65,16 @@ __global__ __launch_bounds__(256) void k_wrap_weight_grid(int W, int H, int tw, 
 
 struct WrapGatherParams {
     int W, H, tw, th, cols, tile_bs, N, C;
-    int t_lo, _pad;
+    int s_lo, _pad;
     const int *xs, *ys;
+    const int* active;        // a sparse plan's active tile indices (position s holds tile active[s]); null: position s is tile s
     const void* x_in;
     void* batch[MDTILE_MAX_BATCHES];
 };
 static_assert(sizeof(WrapGatherParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
-// x_tile[i*N + n, c, ty, tx] = x_in[n, c, (y_i + ty) mod H, (x_i + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = tile
+// position s (a tile of the list, or a slot of a sparse plan) holds tile t: x_tile[(s mod tile_bs) * N + n, c, ty, tx] of batch s / tile_bs =
+// x_in[n, c, (y_t + ty) mod H, (x_t + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = position
 template <typename T>
 __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     const int tw4 = (P.tw + 3) >> 2;
@@ -75,12 +82,13 @@ __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     if (idx >= tw4 * P.th) return;
     const int ty = idx / tw4, tx0 = (idx - ty * tw4) << 2;
     const int plane = blockIdx.y, n = plane / P.C, c = plane - n * P.C;
-    const int t = P.t_lo + blockIdx.z;
+    const int s = P.s_lo + blockIdx.z;
+    const int t = P.active ? P.active[s] : s;
     const int r = t / P.cols, cc = t - r * P.cols;
     int sy = P.ys[r] + ty;                // ys < H and ty < th <= H (th == H only on plain rows, ys = 0): one subtraction brings it back onto the canvas
     if (sy >= P.H) sy -= P.H;
     const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + sy) * P.W;
-    const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+    const int b = s / P.tile_bs, i = s - b * P.tile_bs;
     T* dst = reinterpret_cast<T*>(P.batch[b]) + (((size_t)i * P.N + n) * P.C + c) * ((size_t)P.th * P.tw) + (size_t)ty * P.tw + tx0;
     int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw <= W (tw == W only on plain columns, xs = 0): likewise
     if (sx >= P.W) sx -= P.W;
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     }
 }
 
-struct WrapBlendParams {
+struct WalkBlendParams {
     int W, H, tw, th, cols, tile_bs, N, C;
     const int *xs, *ys;
     const int4 *colquad, *rowinfo;
@@ -105,8 +113,26 @@ struct WrapBlendParams {
     void* out;
     const void* batch[MDTILE_MAX_BATCHES];
     int rows;                 // behind the pointers: the argument layout the per-axis kernel was measured with (docs/history/results_log.md)
+    // a sparse plan only (SPARSE kernels; null otherwise)
+    const int* slot;          // slot[t] = rank of tile t among the active ones = its place in the compact batches, or -1
+    const void* fill;         // [N, C, H, W] in the storage type: the value of every pixel that is not live
 };
-static_assert(sizeof(WrapBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+static_assert(sizeof(WalkBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+
+// the storage type as an integer of its size: what passes `fill` through without a float conversion
+template <typename T> struct RawOf { using type = unsigned short; };
+template <> struct RawOf<float> { using type = unsigned int; };
+template <typename R> struct __attribute__((packed, aligned(sizeof(R)))) raw4_u { R v[4]; };   // 4 elements at an element-aligned address
+
+template <typename T> __device__ __forceinline__ typename RawOf<T>::type raw_bits(float v);
+template <> __device__ __forceinline__ unsigned int raw_bits<float>(float v) { return __float_as_uint(v); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__half>(float v) { return __half_as_ushort(__float2half_rn(v)); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__hip_bfloat16>(float v) {
+    const __hip_bfloat16 h = __float2bfloat16(v);
+    unsigned short u;
+    __builtin_memcpy(&u, &h, sizeof(u));
+    return u;
+}
 
 // 4 consecutive elements at an address aligned to their total size (16 bytes of fp32, 8 bytes of a 16-bit type): one load instruction
 template <typename T> __device__ __forceinline__ void load4_aligned(const T* p, float (&o)[4]);
@@ -126,12 +152,20 @@ template <> __device__ __forceinline__ void load4_aligned<__hip_bfloat16>(const 
 }
 
 // One thread owns one quad (4 consecutive canvas columns of one row; rows start at x = 0, so a quad never straddles the seam) for PP planes.
-// The tile rows that cover the canvas row come from rowinfo[y].x and the tile columns that cover the quad from colquad[xq].x, both as cyclic
-// runs; a canvas row is one row of every tile that covers it (tile-relative row rel(y, ys[r], H)).  A TILE's row segment may straddle the seam:
-// per candidate tile the quad is either one contiguous piece of the tile row (tile-relative x0 .. x0 + 3 all below tw) -- vector loads when
-// that piece is also aligned in memory -- or it is cut by a tile edge / the seam: per-element loads of the covered pixels only.
-template <typename T, int METHOD, int PP>
-__global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
+// The tile rows that cover the canvas row come from rowinfo[y].x and the tile columns that cover ANY pixel of the quad from colquad[xq].x, both
+// as cyclic runs; a canvas row is one row of every tile that covers it (tile-relative row rel(y, ys[r], H)).  A TILE's row segment may straddle
+// the seam: per candidate tile the quad is either one contiguous piece of the tile row (tile-relative x0 .. x0 + 3 all below tw) -- vector
+// loads when that piece is also aligned in memory -- or it is cut by a tile edge / the seam: per-element loads of the covered pixels only.
+//
+// SPARSE (the plan of the active tiles of a plain parent): a tile that is not active has no output, and a pixel is LIVE iff every tile that
+// covers it is active.  A pass over the slot table in front of the walk decides that, before the first tile value is loaded; the walk then
+// skips the tiles that are not active, finds an active tile's rows in the compact batches by its slot and adds the pixels that are covered
+// AND live; a pixel that is not live gets the bit pattern of `fill` (copied as integers: NaN payloads and -0.0 survive in every dtype).
+// A plain tile column that starts 1 - 3 px to the right of x0 has no test of its own: xs[c] + tw <= W there, so rel() gives
+// tx = W + (x0 - xs[c]) >= W - 3, hence tx + 3 >= W >= tw (never `whole`), and each tx + j either passes W and comes back as the true offset
+// x0 + j - xs[c] >= 0 or stays >= x0 + tw + j >= tw, which is not covered.
+template <typename T, int METHOD, int PP, bool SPARSE>
+__global__ __launch_bounds__(256) void k_walk_blend(const WalkBlendParams P) {
     const int W4 = (P.W + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= W4 * P.H) return;
@@ -148,100 +182,161 @@ __global__ __launch_bounds__(256) void k_wrap_blend(const WrapBlendParams P) {
         for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
 
     const CyclicRun run(P.colquad[xq].x, P.cols), rrun(P.rowinfo[y].x, P.rows);
-    float resc[4] = {0.f, 0.f, 0.f, 0.f};
-    if (METHOD == MDTILE_METHOD_MOD) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
-    }
 
-    for (int kr = 0; kr < rrun.count; ++kr) {              // ascending tile index: rows outer, columns inner
-        const int r = rrun.at(kr);
-        const int ty = rel(y, P.ys[r], P.H);               // < th: rowinfo holds exactly the rows that cover y
-        const size_t roff = (size_t)ty * P.tw;             // the tile row inside a [th, tw] plane (and inside the tile-weight map)
-        for (int k = 0; k < run.count; ++k) {
-            const int c = run.at(k);
-            const int t = r * P.cols + c;
-            const int b = t / P.tile_bs, i = t - b * P.tile_bs;
-            const int tx = rel(x0, P.xs[c], P.W);
-            const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * P.N * P.C + p0) * tile_elems + roff;
-            // one contiguous piece of the tile row, at an address aligned for the vector load in this plane and (tile_elems % 4 == 0) in the others
-            const bool whole = nvalid == 4 && tx + 3 < P.tw;
-            if (whole && (reinterpret_cast<uintptr_t>(row + tx) & (4 * sizeof(T) - 1)) == 0 && (tile_elems & 3) == 0) {
-                float wg[4] = {1.f, 1.f, 1.f, 1.f};
-                if (METHOD == MDTILE_METHOD_MOD) {
+    // which pixels of the quad get a blended value (`SPARSE ? live[j] : j < nvalid` below): those on the canvas, and of them, on a sparse plan,
+    // the live ones
+    [[maybe_unused]] bool live[4];
+    bool all_live = true, any_live = true;                 // of the pixels on the canvas; not sparse: every tile has an output
+    if constexpr (SPARSE) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) wg[j] = P.tile_w[roff + tx + j] * resc[j];
-                }
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp) {
-                    float v[4];
-                    load4_aligned<T>(row + (size_t)pp * tile_elems + tx, v);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v[j] * wg[j];
-                        else acc[pp][j] += v[j];
-                    }
-                }
-            } else {
+        for (int j = 0; j < 4; ++j) live[j] = j < nvalid;
+        for (int kr = 0; kr < rrun.count; ++kr) {
+            const int r = rrun.at(kr);
+            for (int k = 0; k < run.count; ++k) {
+                const int c = run.at(k);
+                if (P.slot[r * P.cols + c] >= 0) continue;
+                const int tx = rel(x0, P.xs[c], P.W);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int txj = tx + j;                      // tx < W, j < 4: one subtraction
                     if (txj >= P.W) txj -= P.W;
-                    if (j >= nvalid || txj >= P.tw) continue;
-                    float wgt = 1.0f;
-                    if (METHOD == MDTILE_METHOD_MOD) wgt = P.tile_w[roff + txj] * resc[j];
+                    if (txj < P.tw) live[j] = false;
+                }
+            }
+        }
+        all_live = live[0] && live[1] && live[2] && live[3];   // then nvalid == 4
+        any_live = live[0] || live[1] || live[2] || live[3];
+    }
+    if (any_live) {
+        float resc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (METHOD == MDTILE_METHOD_MOD) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (SPARSE ? live[j] : j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
+        }
+
+        for (int kr = 0; kr < rrun.count; ++kr) {          // ascending tile index: rows outer, columns inner
+            const int r = rrun.at(kr);
+            const int ty = rel(y, P.ys[r], P.H);           // < th: rowinfo holds exactly the rows that cover y
+            const size_t roff = (size_t)ty * P.tw;         // the tile row inside a [th, tw] plane (and inside the tile-weight map)
+            for (int k = 0; k < run.count; ++k) {
+                const int c = run.at(k);
+                int t = r * P.cols + c;                    // the tile's place in the batches: its index, on a sparse plan its slot
+                if constexpr (SPARSE) {
+                    t = P.slot[t];
+                    if (t < 0) continue;                   // no pixel it covers is live
+                }
+                const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+                const int tx = rel(x0, P.xs[c], P.W);
+                const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * P.N * P.C + p0) * tile_elems + roff;
+                // one contiguous piece of the tile row, every pixel live, at an address aligned for the vector load in this plane and
+                // (tile_elems % 4 == 0) in the others
+                // (`nvalid == 4` is tested here, not once in front of the walk: hoisted by hand it changes hipcc's schedule of the kernels that are
+                // not sparse, docs/history/results_log.md)
+                const bool whole = nvalid == 4 && all_live && tx + 3 < P.tw;
+                if (whole && (reinterpret_cast<uintptr_t>(row + tx) & (4 * sizeof(T) - 1)) == 0 && (tile_elems & 3) == 0) {
+                    float wg[4] = {1.f, 1.f, 1.f, 1.f};
+                    if (METHOD == MDTILE_METHOD_MOD) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) wg[j] = P.tile_w[roff + tx + j] * resc[j];
+                    }
 #pragma unroll
                     for (int pp = 0; pp < PP; ++pp) {
-                        const float v = to_f32<T>(row[(size_t)pp * tile_elems + txj]);
-                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
-                        else acc[pp][j] += v;
+                        float v[4];
+                        load4_aligned<T>(row + (size_t)pp * tile_elems + tx, v);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v[j] * wg[j];
+                            else acc[pp][j] += v[j];
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        int txj = tx + j;                  // tx < W, j < 4: one subtraction
+                        if (txj >= P.W) txj -= P.W;
+                        if (!(SPARSE ? live[j] : j < nvalid) || txj >= P.tw) continue;
+                        float wgt = 1.0f;
+                        if (METHOD == MDTILE_METHOD_MOD) wgt = P.tile_w[roff + txj] * resc[j];
+#pragma unroll
+                        for (int pp = 0; pp < PP; ++pp) {
+                            const float v = to_f32<T>(row[(size_t)pp * tile_elems + txj]);
+                            if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
+                            else acc[pp][j] += v;
+                        }
                     }
                 }
             }
         }
-    }
 
-    // MD normalisation: x = where(weights > 1, buf / weights, buf)
-    if (METHOD == MDTILE_METHOD_MD) {
+        // MD normalisation: x = where(weights > 1, buf / weights, buf) (a sparse plan: the parent's full weight map)
+        if (METHOD == MDTILE_METHOD_MD) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j >= nvalid) continue;
-            const float w = P.weights[(size_t)y * P.W + x0 + j];
-            if (w > 1.0f) {
+            for (int j = 0; j < 4; ++j) {
+                if (!(SPARSE ? live[j] : j < nvalid)) continue;
+                const float w = P.weights[(size_t)y * P.W + x0 + j];
+                if (w > 1.0f) {
 #pragma unroll
-                for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
+                    for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
+                }
             }
         }
     }
 
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp) {
-        T* dst = reinterpret_cast<T*>(P.out) + ((size_t)(p0 + pp) * P.H + y) * P.W + x0;
-        if (nvalid == 4) store4<T>(dst, acc[pp]);
-        else {
-            dst[0] = from_f32<T>(acc[pp][0]);
-            if (nvalid > 1) dst[1] = from_f32<T>(acc[pp][1]);
-            if (nvalid > 2) dst[2] = from_f32<T>(acc[pp][2]);
+        const size_t off = ((size_t)(p0 + pp) * P.H + y) * P.W + x0;
+        if constexpr (SPARSE) {
+            using R = typename RawOf<T>::type;
+            R* dst = reinterpret_cast<R*>(P.out) + off;
+            const R* fill = reinterpret_cast<const R*>(P.fill) + off;
+            if (nvalid == 4 && (all_live || !any_live)) {      // four elements, one source: one load (fill only) and one store
+                raw4_u<R> o;
+                if (all_live) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o.v[j] = raw_bits<T>(acc[pp][j]);
+                } else {
+                    o = *reinterpret_cast<const raw4_u<R>*>(fill);
+                }
+                *reinterpret_cast<raw4_u<R>*>(dst) = o;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < nvalid) dst[j] = live[j] ? raw_bits<T>(acc[pp][j]) : fill[j];
+            }
+        } else {
+            T* dst = reinterpret_cast<T*>(P.out) + off;
+            if (nvalid == 4) store4<T>(dst, acc[pp]);
+            else {
+                dst[0] = from_f32<T>(acc[pp][0]);
+                if (nvalid > 1) dst[1] = from_f32<T>(acc[pp][1]);
+                if (nvalid > 2) dst[2] = from_f32<T>(acc[pp][2]);
+            }
         }
     }
 }
 
+// planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as blend.hip sizes k_blend
+int planes_per_thread(const WalkBlendParams& P) {
+    const int planes = P.N * P.C;
+    const long long work = (long long)P.H * ((P.W + 3) / 4) * planes;
+    if (planes % 4 == 0 && work / 4 >= 131072) return 4;
+    return planes % 2 == 0 && work / 2 >= 131072 ? 2 : 1;
+}
+
+using WalkBlendKernel = void (*)(const WalkBlendParams);
 template <typename T, int PP>
-void launch_wrap_blend(const WrapBlendParams& P, int method, hipStream_t s) {
-    dim3 grid(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / PP), block(256);
-    if (method == MDTILE_METHOD_MD) hipLaunchKernelGGL((k_wrap_blend<T, MDTILE_METHOD_MD, PP>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_wrap_blend<T, MDTILE_METHOD_MOD, PP>), grid, block, 0, s, P);
+WalkBlendKernel walk_blend_kernel(int method, bool sparse) {
+    if (method == MDTILE_METHOD_MD) return sparse ? k_walk_blend<T, MDTILE_METHOD_MD, PP, true> : k_walk_blend<T, MDTILE_METHOD_MD, PP, false>;
+    return sparse ? k_walk_blend<T, MDTILE_METHOD_MOD, PP, true> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false>;
 }
 
 template <typename T>
-void launch_wrap_blend_planes(const WrapBlendParams& P, int method, hipStream_t s) {
-    // planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as blend.hip sizes k_blend
-    const int planes = P.N * P.C;
-    const long long work = (long long)P.H * ((P.W + 3) / 4) * planes;
-    if (planes % 4 == 0 && work / 4 >= 131072) launch_wrap_blend<T, 4>(P, method, s);
-    else if (planes % 2 == 0 && work / 2 >= 131072) launch_wrap_blend<T, 2>(P, method, s);
-    else launch_wrap_blend<T, 1>(P, method, s);
+void launch_walk_blend(const WalkBlendParams& P, int method, hipStream_t s) {
+    const int pp = planes_per_thread(P);
+    const bool sparse = P.slot != nullptr;
+    const WalkBlendKernel k = pp == 4 ? walk_blend_kernel<T, 4>(method, sparse) : pp == 2 ? walk_blend_kernel<T, 2>(method, sparse) : walk_blend_kernel<T, 1>(method, sparse);
+    hipLaunchKernelGGL(k, dim3(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / pp), dim3(256), 0, s, P);
 }
 
 }  // namespace
@@ -255,68 +350,76 @@ int mdt::wrap_weight_map(const mdtile_plan* p, const float* d_tile_w, float* d_w
     return MDTILE_OK;
 }
 
-// tiles [t_lo, t_hi) into the plan's batch buffers ptrs[0 .. nptrs) (holes are fine: only the batches of those tiles are touched)
-int mdt::wrap_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int t_lo, int t_hi, hipStream_t s) {
+int mdt::gather_check(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs) {
     MDT_CHECK_ARG(p && d_x_in && ptrs, "mdtile_gather: null argument");
     MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "mdtile_gather: bad N=%d C=%d", N, C);
     MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "mdtile_gather: bad dtype %d", dtype);
-    MDT_CHECK_ARG(t_lo >= 0 && t_hi <= p->T && t_lo < t_hi && t_hi - t_lo <= 65535, "mdtile_gather: bad tile range [%d,%d) of %d", t_lo, t_hi, p->T);
-    MDT_CHECK_ARG(nptrs == p->num_batches, "mdtile_gather: %d batches given, the %s plan has %d", nptrs, wrap_kind(p), p->num_batches);
-    if (nptrs > MDTILE_MAX_BATCHES) {
-        set_error("mdtile_gather: %d batches > MDTILE_MAX_BATCHES=%d (a %s plan has no packed form)", nptrs, MDTILE_MAX_BATCHES, wrap_kind(p));
+    return MDTILE_OK;
+}
+
+// positions [s_lo, s_hi) -- tiles of a wrap-around plan, active slots of a sparse one -- into the plan's batch buffers ptrs[0 .. nptrs) (holes
+// are fine: only the batches of those positions are touched)
+int mdt::walk_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi, hipStream_t s) {
+    if (int rc = gather_check(p, dtype, N, C, d_x_in, ptrs)) return rc;
+    const bool sparse = plan_sparse(p);
+    const char* kind = sparse ? "sparse" : wrap_kind(p);
+    MDT_CHECK_ARG(s_lo >= 0 && s_hi <= plan_tiles(p) && s_lo < s_hi && s_hi - s_lo <= 65535,
+                  sparse ? "mdtile_gather: bad range [%d,%d) of %d active tiles" : "mdtile_gather: bad tile range [%d,%d) of %d", s_lo, s_hi, plan_tiles(p));
+    MDT_CHECK_ARG(nptrs == p->num_batches, "mdtile_gather: %d batches given, the %s plan has %d", nptrs, kind, p->num_batches);
+    if (nptrs > MDTILE_MAX_BATCHES) {      // a wrap-around plan only: mdtile_plan_create_subset makes no sparse plan of that many batches
+        set_error("mdtile_gather: %d batches > MDTILE_MAX_BATCHES=%d (a %s plan has no packed form)", nptrs, MDTILE_MAX_BATCHES, kind);
         return MDTILE_E_LIMIT;
     }
-    for (int t = t_lo; t < t_hi; ++t) MDT_CHECK_ARG(ptrs[t / p->tile_bs], "mdtile_gather: null batch pointer %d", t / p->tile_bs);
+    for (int q = s_lo; q < s_hi; ++q) MDT_CHECK_ARG(ptrs[q / p->tile_bs], "mdtile_gather: null batch pointer %d", q / p->tile_bs);
     if (int rc = plan_upload(p)) return rc;
     WrapGatherParams P;
     memset(&P, 0, sizeof(P));
     P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.tile_bs = p->tile_bs; P.N = N; P.C = C;
-    P.t_lo = t_lo; P.xs = p->d_xs; P.ys = p->d_ys; P.x_in = d_x_in;
+    P.s_lo = s_lo; P.xs = p->d_xs; P.ys = p->d_ys; P.active = sparse ? p->d_active : nullptr; P.x_in = d_x_in;
     for (int b = 0; b < nptrs; ++b) P.batch[b] = ptrs[b];
-    dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, t_hi - t_lo), block(256);
-    switch (dtype) {
-        case MDTILE_DT_F32: hipLaunchKernelGGL(k_wrap_gather<float>, grid, block, 0, s, P); break;
-        case MDTILE_DT_F16: hipLaunchKernelGGL(k_wrap_gather<__half>, grid, block, 0, s, P); break;
-        default: hipLaunchKernelGGL(k_wrap_gather<__hip_bfloat16>, grid, block, 0, s, P); break;
-    }
+    dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, s_hi - s_lo), block(256);
+    with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL(k_wrap_gather<std::remove_pointer_t<decltype(tag)>>, grid, block, 0, s, P); });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
 
-int mdt::wrap_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, hipStream_t s) {
-    MDT_CHECK_ARG(p && a, "mdtile_blend: null plan/args");
-    // what this form does not do, by name (DESIGN.md 3.12)
-    MDT_CHECK_ARG(num_regions == 0, "mdtile_blend: a %s plan takes no custom regions (%d given): wrap-around is not combined with regions", wrap_kind(p),
-                  num_regions);
-    MDT_CHECK_ARG(a->flags == 0, "mdtile_blend: a %s plan takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", wrap_kind(p),
-                  a->flags);
-    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "mdtile_blend: a %s plan takes no row band [%d,%d): wrap-around is not combined with the multi-GPU path",
-                  wrap_kind(p), a->row_lo, a->row_hi);
-    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "mdtile_blend: bad N=%d C=%d", a->N, a->C);
-    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "mdtile_blend: bad method %d", a->method);
-    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "mdtile_blend: bad dtype %d", a->dtype);
-    MDT_CHECK_ARG(a->d_x_out, "mdtile_blend: null output");
-    MDT_CHECK_ARG(batch_out && num_batches == p->num_batches, "mdtile_blend: %d batches given, the %s plan has %d", num_batches, wrap_kind(p), p->num_batches);
-    if (num_batches > MDTILE_MAX_BATCHES) {
-        set_error("mdtile_blend: %d batches > MDTILE_MAX_BATCHES=%d (a %s plan has no packed form: raise the tile batch size)", num_batches,
-                  MDTILE_MAX_BATCHES, wrap_kind(p));
+// The grid blend that takes no regions, flags or row bands: mdtile_blend on a wrap-around plan (d_fill null) and mdtile_blend_sparse (the caller
+// has checked that the plan is sparse).  The texts name the entry point and the kind of plan.
+int mdt::walk_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, const void* d_fill,
+                    hipStream_t s) {
+    const bool sparse = plan_sparse(p);
+    const char* fn = sparse ? "mdtile_blend_sparse" : "mdtile_blend";
+    const char* kind = sparse ? "sparse" : wrap_kind(p);
+    const char* what = sparse ? "tile skipping" : "wrap-around";
+    const char* whose = sparse ? " (the parent's map)" : "";
+    MDT_CHECK_ARG(a, "%s: null plan/args", fn);
+    // what this form does not do, by name (DESIGN.md 3.12, 3.15)
+    MDT_CHECK_ARG(num_regions == 0, "%s: a %s plan takes no custom regions (%d given): %s is not combined with regions", fn, kind, num_regions, what);
+    MDT_CHECK_ARG(a->flags == 0, "%s: a %s plan takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", fn, kind, a->flags);
+    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "%s: a %s plan takes no row band [%d,%d): %s is not combined with the multi-GPU path", fn, kind, a->row_lo,
+                  a->row_hi, what);
+    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "%s: bad N=%d C=%d", fn, a->N, a->C);
+    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "%s: bad method %d", fn, a->method);
+    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "%s: bad dtype %d", fn, a->dtype);
+    MDT_CHECK_ARG(a->d_x_out, "%s: null output", fn);
+    MDT_CHECK_ARG(!sparse || d_fill, "%s: null fill: the pixels no active tile decides need a value", fn);
+    MDT_CHECK_ARG(batch_out && num_batches == p->num_batches, "%s: %d batches given, the %s plan has %d", fn, num_batches, kind, p->num_batches);
+    if (num_batches > MDTILE_MAX_BATCHES) {      // a wrap-around plan only: mdtile_plan_create_subset makes no sparse plan of that many batches
+        set_error("%s: %d batches > MDTILE_MAX_BATCHES=%d (a %s plan has no packed form: raise the tile batch size)", fn, num_batches, MDTILE_MAX_BATCHES, kind);
         return MDTILE_E_LIMIT;
     }
-    if (a->method == MDTILE_METHOD_MD) MDT_CHECK_ARG(a->d_weights, "mdtile_blend: MultiDiffusion needs d_weights");
-    else MDT_CHECK_ARG(a->d_tile_w && a->d_rescale, "mdtile_blend: Mixture of Diffusers needs d_tile_w and d_rescale");
-    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "mdtile_blend: null batch pointer %d", b);
+    if (a->method == MDTILE_METHOD_MD) MDT_CHECK_ARG(a->d_weights, "%s: MultiDiffusion needs d_weights%s", fn, whose);
+    else MDT_CHECK_ARG(a->d_tile_w && a->d_rescale, "%s: Mixture of Diffusers needs d_tile_w and d_rescale%s", fn, whose);
+    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "%s: null batch pointer %d", fn, b);
     if (int rc = plan_upload(p)) return rc;
-    WrapBlendParams P;
+    WalkBlendParams P;
     memset(&P, 0, sizeof(P));
     P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.rows = p->rows; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
     P.xs = p->d_xs; P.ys = p->d_ys; P.colquad = p->d_colquad; P.rowinfo = p->d_rowinfo;
     P.weights = a->d_weights; P.tile_w = a->d_tile_w; P.rescale = a->d_rescale; P.out = a->d_x_out;
+    if (sparse) { P.slot = p->d_slot; P.fill = d_fill; }
     for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
-    switch (a->dtype) {
-        case MDTILE_DT_F32: launch_wrap_blend_planes<float>(P, a->method, s); break;
-        case MDTILE_DT_F16: launch_wrap_blend_planes<__half>(P, a->method, s); break;
-        default: launch_wrap_blend_planes<__hip_bfloat16>(P, a->method, s); break;
-    }
+    with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

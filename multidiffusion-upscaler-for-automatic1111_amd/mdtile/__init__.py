@@ -753,6 +753,21 @@ def _as_one_buffer(parts: Sequence[torch.Tensor]) -> torch.Tensor:
     return torch.cat(list(parts), dim=0)
 
 
+def _blend_operands(plan: "Plan", method: int, batch_out, N: int, C: int, out_dtype, dtype, device, out, weights, tile_w, rescale, flags: int = 0,
+                    tile_range=None, row_range=None):
+    """What mdtile_blend and mdtile_blend_sparse share: the checked output (made here if None) and maps, the argument struct and the
+    batch-pointer array -> (out, _BlendArgs, pointers)."""
+    if out is None:
+        out = torch.empty((N, C, plan.h, plan.w), dtype=out_dtype, device=device)
+    _dev_tensor(out, "out", out_dtype)
+    for nm, t in (("weights", weights), ("tile_w", tile_w), ("rescale", rescale)):
+        if t is not None:
+            _dev_tensor(t, nm, torch.float32)
+    a = _BlendArgs(method, dtype_code(dtype), N, C, flags, *(tile_range or (0, 0)), *(row_range or (0, 0)),
+                   _p(weights).value, _p(tile_w).value, _p(rescale).value, out.data_ptr())
+    return out, a, (c_void_p * max(1, len(batch_out)))(*[t.data_ptr() for t in batch_out])
+
+
 class BlendCall:
     """A fully marshalled mdtile_blend call: the argument struct, the batch-pointer array and the region array are built ONCE; calling
     the object only does the C call (a few microseconds of host time instead of rebuilding ~10 ctypes objects per evaluation -- the
@@ -777,16 +792,9 @@ class BlendCall:
             # gather_all returns in this situation are already one buffer; anything else costs one concatenation.
             batch_out, packed = [_as_one_buffer(batch_out)], True
         flags = (BLEND_PARTIAL if partial else 0) | (BLEND_PACKED if packed else 0) | (BLEND_TILE_RANGE if tile_range is not None else 0)
-        if out is None:
-            out = torch.empty((N, C, plan.h, plan.w), dtype=torch.float32 if partial else dtype, device=device)
-        _dev_tensor(out, "out", torch.float32 if partial else dtype)
-        for nm, t in (("weights", weights), ("tile_w", tile_w), ("rescale", rescale)):
-            if t is not None:
-                _dev_tensor(t, nm, torch.float32)
-        self.plan, self.out = plan, out
-        self._a = _BlendArgs(method, dtype_code(dtype), N, C, flags, *(tile_range or (0, 0)), *(row_range or (0, 0)),
-                             _p(weights).value, _p(tile_w).value, _p(rescale).value, out.data_ptr())
-        self._ptrs = (c_void_p * max(1, len(batch_out)))(*[t.data_ptr() for t in batch_out])
+        self.plan = plan
+        self.out, self._a, self._ptrs = _blend_operands(plan, method, batch_out, N, C, torch.float32 if partial else dtype, dtype, device, out, weights,
+                                                        tile_w, rescale, flags, tile_range, row_range)
         self._n = len(batch_out)
         self._aligned = all(t.data_ptr() % 16 == 0 for t in batch_out)
         self._rarr, keep = _regions_array(regions, dtype)
@@ -868,14 +876,7 @@ def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: 
         assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
     _dev_tensor(fill, "fill", dtype)
     assert tuple(fill.shape) == (N, C, plan.h, plan.w), f"fill {tuple(fill.shape)}"
-    if out is None:
-        out = torch.empty((N, C, plan.h, plan.w), dtype=dtype, device=device)
-    _dev_tensor(out, "out", dtype)
-    for nm, t in (("weights", weights), ("tile_w", tile_w), ("rescale", rescale)):
-        if t is not None:
-            _dev_tensor(t, nm, torch.float32)
-    a = _BlendArgs(method, dtype_code(dtype), N, C, 0, 0, 0, 0, 0, _p(weights).value, _p(tile_w).value, _p(rescale).value, out.data_ptr())
-    ptrs = (c_void_p * max(1, len(batch_out)))(*[t.data_ptr() for t in batch_out])
+    out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
     _check(lib().mdtile_blend_sparse(plan.handle, ctypes.byref(a), ptrs, len(batch_out), _p(fill), _stream()), "mdtile_blend_sparse")
     return out
 

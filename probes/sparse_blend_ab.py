@@ -1,4 +1,4 @@
-"""A/B of tile skipping (csrc/sparse.hip: k_sparse_gather, k_sparse_blend), the protocol of probes/wrap_ab.py and
+"""A/B of tile skipping (csrc/wrap.hip: k_wrap_gather with the active table, k_walk_blend<..., SPARSE>), the protocol of probes/wrap_ab.py and
 probes/seam_blend_ab.py: one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache), 20 back-to-back calls per HIP-event
 pair, median of 7 rounds -- at latent 1024^2, tile 128 / overlap 8 (81 tiles), fp32, N = 2, C = 4, MultiDiffusion and Mixture of Diffusers:
     sparse ~1/10   gather_all on the sparse plan + mdtile_blend_sparse for a mask that touches about a tenth of the tiles

@@ -1,8 +1,8 @@
 """A/B of the wrap-x and torus blends (csrc/wrap.hip), one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache),
 20 back-to-back launches per HIP-event pair, median of 7 rounds -- the method of DESIGN.md 3.4 / probes/blend_r6_ab.py -- at latent 1024^2,
 tile 128 / overlap 8 and tile 96 / overlap 48, N = 2, C = 4, fp32, MultiDiffusion:
-    torus      mdtile_blend on the plan closed in both axes (mdtile_plan_create_wrap(1, 1): k_wrap_blend, cyclic rows and columns)
-    wrap-x     mdtile_blend on the wrap-x plan (mdtile_plan_create_wrap(1, 0): the same k_wrap_blend on plain rows)
+    torus      mdtile_blend on the plan closed in both axes (mdtile_plan_create_wrap(1, 1): k_walk_blend, cyclic rows and columns)
+    wrap-x     mdtile_blend on the wrap-x plan (mdtile_plan_create_wrap(1, 0): the same k_walk_blend on plain rows)
     plain      mdtile_blend on the plain plan of the same canvas (what it dispatches: k_blend / k_blend_lds), batches handed over the same way
     copy       mdtile_stream_copy of the wrap-x launch's bytes: the floor of one launch of that size
 The torus and wrap-x results are checked first against a torch restatement of the sequential `+=` loop on the device (bitwise).

@@ -31,6 +31,11 @@ CASES = {
     "order40sq": (40, 40, 24, 24, 16, 2, False),
     # the vector path must be skipped: every batch tensor starts one element into its storage
     "aligned64_misaligned": (64, 24, 32, 32, 16, 3, True),
+    # 2 x 3 tiles of 32 x 12 whose second tile column starts 1, 2, 3 px into the first quad (origins {0, 1}, {0, 2}, {0, 3}) and whose last quad
+    # has 1, 2, 3 valid pixels: the second column's offset from quad 0 is negative, which the blend takes on the circle of W columns
+    "shift1_33": (33, 20, 32, 12, 8, 4, False),
+    "shift2_34": (34, 20, 32, 12, 8, 4, False),
+    "shift3_35": (35, 20, 32, 12, 8, 4, False),
 }
 # the launcher's other forms.  It gives a thread 4 (2) planes while that leaves >= 131072 threads: H * ceil(W / 4) * 8 / 4 = 131072 at 1024 x 256,
 # and 65536 (so 2 planes: 131072) at 512 x 256.  Upstream's default 96 / 48 grid, odd origins; 128 / 8, origins 0, 112, 224, ...
@@ -242,7 +247,7 @@ def test_all_active_reads_no_fill(plugin, cuda, case, method, dt):
     _assert_bitwise(got, full_ref, f"{case} all active {method} {dt}")
 
 
-@pytest.mark.parametrize("case", ["odd37", "aligned64"])
+@pytest.mark.parametrize("case", ["odd37", "aligned64", "shift1_33", "shift2_34", "shift3_35"])
 @pytest.mark.parametrize("dt", list(DT))
 def test_fill_passes_through_bit_for_bit(plugin, cuda, case, dt):
     """+-0, +-inf, denormals and NaNs with payloads in `fill` come back with every bit at the pixels that are not live (integer comparison:

@@ -24,7 +24,7 @@ from wrap_common import host, wired, delegate, load_preload      # noqa: E402,F4
 
 NEW_SYMBOLS = ["mdtile_tile_activity", "mdtile_plan_create_subset", "mdtile_plan_active", "mdtile_blend_sparse"]
 # (W, H, requested tile_w, tile_h, overlap, tile_bs): the GPU cases of tests/test_gpu_sparse.py and an 8K canvas's latent at tile 128 / overlap 8
-GEOMETRIES = [(37, 20, 16, 12, 6, 4), (64, 24, 32, 32, 16, 3), (40, 24, 24, 24, 16, 2), (1024, 1024, 128, 128, 8, 8)]
+GEOMETRIES = [(37, 20, 16, 12, 6, 4), (64, 24, 32, 32, 16, 3), (40, 24, 24, 24, 16, 2), (34, 20, 32, 12, 8, 4), (1024, 1024, 128, 128, 8, 8)]
 
 
 def _flags(T, ids):
@@ -51,6 +51,8 @@ def test_the_restatement_grid_is_the_plain_plan(built_lib):
         assert not plan.sparse and plan.active_ids == () and built_lib.lib().mdtile_plan_active(plan.handle, None) == 0
     g = sr.grid(37, 20, 16, 12, 6, 4)
     assert (g.xs, g.ys) == ((0, 7, 14, 21), (0, 4, 8))      # literal numbers, so that the restatement is not pinned to itself alone
+    g = sr.grid(34, 20, 32, 12, 8, 4)                       # the second tile column starts 2 px into the first quad, the last quad has 2 px
+    assert (g.xs, g.ys, g.tw, g.th) == ((0, 2), (0, 4, 8), 32, 12)
 
 
 @pytest.mark.parametrize("geom,ids,tile_bs", [
@@ -59,6 +61,7 @@ def test_the_restatement_grid_is_the_plain_plan(built_lib):
     ((37, 20, 16, 12, 6, 4), tuple(range(12)), 5),                  # Ta == T is allowed
     ((64, 24, 32, 32, 16, 3), (0, 2), 3),
     ((40, 24, 24, 24, 16, 2), (0, 1, 2), 2),
+    ((34, 20, 32, 12, 8, 4), (1, 2, 5), 4),
     ((1024, 1024, 128, 128, 8, 8), (0, 1, 9, 10, 40, 41, 49, 50, 80), 8),
 ], ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_subset_matches_the_restatement(built_lib, geom, ids, tile_bs):

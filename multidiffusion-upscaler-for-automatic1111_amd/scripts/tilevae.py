@@ -63,9 +63,9 @@ def get_rcmd_dec_tsize() -> int:
     return 256 if torch.cuda.is_available() else 64
 
 
-# the program (task queue with the engine's fusions), live-window arithmetic, crop_valid_region, GroupNormParam, TileState
-from tile_utils.vae_program import (AttnPack, GroupNormParam, Step, TileState, _norm_params, _pack, _resblock,      # noqa: E402,F401
-                                    build_task_queue, crop_valid_region, live_windows)
+# the program (task queue with the engine's fusions), its resolved route, live-window arithmetic, crop_valid_region, GroupNormParam, TileState
+from tile_utils.vae_program import (AttnPack, GroupNormParam, Routed, Step, TileState, _norm_params, _pack, _resblock,      # noqa: E402,F401
+                                    build_task_queue, crop_valid_region, live_windows, pooled_site_takes_rec, resolve_route)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -328,88 +328,69 @@ class VAEHook:
             self._program_dev = dev
         return self._program
 
-    @staticmethod
-    def _feeds_norm(steps: List[Step], i: int) -> bool:
-        """The value steps[i] produces is the input of a GroupNorm (only residual bookkeeping in between)."""
-        j = i + 1
-        while j < len(steps) and steps[j].kind == "store_res":
-            j += 1
-        return j < len(steps) and steps[j].kind == "norm"
-
-    def _run_until_norm(self, steps: List[Step], st: TileState, want_stats: bool = False):
-        """Advance one tile to its next GroupNorm (exclusive) or to the end.
-        want_stats (slow mode, the norm ahead is pooled): the conv that produces the norm's input also leaves its (var, mean) in st.stats
-        where a kernel does that in its epilogue (PackedConv.leaves_stats) -- the pooling then needs no pass over the tile."""
-        while st.pc < len(steps):
-            s = steps[st.pc]
-            if s.kind == "norm":
-                return
-            if s.kind != "store_res":
-                st.stats = None
-            if s.kind == "store_res":
-                st.res.append(st.x if s.conv is None else s.conv(st.x))
-            elif s.kind == "conv":
-                route = self._conv_route(s, st.pre is not None, want_stats and self._feeds_norm(steps, st.pc))
-                residual = st.res.pop() if s.fuse_res and route != "down" else None
-                if route == "down":
-                    st.x = s.conv.down2(st.x)
-                elif route == "rec_stats":
-                    xrec = self.engine.rec_from_f32(st.x, st.pre)
-                    st.x, st.stats = s.conv.call_rec_stats(xrec, residual=residual, upsample2x=s.upsample, groups=32)
-                elif route == "handover_stats":
-                    st.x, st.stats = s.conv.call_stats(st.x, st.pre, residual=residual, groups=32)
-                elif route == "rec":
-                    # pooled-statistics site on the record kernels: one conversion pass (norm + SiLU fused into it) + the record conv --
-                    # the fp32 hand-over kernel's output to fp32 rounding (a fused residual enters the accumulation first here: (res + sum) + bias), cheaper where _pooled_site_takes_rec says so
-                    xrec = self.engine.rec_from_f32(st.x, st.pre)
-                    st.x, _ = s.conv.call_rec(xrec, residual=residual, upsample2x=s.upsample, want_f32=True, want_rec=False)
-                else:
-                    st.x = s.conv(st.x, residual=residual, upsample2x=s.upsample, pre_gn=st.pre)
-                st.pre = None
-            elif s.kind == "attn":
-                st.x = s.attn(st.x, st.res.pop())
-            elif s.kind == "tanh":
-                st.x = self.engine.tanh(st.x)
-            st.pc += 1
-
-    def _conv_route(self, s: Step, has_pre: bool, want_stats: bool = False) -> str:
-        """Which engine call a conv step of the norm-to-norm walk (slow mode, the estimator pass) takes -- THE one place that decides it:
-        _run_until_norm dispatches on it and _apply_norm asks it whether the norm it has just resolved may ride on the conv as pending
-        (a, s) coefficients (`has_pre`), so the two cannot disagree about who applies a norm.
-          "down"            ldm Downsample (stride 2; no norm in front of it)
-          "rec_stats"       conversion pass (takes the pending coefficients) + record conv that leaves get_var_mean of its output
-          "handover_stats"  fp32 hand-over conv applying the pending coefficients while staging + statistics from its epilogue
-          "rec"             conversion pass + record conv (_pooled_site_takes_rec: where that is the cheaper pair)
-          "plain"           the conv's own call: applies pending coefficients only where fuses_pre_gn() says it can"""
-        if s.downsample:
-            return "down"
-        takes_rec = self._pooled_site_takes_rec(s)
-        stats_fn = getattr(s.conv, "leaves_stats", None) if (want_stats and SLOW_STATS) else None
-        if stats_fn is not None and takes_rec and stats_fn(32, upsample2x=s.upsample, rec=True):
-            return "rec_stats"
-        if stats_fn is not None and has_pre and not s.upsample and not takes_rec and stats_fn(32):
-            return "handover_stats"
-        return "rec" if takes_rec else "plain"
-
-    def _norm_rides_on(self, nxt: Optional[Step]) -> bool:
-        """A resolved norm + SiLU in front of `nxt` stays pending as (a, s) coefficients exactly when the route `nxt` will take applies them."""
-        if not (FUSE_PRE_GN and nxt is not None and nxt.kind == "conv" and not nxt.downsample):
-            return False
-        route = self._conv_route(nxt, True)        # (statistics variants of a route apply the coefficients the same way)
-        return (route == "rec" and not nxt.upsample) or (route == "plain" and bool(nxt.conv.fuses_pre_gn(upsample2x=nxt.upsample)))
+    def _route(self, steps: List[Step], hand_over: bool, pooled=()) -> List[Routed]:
+        """resolve_route under the switches as they stand NOW: once per vae_tile_forward call and lane program, once more for the estimator
+        pass, never kept across calls (a switch or the engine's precision mode may change between two calls)."""
+        return resolve_route(steps, self.engine, FUSE_PRE_GN, REC_PATH, SLOW_REC, SLOW_STATS, hand_over, pooled)
 
     def _pooled_site_takes_rec(self, s: Step) -> bool:
-        """Slow mode / the estimator pass: a norm whose statistics are pooled cannot be applied by the conv that PRODUCES its input, so the
-        record kernels cost an extra conversion pass (fp32 -> activated records) there.  They still win where the conv is long against its
-        activation: the 512 -> 512 layers (-7 ... -9 % incl. the pass) and every upsample conv (the pass runs on the quarter-size input:
-        -8 ... -21 %); at 256 / 128 input channels the pass costs more than the faster conv saves (+1 ... +8 %) -- profiles/r4z/conv_probe.log.
-        conv_out (cout < 32) behind a pooled norm_out: no hand-over kernel applies a norm for so few couts, so the alternative is a norm pass
-        (1R + 1W) + the exact-fp32 conv -- 3.8 ms per 2224^2 tile against 1.9 ms for conversion pass + narrow record conv (profiles/r5q:
-        kernel_stats_slow.csv, 61 ms of a slow-mode 8K decode)."""
-        if not (SLOW_REC and self._takes_rec(s)):
-            return False
-        c = s.conv
-        return bool(s.upsample or (getattr(c, "cin", 0) >= 512 and getattr(c, "cout", 0) >= 512) or 0 < getattr(c, "cout", 0) < 32)
+        """The pooled-statistics site of conv step `s` runs on the record kernels (pooled_site_takes_rec: the rule and its measurements)."""
+        return pooled_site_takes_rec(s, self.engine, REC_PATH, SLOW_REC)
+
+    def _advance(self, route: List[Routed], st: TileState, norm=None, frozen=None, windows=None):
+        """THE executor: advance one tile (or one stack of tiles) along its resolved route --
+          neither keyword     to its next GroupNorm (exclusive), or to the end; the statistics a conv leaves of its output go to st.stats;
+          norm=(var, mean)    st stands at a norm the sweep has just resolved: through that norm alone (every tile, before any moves on);
+          frozen=(stats, coefs)  every norm resolved, (var, mean) and gn_coeffs by ordinal (upstream's single sweep, :578-642): to the end;
+                              windows (live_windows): the upsample convs listed there compute only that window of their input plane."""
+        E = self.engine
+        while st.pc < len(route):
+            r = route[st.pc]
+            s = r.step
+            if s.kind == "norm" and frozen is None and norm is None:
+                return
+            if s.kind != "store_res":
+                st.stats = None                               # (var, mean) describe the tensor that is about to be replaced
+            if s.kind == "store_res":
+                st.res.append(st.x if s.conv is None else s.conv(st.x))
+            elif s.kind == "norm":
+                var, mean = norm if frozen is None else frozen[0][r.ordinal]
+                if r.how in ("convert", "ride"):
+                    # norm + SiLU ride on the conv's input staging (or its conversion pass): only the per-channel (a, s) pair is formed here
+                    st.pre = E.gn_coeffs(mean, var, s.norm[0], s.norm[1], st.x.shape[1], 32, 1e-6) if frozen is None else frozen[1][r.ordinal]
+                elif r.how == "apply":
+                    keep = st.res and st.res[-1] is st.x          # identity shortcut: the residual aliases the pre-norm tensor
+                    st.x = E.gn_apply(st.x, mean, var, s.norm[0], s.norm[1], 32, 1e-6, s.silu, out=None if keep else st.x)
+                if frozen is None:
+                    st.pc += 1
+                    return
+            elif s.kind == "conv":
+                residual = st.res.pop() if r.pops_res else None
+                if r.how in ("rec", "rec_stats") and st.xrec is None:
+                    # fp32 in front of a record conv: one conversion pass, a pending norm + SiLU fused into it (the pair equals the fp32 hand-over
+                    # kernel to fp32 rounding: a fused residual enters the accumulation first here, (res + sum) + bias)
+                    st.xrec = E.rec_from_f32(st.x, st.pre)
+                if r.how == "down":
+                    st.x, st.xrec = s.conv.down2(st.x), None
+                elif r.how == "rec_stats":
+                    (st.x, st.stats), st.xrec = s.conv.call_rec_stats(st.xrec, residual=residual, upsample2x=s.upsample, groups=32), None
+                elif r.how == "handover_stats":
+                    st.x, st.stats = s.conv.call_stats(st.x, st.pre, residual=residual, groups=32)
+                elif r.how == "rec":
+                    win = windows.get(st.pc) if windows else None
+                    st.x, st.xrec = s.conv.call_rec(st.xrec, residual=residual, upsample2x=s.upsample, want_f32=r.f32_out, want_rec=r.rec_out is not None,
+                                                    rec_coef=None if r.rec_out in (None, "raw") else frozen[1][r.rec_out], **({"window": win} if win else {}))
+                elif r.how == "window_f32" and windows and windows.get(st.pc):
+                    assert residual is None and st.pre is None      # ldm Upsample: no norm in front, no skip connection into it
+                    st.x, st.xrec = self._upconv_window_f32(s.conv, st.x, windows[st.pc]), None
+                else:
+                    st.x, st.xrec = s.conv(st.x, residual=residual, upsample2x=s.upsample, pre_gn=st.pre), None
+                st.pre = None
+            elif s.kind == "attn":
+                st.x, st.xrec = s.attn(st.x, st.res.pop()), None
+            elif s.kind == "tanh":
+                st.x = E.tanh(st.x)
+            st.pc += 1
 
     def _tile_batch_that_fits(self, N: int, tile_hw: Tuple[int, int], dev) -> int:
         """Tiles of one shape per sweep (TILE_BATCH at most): what 60 % of the free device memory holds.  Peak of one tile: about five
@@ -429,79 +410,6 @@ class VAEHook:
             self._said_tb = True
             print(f"[Tiled VAE]: {tb} instead of {TILE_BATCH} tiles per sweep ({free / 2**30:.1f} GiB free, {per_tile / 2**30:.1f} GiB per {h}x{w} tile)")
         return tb
-
-    # ---- fast mode, every norm frozen: record-image hand-over between the 3x3 convs ----------------------------------
-    def _takes_rec(self, step: Step) -> bool:
-        """The conv of `step` runs on the record kernels: REC_PATH on, an engine with record images, a conv they take."""
-        fn = getattr(step.conv, "takes_rec", None)
-        return bool(REC_PATH and hasattr(self.engine, "rec_from_f32") and fn and not step.downsample and fn(step.upsample))
-
-    def _demand(self, steps: List[Step], i: int):
-        """Forms in which the value produced by steps[i] has to exist: (fp32 NCHW?, record image: None | "raw" | index of the
-        norm step whose (a, s) + SiLU the producer applies)."""
-        need_f32, j = False, i + 1
-        while j < len(steps) and steps[j].kind == "store_res":     # residual / nin_shortcut input: fp32
-            need_f32, j = True, j + 1
-        if j >= len(steps):
-            return True, None
-        s = steps[j]
-        if s.kind == "norm":
-            nxt = steps[j + 1] if j + 1 < len(steps) else None
-            if s.silu and nxt is not None and nxt.kind == "conv" and not nxt.upsample and self._takes_rec(nxt):
-                return need_f32, j
-            return True, None
-        if s.kind == "conv" and s.upsample and self._takes_rec(s):
-            return need_f32, "raw"
-        return True, None
-
-    def _run_tile_rec(self, steps: List[Step], x: Tensor, frozen, coefs, norm_ord, windows=None):
-        """One tile start to finish with frozen statistics (upstream's single sweep, :578-642).  A 3x3 conv that the record
-        kernels take reads its input as a record image; whoever produces that input writes it in that form -- the previous
-        record conv's epilogue (norm + SiLU + split fused), or mdtile_rec_from_f32 behind conv_in / attention.  Where they take
-        none (_takes_rec), a norm is applied by gn_apply or rides on the next conv as its (a, s) coefficients, as in _apply_norm.
-        windows (live_windows): the upsample convs listed there compute only that window of their input plane."""
-        E = self.engine
-        res: List[Tensor] = []
-        pre = xrec = None
-        for i, s in enumerate(steps):
-            if s.kind == "store_res":
-                res.append(x if s.conv is None else s.conv(x))
-            elif s.kind == "norm":
-                k = norm_ord[i]
-                nxt = steps[i + 1] if i + 1 < len(steps) else None
-                is_conv = nxt is not None and nxt.kind == "conv" and not nxt.downsample
-                if s.silu and is_conv and not nxt.upsample and self._takes_rec(nxt):
-                    if xrec is None:
-                        xrec = E.rec_from_f32(x, coefs[k])
-                elif FUSE_PRE_GN and s.silu and is_conv and nxt.conv.fuses_pre_gn(upsample2x=nxt.upsample):
-                    pre = coefs[k]
-                else:
-                    var, mean = frozen[k]
-                    keep = res and res[-1] is x
-                    x = E.gn_apply(x, mean, var, s.norm[0], s.norm[1], 32, 1e-6, s.silu, out=None if keep else x)
-            elif s.kind == "conv":
-                if s.downsample:
-                    x, xrec = s.conv.down2(x), None
-                else:
-                    residual = res.pop() if s.fuse_res else None
-                    if self._takes_rec(s) and (xrec is not None or s.upsample):
-                        if xrec is None:
-                            xrec = E.rec_from_f32(x, None)
-                        need_f32, rk = self._demand(steps, i)
-                        win = windows.get(i) if windows else None
-                        x, xrec = s.conv.call_rec(xrec, residual=residual, upsample2x=s.upsample, want_f32=need_f32, want_rec=rk is not None,
-                                                  rec_coef=None if rk in (None, "raw") else coefs[norm_ord[rk]], **({"window": win} if win else {}))
-                    elif s.upsample and windows and windows.get(i):
-                        assert residual is None and pre is None      # ldm Upsample: no norm in front, no skip connection into it
-                        x, xrec = self._upconv_window_f32(s.conv, x, windows[i]), None
-                    else:
-                        x, xrec = s.conv(x, residual=residual, upsample2x=s.upsample, pre_gn=pre), None
-                pre = None
-            elif s.kind == "attn":
-                x, xrec = s.attn(x, res.pop()), None
-            elif s.kind == "tanh":
-                x = E.tanh(x)
-        return x
 
     @staticmethod
     def _upconv_window_f32(conv, x: Tensor, window) -> Tensor:
@@ -528,7 +436,7 @@ class VAEHook:
         return out
 
     def _live_plan(self, steps: List[Step], in_bbox, out_bbox, grow=(0, 0, 0, 0)):
-        """(windows, narrowed input bbox) of one decoder tile for _run_tile_rec / crop_store -- ({}, in_bbox) when live-window narrowing does
+        """(windows, narrowed input bbox) of one decoder tile for _advance / crop_store -- ({}, in_bbox) when live-window narrowing does
         not apply (switched off, encoder).  grow (left, right, top, bottom; latent px): the valid rectangle grown by what the cross-faded
         assembly reads beyond the out box (seam_blend), clamped to the tile -- narrowing is exact for the rectangle it is given."""
         if not (LIVE_WINDOW and self.is_decoder):
@@ -541,20 +449,6 @@ class VAEHook:
         windows, (ry0, rx0, ry1, rx1) = live_windows(steps, (y2 - y1, x2 - x1), valid)
         return windows, (x1 + rx0, x1 + rx1, y1 + ry0, y1 + ry1)
 
-    def _apply_norm(self, steps: List[Step], st: TileState, var: Tensor, mean: Tensor):
-        E = self.engine
-        s = steps[st.pc]
-        gamma, beta = s.norm
-        nxt = steps[st.pc + 1] if st.pc + 1 < len(steps) else None
-        if s.silu and self._norm_rides_on(nxt):
-            # norm + SiLU ride on the conv's input staging: only the per-channel (a, s) pair is formed here
-            st.pre = E.gn_coeffs(mean, var, gamma, beta, st.x.shape[1], 32, 1e-6)
-        else:
-            keep = st.res and st.res[-1] is st.x          # identity shortcut: the residual aliases the pre-norm tensor
-            st.x = E.gn_apply(st.x, mean, var, gamma, beta, 32, 1e-6, s.silu, out=None if keep else st.x)
-            st.stats = None                               # (var, mean) described the tensor that was just replaced
-        st.pc += 1
-
     @torch.no_grad()
     def estimate_group_norm(self, z: Tensor, steps: List[Step]) -> Optional[List[Tuple[Tensor, Tensor]]]:
         """Fast mode: run the program on the down-sampled latent and freeze (var, mean) at every norm (:464-505).
@@ -562,13 +456,14 @@ class VAEHook:
         st = TileState(z)
         frozen = []
         n_norm = sum(1 for s in steps if s.kind == "norm")
+        route = self._route(steps, hand_over=False, pooled=range(n_norm))      # every norm's statistics come from this pass itself
         if self.color_fix:
             # semi-fast encoder mode (upstream :492-496): the estimate stops at the first downsample; only the norms before
             # it are frozen, the others are pooled across the tiles as in slow mode
             first_down = next((i for i, s in enumerate(steps) if s.kind == "conv" and s.downsample), len(steps))
             n_norm = sum(1 for s in steps[:first_down] if s.kind == "norm")
         while True:
-            self._run_until_norm(steps, st, want_stats=True)
+            self._advance(route, st)
             if st.pc >= len(steps):
                 break
             # (the conv that produced st.x has left its statistics where a kernel does that in its epilogue: TileState.stats)
@@ -576,7 +471,7 @@ class VAEHook:
             frozen.append((var, mean))
             if len(frozen) == n_norm:
                 break
-            self._apply_norm(steps, st, var, mean)
+            self._advance(route, st, norm=(var, mean))
         # upstream tests the activation for NaN after every norm (:487-490) and falls back to slow mode; a NaN anywhere upstream of a
         # norm poisons that norm's statistics, so ONE test of the frozen (var, mean) rows at the end sees the same events without a
         # host sync per norm
@@ -655,6 +550,7 @@ class VAEHook:
         def __init__(self, hook, z, in_bboxes, out_bboxes, mine: List[int], steps: List[Step], frozen, keep_tiles: bool):
             self.hook, self.z, self.in_bboxes, self.out_bboxes, self.mine = hook, z, in_bboxes, out_bboxes, mine
             self.steps, self.frozen, self.device = steps, frozen, z.device
+            self.route = None       # steps resolved for the sweep this call runs (VAEHook._route)
             self.tiles = {i: TileState(self.gather(i)) for i in mine}
             self.result = None
             self.kept = [] if keep_tiles else None      # (tile, its input bbox, output bbox) of every finished tile
@@ -697,9 +593,8 @@ class VAEHook:
         E, z, tiles, steps, frozen = self.engine, lane.z, lane.tiles, lane.steps, lane.frozen
         N, dev = z.shape[0], z.device
         use_rec = REC_PATH and hasattr(E, "rec_from_f32")
-        norm_ord = {i: k for k, i in enumerate(i for i, s in enumerate(steps) if s.kind == "norm")}
-        coefs = [E.gn_coeffs(mean, var, steps[i].norm[0], steps[i].norm[1], steps[i].channels, 32, 1e-6)
-                 for i, (var, mean) in zip(norm_ord, frozen)]
+        coefs = [E.gn_coeffs(mean, var, s.norm[0], s.norm[1], s.channels, 32, 1e-6)
+                 for s, (var, mean) in zip((s for s in steps if s.kind == "norm"), frozen)]
         if use_rec:
             for i in lane.mine:
                 lane.live[i] = self._live_plan(steps, lane.in_bboxes[i], lane.out_bboxes[i], lane.seam_grow(i))
@@ -727,16 +622,16 @@ class VAEHook:
             def run_stack(chunk):
                 T = len(chunk)
                 xb = tiles[chunk[0]].x if T == 1 else torch.cat([tiles[i].x for i in chunk], dim=0)     # (4-channel latent tiles: KBs)
-                fz, cf = rep(T)
                 if T > 1:
                     for i in chunk:
                         tiles[i].x = None          # the stacked copy is the live one
                 w0 = lane.live[chunk[0]][0]
                 wins = {k: ([lane.live[i][0][k][0] for i in chunk for _ in range(N)], [lane.live[i][0][k][1] for i in chunk for _ in range(N)], w[2], w[3])
                         for k, w in w0.items()} if w0 else None
-                yb = self._run_tile_rec(steps, xb, fz, cf, norm_ord, wins)
+                stack = TileState(xb)
+                self._advance(lane.route, stack, frozen=rep(T), windows=wins)
                 for t, i in enumerate(chunk):
-                    tiles[i].x = yb[t * N:(t + 1) * N]
+                    tiles[i].x = stack.x[t * N:(t + 1) * N]
                     lane.finish(i)
 
             groups: Dict[tuple, List[int]] = {}
@@ -773,7 +668,7 @@ class VAEHook:
             if state.interrupted:
                 lane.interrupted = True
                 return
-            tiles[i].x = self._run_tile_rec(steps, tiles[i].x, frozen, coefs, norm_ord, lane.live[i][0] if use_rec else None)
+            self._advance(lane.route, tiles[i], frozen=(frozen, coefs), windows=lane.live[i][0] if use_rec else None)
             lane.finish(i)
             yield [i]
 
@@ -807,7 +702,7 @@ class VAEHook:
                     break
                 st = lane.tiles[i]
                 with _on_device(lane.device):
-                    self._run_until_norm(lane.steps, st, want_stats=not use_frozen)
+                    self._advance(lane.route, st)
                     if st.pc < len(lane.steps) and not use_frozen:
                         rows[i] = (*(st.stats if st.stats is not None else E.gn_stats(st.x, 32)), st.x.shape[2] * st.x.shape[3])
             if lane0.interrupted and world == 1:
@@ -820,7 +715,7 @@ class VAEHook:
                 for lane in lanes:
                     with _on_device(lane.device):
                         for i in (() if lane.interrupted else lane.mine):
-                            self._apply_norm(lane.steps, lane.tiles[i], *lane.frozen[k_norm])
+                            self._advance(lane.route, lane.tiles[i], norm=lane.frozen[k_norm])
                 k_norm += 1
                 continue
             # (copied only now: a copy between two devices makes each one's stream wait for the other's, which inside the loop above would
@@ -846,7 +741,7 @@ class VAEHook:
                         continue
                     var, mean = pooled[0].to(lane.device), pooled[1].to(lane.device)
                     for i in lane.mine:
-                        self._apply_norm(lane.steps, lane.tiles[i], var, mean)
+                        self._advance(lane.route, lane.tiles[i], norm=(var, mean))
             if pooled is None:
                 return
             forward = not forward
@@ -890,7 +785,8 @@ class VAEHook:
                 frozen = seqpar.estimate_group_norm_sp(steps, zs, seqpar.BandComm(rank, world), self._sp_ops or seqpar.EngineOps(), FUSE_PRE_GN)
             else:
                 frozen = self.estimate_group_norm(zs, steps)
-        all_frozen = frozen is not None and len(frozen) == sum(1 for s in steps if s.kind == "norm")
+        n_norm = sum(1 for s in steps if s.kind == "norm")
+        all_frozen = frozen is not None and len(frozen) == n_norm
 
         # one lane for one device or this rank, one per device slot (the slots after the first with their own program and copies of z and
         # of the frozen statistics); the tiles dealt by area (mdtile/sharding.py: deal_tiles), the same list on every rank
@@ -907,6 +803,8 @@ class VAEHook:
                 lanes.append(VAEHook._Lane(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, mine, lane_steps, lane_frozen,
                                            keep_tiles=bool(slots) or seam is not None))
                 lanes[-1].seam = seam
+                # every norm frozen: the hand-over sweep; else the lockstep sweep, the statistics of the norms behind the frozen ones pooled
+                lanes[-1].route = self._route(lane_steps, all_frozen, () if all_frozen else range(len(frozen or ()), n_norm))
         if all_frozen:
             sweeps = [(lane, self._sweep_frozen(lane)) for lane in lanes]
             while sweeps:                                # one chunk of every lane per round: no device waits while another's list is issued

@@ -1,8 +1,9 @@
 """
 The Tiled-VAE PROGRAM and its geometry helpers: upstream's task queue (scripts/tilevae.py:107-204) with the fusions the engine offers
 already applied, the live-window arithmetic of the fast-mode decoder, crop_valid_region (:248-259), the slow-mode statistics collector
-(GroupNormParam, :289-335) and the per-tile executor state.  Pure host code: no switches, no device work besides what the packed
-convs / the engine do when called.  scripts/tilevae.py (the plugin surface: Script, VAEHook) re-exports every name defined here.
+(GroupNormParam, :289-335), the resolved route (resolve_route: which engine call every step takes in a given mode, who applies every
+norm, which forms a conv writes; VAEHook._advance executes it) and the per-tile executor state.  Pure host code: switches arrive as
+arguments, no device work besides what the packed convs / the engine do when called.  scripts/tilevae.py re-exports every name here.
 """
 from __future__ import annotations
 
@@ -198,11 +199,110 @@ class GroupNormParam:
         return self.engine.gn_pool(torch.vstack(self.mean_list), torch.vstack(self.var_list), self.pixel_list)
 
 
-# ---------------------------------------------------------------------------------------------------------------------
+# ---- the resolved route: what runs at step i in a given mode, decided ONCE per sweep (VAEHook._advance executes it) ----------------
+class Routed:
+    """One step of a resolved route.  conv steps -- how:
+      "down"            ldm Downsample (stride 2; no norm in front of it)
+      "rec"             record conv; a conversion pass (taking the pending coefficients) comes first when its input is fp32
+      "rec_stats"       the same, and the conv leaves get_var_mean of its output (the input of a pooled norm)
+      "handover_stats"  fp32 hand-over conv applying the pending coefficients while staging + statistics from its epilogue
+      "plain"           the conv's own call: applies pending coefficients only where fuses_pre_gn() says it can
+      "window_f32"      "plain" for an upsample conv of the hand-over sweep: over the tile's live window where it has one
+    pops_res: the conv adds the residual on top of the stack; f32_out / rec_out: the forms a "rec" conv writes -- fp32 NCHW, and a record
+    image (None, "raw", or k: already activated with norm k's coefficients + SiLU).
+    norm steps -- ordinal k and how:
+      "epilogue"        the producing record conv has already applied it (rec_out == k there)
+      "convert"         pending (a, s): the conversion pass in front of the record conv behind it applies them
+      "ride"            pending (a, s): the conv behind it applies them while staging its input
+      "apply"           gn_apply"""
+    __slots__ = ("step", "how", "pops_res", "f32_out", "rec_out", "ordinal")
+
+    def __init__(self, step):
+        self.step, self.how, self.ordinal, self.f32_out, self.rec_out = step, None, None, True, None
+        self.pops_res = step.kind == "conv" and step.fuse_res and not step.downsample
+
+
+def takes_rec(step: Step, engine, rec_path: bool) -> bool:
+    """The conv of `step` runs on the record kernels: the record path on, an engine with record images, a conv they take."""
+    fn = getattr(step.conv, "takes_rec", None)
+    return bool(rec_path and hasattr(engine, "rec_from_f32") and fn and not step.downsample and fn(step.upsample))
+
+
+def pooled_site_takes_rec(step: Step, engine, rec_path: bool, slow_rec: bool) -> bool:
+    """Slow mode / the estimator pass: a norm whose statistics are pooled cannot be applied by the conv that PRODUCES its input, so the
+    record kernels cost an extra conversion pass (fp32 -> activated records) there.  They still win where the conv is long against its
+    activation: the 512 -> 512 layers (-7 ... -9 % incl. the pass) and every upsample conv (the pass runs on the quarter-size input:
+    -8 ... -21 %); at 256 / 128 input channels the pass costs more than the faster conv saves (+1 ... +8 %) -- profiles/r4z/conv_probe.log.
+    conv_out (cout < 32) behind a pooled norm_out: no hand-over kernel applies a norm for so few couts, so the alternative is a norm pass
+    (1R + 1W) + the exact-fp32 conv -- 3.8 ms per 2224^2 tile against 1.9 ms for conversion pass + narrow record conv (profiles/r5q:
+    kernel_stats_slow.csv, 61 ms of a slow-mode 8K decode)."""
+    if not (slow_rec and takes_rec(step, engine, rec_path)):
+        return False
+    c = step.conv
+    return bool(step.upsample or (getattr(c, "cin", 0) >= 512 and getattr(c, "cout", 0) >= 512) or 0 < getattr(c, "cout", 0) < 32)
+
+
+def resolve_route(steps: List[Step], engine, fuse_pre_gn: bool, rec_path: bool, slow_rec: bool, slow_stats: bool, hand_over: bool,
+                  pooled=()) -> List[Routed]:
+    """THE one place that decides what every step does: one Routed per step, from the program, the switches and what the engine and the
+    packed convs report -- nothing of it depends on the tile.
+    hand_over: the whole-tile sweep with every norm frozen.  Producers know the next norm's coefficients, so activations travel between
+      the 3x3 convs as record images that the PRODUCING conv writes already normalised + SiLU'd (mdtile_rec_from_f32 behind conv_in /
+      attention); a conv writes the forms its consumers read.
+    else (slow mode, the estimator pass, semi-fast mode's lockstep sweep -- its frozen norms included): no producer applies a norm; the
+      record kernels run behind a conversion pass where pooled_site_takes_rec says they pay, and the producer of the input of a norm
+      whose ordinal is in `pooled` leaves that input's statistics where a kernel does (leaves_stats)."""
+    n = len(steps)
+    ordinal = {i: k for k, i in enumerate(i for i, s in enumerate(steps) if s.kind == "norm")}
+    rec = [s.kind == "conv" and (takes_rec(s, engine, rec_path) if hand_over else pooled_site_takes_rec(s, engine, rec_path, slow_rec)) for s in steps]
+
+    def rec_fed(i):          # norm i + SiLU reach the plain record conv behind them as its activated input image
+        return steps[i].silu and i + 1 < n and rec[i + 1] and not steps[i + 1].upsample
+
+    route, has_rec = [], False      # has_rec (hand-over sweep): a record image of the current value exists
+    for i, s in enumerate(steps):
+        r = Routed(s)
+        route.append(r)
+        j = i + 1            # the consumer of what steps[i] produces; residual bookkeeping (+ nin_shortcut) in between reads fp32
+        while j < n and steps[j].kind == "store_res":
+            j += 1
+        c = steps[j] if j < n else None
+        if s.kind == "norm":
+            r.ordinal, r.how = ordinal[i], "apply"
+            nxt = steps[i + 1] if i + 1 < n else None
+            # norm + SiLU in front of a conv can stay pending as (a, s) coefficients; the frozen sweep's conversion pass is no fusion to switch off
+            pending = s.silu and nxt is not None and nxt.kind == "conv" and not nxt.downsample and (fuse_pre_gn or hand_over)
+            if pending and rec_fed(i):
+                r.how, has_rec = ("epilogue" if has_rec else "convert"), hand_over
+            elif pending and fuse_pre_gn and (hand_over or not rec[i + 1]) and nxt.conv.fuses_pre_gn(upsample2x=nxt.upsample):
+                r.how = "ride"
+        elif s.kind == "attn" or (s.kind == "conv" and s.downsample):
+            r.how, has_rec = ("down" if s.kind == "conv" else None), False
+        elif s.kind == "conv" and hand_over and rec[i] and (has_rec or s.upsample):
+            if c is not None and c.kind == "norm" and rec_fed(j):
+                r.rec_out = ordinal[j]
+            elif c is not None and c.kind == "conv" and c.upsample and rec[j]:
+                r.rec_out = "raw"
+            r.how, r.f32_out, has_rec = "rec", j > i + 1 or r.rec_out is None, r.rec_out is not None
+        elif s.kind == "conv" and hand_over:
+            r.how, has_rec = ("window_f32" if s.upsample else "plain"), False
+        elif s.kind == "conv":
+            has_pre = i > 0 and route[i - 1].how in ("convert", "ride")
+            wanted = slow_stats and c is not None and c.kind == "norm" and ordinal[j] in pooled
+            stats_fn = getattr(s.conv, "leaves_stats", None) if wanted else None
+            r.how = "rec" if rec[i] else "plain"
+            if stats_fn is not None and rec[i] and stats_fn(32, upsample2x=s.upsample, rec=True):
+                r.how = "rec_stats"
+            elif stats_fn is not None and has_pre and not s.upsample and not rec[i] and stats_fn(32):
+                r.how = "handover_stats"
+    return route
+
+
 class TileState:
-    __slots__ = ("x", "res", "pc", "pre", "stats")
+    __slots__ = ("x", "res", "pc", "pre", "stats", "xrec")
 
     def __init__(self, x):
         self.x, self.res, self.pc = x, [], 0
         self.pre = None   # pending fused pre-activation: gn_coeffs of the norm just resolved, consumed by the next conv
         self.stats = None  # slow mode: (var, mean) of x, left by the conv that produced it (None: nobody has them yet)
+        self.xrec = None  # the record image of x, where the producer wrote one (None: x exists as fp32 only)

@@ -160,15 +160,16 @@ def _worker_interrupt(rank, world, port, q):
         from modules.shared import state
         state.interrupted = False
         calls = [0]
-        orig = hook._run_until_norm
+        orig = hook._advance
 
-        def counted(steps, st, **kw):
-            calls[0] += 1
-            if rank == 1 and calls[0] == 3:
-                state.interrupted = True
-            return orig(steps, st, **kw)
+        def counted(route, st, norm=None, **kw):
+            if norm is None:            # a segment: the tile moves on to its next norm (with `norm` it only takes the norm it stands at)
+                calls[0] += 1
+                if rank == 1 and calls[0] == 3:
+                    state.interrupted = True
+            return orig(route, st, norm=norm, **kw)
 
-        hook._run_until_norm = counted
+        hook._advance = counted
         with torch.no_grad():
             out = hook(z)
         assert out.shape == (1, 3, 320, 448) and torch.isfinite(out).all()      # the host's cheap approximation: no tile finished
@@ -201,7 +202,7 @@ def test_interrupt_in_multi_rank_slow_mode_leaves_the_sweep_on_every_rank():
 def _rec_hook(net, ts, fast=True, rec_convs=True):
     import torch_engine as te
     hook = _hook(net, ts, True, fast)
-    # the record-path sweep (_run_tile_rec) on torch doubles; rec_convs=False: convs that the record kernels do not take (exact-fp32 mode,
+    # the record-path sweep (_advance on a hand-over route) on torch doubles; rec_convs=False: convs that the record kernels do not take (exact-fp32 mode,
     # odd channel counts) -- the same sweep on the fp32 hand-over calls, upsample windows through VAEHook._upconv_window_f32
     hook.engine, hook._pack = te.TorchEngineRec(), (te.TorchConvRec if rec_convs else te.TorchConvCounting)
     return hook
@@ -347,17 +348,24 @@ def test_live_windows_are_exact_and_tight_in_float64():
     pl = sys.modules[type(hook).__module__]
     steps = hook.program()
     norm_idx = [i for i, s in enumerate(steps) if s.kind == "norm"]
-    norm_ord = {i: k for k, i in enumerate(norm_idx)}
+    route = hook._route(steps, hand_over=True)
     g = torch.Generator().manual_seed(8)
     frozen = [(torch.rand(32, generator=g, dtype=torch.float64) + 0.5, torch.randn(32, generator=g, dtype=torch.float64) * 0.1) for _ in norm_idx]
     E = hook.engine
     coefs = [E.gn_coeffs(m, v, steps[i].norm[0], steps[i].norm[1], steps[i].channels, 32, 1e-6) for i, (v, m) in zip(norm_idx, frozen)]
     th, tw, valid = 38, 40, (11, 11, 27, 29)
     x = torch.randn(1, 4, th, tw, generator=g, dtype=torch.float64)
+
+    def sweep(windows):                  # the executor itself, one tile start to finish
+        st = pl.TileState(x)
+        hook._advance(route, st, frozen=(frozen, coefs), windows=windows)
+        assert st.pc == len(steps)
+        return st.x
+
     with torch.no_grad():
-        whole = hook._run_tile_rec(steps, x, frozen, coefs, norm_ord, None)
+        whole = sweep(None)
         windows, rect = pl.live_windows(steps, (th, tw), valid)
-        narrowed = hook._run_tile_rec(steps, x, frozen, coefs, norm_ord, windows)
+        narrowed = sweep(windows)
     assert len(windows) == 3 and narrowed.shape[2:] == ((rect[2] - rect[0]) * 8, (rect[3] - rect[1]) * 8)
 
     def valid_of(t, r):
@@ -374,7 +382,7 @@ def test_live_windows_are_exact_and_tight_in_float64():
     y0, x0, h, w = windows[ups[1]]
     tight[ups[1]] = (y0 - 2, x0 - 2, h, w)          # same absolute rectangle at the 4x level (its origin is relative to the 2x window)
     with torch.no_grad():
-        short = hook._run_tile_rec(steps, x, frozen, coefs, norm_ord, tight)
+        short = sweep(tight)
     assert short.shape == narrowed.shape
     off = (valid_of(short, rect) - ref).abs().max().item() / ref.abs().max().item()
     print(f"narrowed vs whole tile {exact:.1e}; windows one latent px short {off:.1e}")

@@ -147,7 +147,7 @@ class TorchSeqParOps:
         return torch.tanh(x)
 
 
-# ---- record-path doubles: the fast-mode sweep of scripts/tilevae.py (_run_tile_rec) with the hand-over between the 3x3 convs emulated
+# ---- record-path doubles: the fast-mode sweep of scripts/tilevae.py (VAEHook._advance on a hand-over route) with the hand-over between the 3x3 convs emulated
 # in fp32 torch, so that the host logic of that sweep -- which producer applies which norm, the live-window narrowing of the tiles
 # (live_windows), stacking by shape -- is checked against the oracle on CPU.
 class TorchRec:

@@ -123,6 +123,18 @@ int mdtile_plan_wrap_x(const mdtile_plan* plan);
  * the same calls are refused. */
 mdtile_plan* mdtile_plan_create_wrap(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int wrap_x, int wrap_y);
 int mdtile_plan_wrap_y(const mdtile_plan* plan);
+/* The wrapped grid displaced cyclically by (sx, sy) (a new offset every sampler step averages the tile borders out over time).
+ * Displacing every tile origin of a wrap plan on the circle does not change which tile indices cover a pixel, or in which order; it moves the pixel:
+ *   mdtile_gather_all_shift: tile t with plan origin (x_t, y_t) gets x_tile[ty, tx] = x_in[(y_t + sy + ty) mod h, (x_t + sx + tx) mod w]
+ *                            = mdtile_gather_all on roll(x_in, (-sy, -sx))
+ *   mdtile_blend_shift:      the value mdtile_blend computes for plan coordinate (y, x) -- same covering tiles in ascending tile index, d_weights /
+ *                            d_rescale / d_tile_w read in PLAN coordinates, same per-term operations and epilogue, fp32 accumulation from +0.0 -- is
+ *                            stored at out[(y + sy) mod h, (x + sx) mod w] = roll(mdtile_blend(...), (+sy, +sx)), bit for bit
+ * No table, weight map or reciprocal map is rebuilt for a shift.  0 <= sx < w, 0 <= sy < h; (0, 0) equals the unshifted calls bitwise.
+ * REFUSED (MDTILE_E_ARG, the text names the reason, nothing is written): a plain plan, a sparse plan, a shift out of range, a non-zero shift on
+ * an axis that does not wrap, and everything mdtile_gather_all / mdtile_blend refuse on a wrap plan (no regions exist in this call). */
+int mdtile_gather_all_shift(const mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs,
+                            int num_batches, int sx, int sy, mdtile_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Weight maps (init time, device).
@@ -211,6 +223,9 @@ typedef struct mdtile_blend_args {
 
 int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                  const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
+/* mdtile_blend on a wrap plan with the grid displaced by (sx, sy): specified with mdtile_gather_all_shift above. */
+int mdtile_blend_shift(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                       int sx, int sy, mdtile_stream_t stream);
 /* Which kernel mdtile_blend launches for these arguments, and in what shape -- answered by the SAME host function the launcher calls, from
  * the plan's host tables alone (no device is touched, no GPU is needed): tests pin a geometry to the code path it was written for.
  *   flags = the MDTILE_BLEND_* of the call; num_batches as for mdtile_blend (0 = no grid); ptrs_aligned16 = every batch pointer (the packed

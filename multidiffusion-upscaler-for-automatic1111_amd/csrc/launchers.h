@@ -15,10 +15,11 @@ namespace mdt {
 // d_fill for a sparse plan only.  gather_check: what every mdtile_gather* asks of its arguments.
 int wrap_weight_map(const struct ::mdtile_plan* plan, const float* d_tile_w, float* d_weights, hipStream_t s);
 int gather_check(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs);
+// shift = {sx, sy}: the shifted grid of mdtile_gather_all_shift / mdtile_blend_shift (wrap.hip, which checks it); null: not shifted.
 int walk_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi,
-                hipStream_t s);
+                hipStream_t s, const int* shift = nullptr);
 int walk_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
-               int num_regions, const void* d_fill, hipStream_t s);
+               int num_regions, const void* d_fill, hipStream_t s, const int* shift = nullptr);
 
 // ---- plan.hip
 int device_cus();      // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached

@@ -18,6 +18,11 @@
 // wrap.  What they add -- the gather's `active` table, the blend's liveness pass over `slot`, the skip of tiles that are not active and the
 // `fill` pass-through -- is compiled into k_walk_blend<..., SPARSE = true> only; the wrap-around instantiations hold none of it.
 //
+// The SHIFTED grid (mdtile_gather_all_shift / mdtile_blend_shift; wrap-around plans only) displaces every tile origin by (sx, sy)
+// on the circle.  That changes neither which tile indices cover a pixel nor their order, it moves the pixel: the gather adds the shift to the
+// source coordinate, the blend keeps its threads on PLAN coordinates and adds it to the store address.  Both are compiled under
+// `if constexpr (SHIFT)` into instantiations of their own, with an argument block of their own; the others hold none of it.
+//
 // Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
 // mdtile_blend_finalize -- neither wrap-around nor tile skipping is combined with regions or with the multi-GPU partial path.
 #include "launchers.h"
@@ -72,11 +77,19 @@ struct WrapGatherParams {
     void* batch[MDTILE_MAX_BATCHES];
 };
 static_assert(sizeof(WrapGatherParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// the shifted grid (mdtile_gather_all_shift): every tile origin displaced by (shift_x, shift_y) on the circle.  The kernels that
+// are not shifted keep the argument block above.
+struct WrapGatherShiftParams : WrapGatherParams {
+    int shift_x, shift_y;     // 0 <= shift_x < W, 0 <= shift_y < H; 0 on an axis that does not wrap
+};
+static_assert(sizeof(WrapGatherShiftParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
 // position s (a tile of the list, or a slot of a sparse plan) holds tile t: x_tile[(s mod tile_bs) * N + n, c, ty, tx] of batch s / tile_bs =
 // x_in[n, c, (y_t + ty) mod H, (x_t + tx) mod W].  grid: x = quads over (th rows x tw4), y = plane (n*C + c), z = position
-template <typename T>
-__global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
+// SHIFT: the origin is ((x_t + shift_x) mod W, (y_t + shift_y) mod H).  The reduced source coordinate is < extent and the shift is < extent, so
+// their sum is < 2 * extent: one more subtraction, after the first (x_t + shift_x + tx itself may pass 2 W: it is never formed).
+template <typename T, bool SHIFT>
+__global__ __launch_bounds__(256) void k_wrap_gather(const std::conditional_t<SHIFT, WrapGatherShiftParams, WrapGatherParams> P) {
     const int tw4 = (P.tw + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= tw4 * P.th) return;
@@ -87,11 +100,19 @@ __global__ __launch_bounds__(256) void k_wrap_gather(const WrapGatherParams P) {
     const int r = t / P.cols, cc = t - r * P.cols;
     int sy = P.ys[r] + ty;                // ys < H and ty < th <= H (th == H only on plain rows, ys = 0): one subtraction brings it back onto the canvas
     if (sy >= P.H) sy -= P.H;
+    if constexpr (SHIFT) {
+        sy += P.shift_y;
+        if (sy >= P.H) sy -= P.H;
+    }
     const T* srow = reinterpret_cast<const T*>(P.x_in) + (((size_t)n * P.C + c) * P.H + sy) * P.W;
     const int b = s / P.tile_bs, i = s - b * P.tile_bs;
     T* dst = reinterpret_cast<T*>(P.batch[b]) + (((size_t)i * P.N + n) * P.C + c) * ((size_t)P.th * P.tw) + (size_t)ty * P.tw + tx0;
     int sx = P.xs[cc] + tx0;              // xs < W and tx0 < tw <= W (tw == W only on plain columns, xs = 0): likewise
     if (sx >= P.W) sx -= P.W;
+    if constexpr (SHIFT) {
+        sx += P.shift_x;
+        if (sx >= P.W) sx -= P.W;
+    }
     const int nvalid = P.tw - tx0 < 4 ? P.tw - tx0 : 4;
     if (nvalid == 4 && sx + 3 < P.W) {    // the four source columns are consecutive in memory
         float v[4];
@@ -118,6 +139,12 @@ struct WalkBlendParams {
     const void* fill;         // [N, C, H, W] in the storage type: the value of every pixel that is not live
 };
 static_assert(sizeof(WalkBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// the shifted grid (mdtile_blend_shift): the value of plan coordinate (y, x) is stored at ((y + shift_y) mod H, (x + shift_x) mod W).
+// The kernels that are not shifted keep the argument block above.
+struct WalkBlendShiftParams : WalkBlendParams {
+    int shift_x, shift_y;     // 0 <= shift_x < W, 0 <= shift_y < H; 0 on an axis that does not wrap
+};
+static_assert(sizeof(WalkBlendShiftParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
 // the storage type as an integer of its size: what passes `fill` through without a float conversion
 template <typename T> struct RawOf { using type = unsigned short; };
@@ -164,8 +191,14 @@ template <> __device__ __forceinline__ void load4_aligned<__hip_bfloat16>(const 
 // A plain tile column that starts 1 - 3 px to the right of x0 has no test of its own: xs[c] + tw <= W there, so rel() gives
 // tx = W + (x0 - xs[c]) >= W - 3, hence tx + 3 >= W >= tw (never `whole`), and each tx + j either passes W and comes back as the true offset
 // x0 + j - xs[c] >= 0 or stays >= x0 + tw + j >= tw, which is not covered.
-template <typename T, int METHOD, int PP, bool SPARSE>
-__global__ __launch_bounds__(256) void k_walk_blend(const WalkBlendParams P) {
+//
+// SHIFT (wrap-around plans only, never SPARSE): the thread still owns the quad of PLAN coordinates (y, x0 .. x0 + 3) -- the walk, the weight /
+// rescale loads and the tile loads are those above -- and only its store moves: to row (y + shift_y) mod H, columns (x0 + shift_x + j) mod W.
+// The displaced quad is in general not aligned and, on a wrapped x, may be cut by the seam: one element-aligned group of four when it is not
+// cut, per element with the column taken mod W when it is.
+template <typename T, int METHOD, int PP, bool SPARSE, bool SHIFT>
+__global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHIFT, WalkBlendShiftParams, WalkBlendParams> P) {
+    static_assert(!(SPARSE && SHIFT), "a sparse plan is never shifted");
     const int W4 = (P.W + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= W4 * P.H) return;
@@ -283,6 +316,33 @@ __global__ __launch_bounds__(256) void k_walk_blend(const WalkBlendParams P) {
         }
     }
 
+    if constexpr (SHIFT) {
+        using R = typename RawOf<T>::type;
+        int yd = y + P.shift_y;                            // y < H, shift_y < H: one subtraction
+        if (yd >= P.H) yd -= P.H;
+        int xd = x0 + P.shift_x;                           // x0 < W, shift_x < W: likewise
+        if (xd >= P.W) xd -= P.W;
+        const bool uncut = nvalid == 4 && xd + 3 < P.W;    // the four destination columns are consecutive in memory
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp) {
+            R* drow = reinterpret_cast<R*>(P.out) + ((size_t)(p0 + pp) * P.H + yd) * P.W;
+            if (uncut) {
+                raw4_u<R> o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o.v[j] = raw_bits<T>(acc[pp][j]);
+                *reinterpret_cast<raw4_u<R>*>(drow + xd) = o;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j >= nvalid) continue;
+                    const int xj = xd + j < P.W ? xd + j : xd + j - P.W;
+                    drow[xj] = raw_bits<T>(acc[pp][j]);
+                }
+            }
+        }
+        return;
+    }
+
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp) {
         const size_t off = ((size_t)(p0 + pp) * P.H + y) * P.W + x0;
@@ -327,16 +387,32 @@ int planes_per_thread(const WalkBlendParams& P) {
 using WalkBlendKernel = void (*)(const WalkBlendParams);
 template <typename T, int PP>
 WalkBlendKernel walk_blend_kernel(int method, bool sparse) {
-    if (method == MDTILE_METHOD_MD) return sparse ? k_walk_blend<T, MDTILE_METHOD_MD, PP, true> : k_walk_blend<T, MDTILE_METHOD_MD, PP, false>;
-    return sparse ? k_walk_blend<T, MDTILE_METHOD_MOD, PP, true> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false>;
+    if (method == MDTILE_METHOD_MD) return sparse ? k_walk_blend<T, MDTILE_METHOD_MD, PP, true, false> : k_walk_blend<T, MDTILE_METHOD_MD, PP, false, false>;
+    return sparse ? k_walk_blend<T, MDTILE_METHOD_MOD, PP, true, false> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false, false>;
 }
+
+dim3 walk_blend_grid(const WalkBlendParams& P, int pp) { return dim3(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / pp); }
 
 template <typename T>
 void launch_walk_blend(const WalkBlendParams& P, int method, hipStream_t s) {
     const int pp = planes_per_thread(P);
     const bool sparse = P.slot != nullptr;
     const WalkBlendKernel k = pp == 4 ? walk_blend_kernel<T, 4>(method, sparse) : pp == 2 ? walk_blend_kernel<T, 2>(method, sparse) : walk_blend_kernel<T, 1>(method, sparse);
-    hipLaunchKernelGGL(k, dim3(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / pp), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k, walk_blend_grid(P, pp), dim3(256), 0, s, P);
+}
+
+// the shifted forms: the same launch shape, the kernels compiled with SHIFT
+using WalkBlendShiftKernel = void (*)(const WalkBlendShiftParams);
+template <typename T, int PP>
+WalkBlendShiftKernel walk_blend_shift_kernel(int method) {
+    return method == MDTILE_METHOD_MD ? k_walk_blend<T, MDTILE_METHOD_MD, PP, false, true> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false, true>;
+}
+
+template <typename T>
+void launch_walk_blend_shift(const WalkBlendShiftParams& P, int method, hipStream_t s) {
+    const int pp = planes_per_thread(P);
+    const WalkBlendShiftKernel k = pp == 4 ? walk_blend_shift_kernel<T, 4>(method) : pp == 2 ? walk_blend_shift_kernel<T, 2>(method) : walk_blend_shift_kernel<T, 1>(method);
+    hipLaunchKernelGGL(k, walk_blend_grid(P, pp), dim3(256), 0, s, P);
 }
 
 }  // namespace
@@ -359,7 +435,9 @@ int mdt::gather_check(const mdtile_plan* p, int dtype, int N, int C, const void*
 
 // positions [s_lo, s_hi) -- tiles of a wrap-around plan, active slots of a sparse one -- into the plan's batch buffers ptrs[0 .. nptrs) (holes
 // are fine: only the batches of those positions are touched)
-int mdt::walk_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi, hipStream_t s) {
+// shift: null, or {shift_x, shift_y} of mdtile_gather_all_shift (checked there) -> the SHIFT kernels
+int mdt::walk_gather(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* ptrs, int nptrs, int s_lo, int s_hi, hipStream_t s,
+                     const int* shift) {
     if (int rc = gather_check(p, dtype, N, C, d_x_in, ptrs)) return rc;
     const bool sparse = plan_sparse(p);
     const char* kind = sparse ? "sparse" : wrap_kind(p);
@@ -372,23 +450,30 @@ int mdt::walk_gather(const mdtile_plan* p, int dtype, int N, int C, const void* 
     }
     for (int q = s_lo; q < s_hi; ++q) MDT_CHECK_ARG(ptrs[q / p->tile_bs], "mdtile_gather: null batch pointer %d", q / p->tile_bs);
     if (int rc = plan_upload(p)) return rc;
-    WrapGatherParams P;
+    WrapGatherShiftParams P;
     memset(&P, 0, sizeof(P));
     P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.tile_bs = p->tile_bs; P.N = N; P.C = C;
     P.s_lo = s_lo; P.xs = p->d_xs; P.ys = p->d_ys; P.active = sparse ? p->d_active : nullptr; P.x_in = d_x_in;
     for (int b = 0; b < nptrs; ++b) P.batch[b] = ptrs[b];
     dim3 grid(cdiv((long long)p->th * ((p->tw + 3) / 4), 256), N * C, s_hi - s_lo), block(256);
-    with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL(k_wrap_gather<std::remove_pointer_t<decltype(tag)>>, grid, block, 0, s, P); });
+    if (shift) {
+        P.shift_x = shift[0]; P.shift_y = shift[1];
+        with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL((k_wrap_gather<std::remove_pointer_t<decltype(tag)>, true>), grid, block, 0, s, P); });
+    } else {
+        const WrapGatherParams& P0 = P;
+        with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL((k_wrap_gather<std::remove_pointer_t<decltype(tag)>, false>), grid, block, 0, s, P0); });
+    }
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }
 
 // The grid blend that takes no regions, flags or row bands: mdtile_blend on a wrap-around plan (d_fill null) and mdtile_blend_sparse (the caller
 // has checked that the plan is sparse).  The texts name the entry point and the kind of plan.
+// shift: null, or {shift_x, shift_y} of mdtile_blend_shift (checked there; never a sparse plan) -> the SHIFT kernels
 int mdt::walk_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, int num_regions, const void* d_fill,
-                    hipStream_t s) {
+                    hipStream_t s, const int* shift) {
     const bool sparse = plan_sparse(p);
-    const char* fn = sparse ? "mdtile_blend_sparse" : "mdtile_blend";
+    const char* fn = sparse ? "mdtile_blend_sparse" : shift ? "mdtile_blend_shift" : "mdtile_blend";
     const char* kind = sparse ? "sparse" : wrap_kind(p);
     const char* what = sparse ? "tile skipping" : "wrap-around";
     const char* whose = sparse ? " (the parent's map)" : "";
@@ -412,14 +497,47 @@ int mdt::walk_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void
     else MDT_CHECK_ARG(a->d_tile_w && a->d_rescale, "%s: Mixture of Diffusers needs d_tile_w and d_rescale%s", fn, whose);
     for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "%s: null batch pointer %d", fn, b);
     if (int rc = plan_upload(p)) return rc;
-    WalkBlendParams P;
+    WalkBlendShiftParams P;
     memset(&P, 0, sizeof(P));
     P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.rows = p->rows; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
     P.xs = p->d_xs; P.ys = p->d_ys; P.colquad = p->d_colquad; P.rowinfo = p->d_rowinfo;
     P.weights = a->d_weights; P.tile_w = a->d_tile_w; P.rescale = a->d_rescale; P.out = a->d_x_out;
     if (sparse) { P.slot = p->d_slot; P.fill = d_fill; }
     for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
-    with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
+    if (shift) {
+        P.shift_x = shift[0]; P.shift_y = shift[1];
+        with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend_shift<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
+    } else {
+        with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
+    }
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
+}
+
+// what both shifted entry points ask of the plan and the shift before anything else is looked at
+static int shift_check(const char* fn, const mdtile_plan* p, int sx, int sy) {
+    MDT_CHECK_ARG(p, "%s: null plan", fn);
+    MDT_CHECK_ARG(!plan_sparse(p), "%s: refused on a sparse plan: the grid shift is not combined with tile skipping", fn);
+    MDT_CHECK_ARG(plan_wraps(p), "%s: refused on a plain plan: only a wrap-around plan (mdtile_plan_create_wrap) has a circle to shift the grid on", fn);
+    MDT_CHECK_ARG(sx >= 0 && sx < p->w && sy >= 0 && sy < p->h, "%s: shift (%d, %d) out of range: 0 <= sx < %d and 0 <= sy < %d", fn, sx, sy, p->w, p->h);
+    MDT_CHECK_ARG(sx == 0 || p->wrap_x, "%s: sx = %d on a %s plan: the x axis does not wrap", fn, sx, wrap_kind(p));
+    MDT_CHECK_ARG(sy == 0 || p->wrap_y, "%s: sy = %d on a %s plan: the y axis does not wrap", fn, sy, wrap_kind(p));
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_gather_all_shift(const mdtile_plan* p, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs, int num_batches, int sx,
+                                       int sy, mdtile_stream_t stream) {
+    if (int rc = shift_check("mdtile_gather_all_shift", p, sx, sy)) return rc;
+    MDT_CHECK_ARG(batch_ptrs, "mdtile_gather_all_shift: null argument");
+    MDT_CHECK_ARG(num_batches == p->num_batches, "mdtile_gather_all_shift: %d batches given, the %s plan has %d (it has no packed form)", num_batches,
+                  wrap_kind(p), p->num_batches);
+    const int shift[2] = {sx, sy};
+    return walk_gather(p, dtype, N, C, d_x_in, batch_ptrs, num_batches, 0, plan_tiles(p), as_stream(stream), shift);
+}
+
+extern "C" int mdtile_blend_shift(const mdtile_plan* p, const mdtile_blend_args* args, const void* const* batch_out, int num_batches, int sx, int sy,
+                                  mdtile_stream_t stream) {
+    if (int rc = shift_check("mdtile_blend_shift", p, sx, sy)) return rc;
+    const int shift[2] = {sx, sy};
+    return walk_blend(p, args, batch_out, num_batches, 0, nullptr, as_stream(stream), shift);
 }

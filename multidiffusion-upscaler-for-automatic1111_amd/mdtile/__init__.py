@@ -87,10 +87,12 @@ _SIGNATURES = {
     "mdtile_rect_mul_canvas": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mdtile_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "mdtile_gather_all": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
+    "mdtile_gather_all_shift": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
     "mdtile_gather_range": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_gather_rect": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mdtile_stream_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "mdtile_blend": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_Region), c_int, c_void_p]),
+    "mdtile_blend_shift": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
     "mdtile_blend_dispatch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _IP]),
     "mdtile_blend_finalize": (c_int, [c_void_p, POINTER(_BlendArgs), c_void_p, POINTER(_Region), c_int, c_void_p]),
     "mdtile_tile_activity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -691,6 +693,23 @@ def gather_all(plan: Plan, x_in: torch.Tensor, out: Optional[Sequence[torch.Tens
     return list(out)
 
 
+def gather_all_shift(plan: Plan, x_in: torch.Tensor, sx: int, sy: int, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """gather_all with the wrapped grid displaced cyclically by (sx, sy): every tile batch of roll(x_in, (-sy, -sx)), one launch, nothing copied.
+    Wrap-around plans only; a non-zero shift needs an axis that wraps."""
+    _dev_tensor(x_in, "x_in")
+    N, C, H, W = x_in.shape
+    assert (H, W) == (plan.h, plan.w)
+    if out is None:
+        out = [torch.empty((len(b) * N, C, plan.tile_h, plan.tile_w), dtype=x_in.dtype, device=x_in.device)
+               for b in plan.batches]
+    for i, t in enumerate(out):
+        _dev_tensor(t, f"out[{i}]", x_in.dtype)
+    ptrs = (c_void_p * max(1, len(out)))(*[t.data_ptr() for t in out])
+    _check(lib().mdtile_gather_all_shift(plan.handle, dtype_code(x_in.dtype), N, C, _p(x_in), ptrs, len(out), int(sx), int(sy), _stream()),
+           "mdtile_gather_all_shift")
+    return list(out)
+
+
 def gather_range(plan: Plan, x_in: torch.Tensor, packed: torch.Tensor, tile_lo: int, tile_hi: int) -> torch.Tensor:
     """Tiles [tile_lo, tile_hi) into the packed [T*N, C, th, tw] buffer (rows of other tiles are left untouched)."""
     _dev_tensor(x_in, "x_in")
@@ -859,6 +878,21 @@ def blend(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C:
     """One fused launch replacing the scatter/normalise/feather op sequence of sample_one_step / apply_model_hijack."""
     return BlendCall(plan, method, batch_out, N, C, weights=weights, tile_w=tile_w, rescale=rescale, regions=regions, out=out, dtype=dtype,
                      device=device, partial=partial, tile_range=tile_range, row_range=row_range, packed=packed)()
+
+
+def blend_shift(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, sx: int, sy: int, weights=None, tile_w=None,
+                rescale=None, out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
+    """blend on a wrap-around plan with the grid displaced cyclically by (sx, sy): roll(blend(...), (+sy, +sx)) bit for bit, in one launch.
+    weights / tile_w / rescale are the plan's unshifted maps."""
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    _check(lib().mdtile_blend_shift(plan.handle, ctypes.byref(a), ptrs, len(batch_out), int(sx), int(sy), _stream()), "mdtile_blend_shift")
+    return out
 
 
 def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, fill: torch.Tensor, weights=None, tile_w=None,

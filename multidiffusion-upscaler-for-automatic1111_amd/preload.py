@@ -27,6 +27,12 @@ def preload(parser):
              "input with the rows of the other edge. With --mdtile-wrap-x the canvas is a torus (seamless textures that tile in both directions). "
              "Not combined with region control. Default: off.")
     parser.add_argument(
+        "--mdtile-grid-shift", action="store_true",
+        help="Tiled Diffusion with --mdtile-wrap-x / --mdtile-wrap-y (MultiDiffusion, Mixture of Diffusers): displace the whole tile grid cyclically "
+             "along the wrapped axes by a new offset every sampler step (a function of the job's seed and the step), so that no tile border stays in "
+             "place for two steps and small or zero overlaps become usable. Ignored on a grid that does not wrap, by Noise Inversion's own "
+             "evaluations and by DemoFusion. Default: off, the grid stays where it is.")
+    parser.add_argument(
         "--mdtile-vae-seam-blend", type=int, default=None, metavar="PX",
         help="Tiled VAE decoder: cross-fade neighbouring tiles over PX image pixels per side of a tile border (1-88; 16-32 is a sensible range), out "
              "of the padding that is otherwise decoded and thrown away, instead of pasting the tiles edge to edge. Every decoded tile is kept "

@@ -25,7 +25,8 @@ from modules.shared import state
 from modules.processing import opt_f
 
 import mdtile
-from tile_utils.utils import BBox, BBoxSettings, BlendMode, Condition, CustomBBox, NoiseInverseCache, Prompt, get_retouch_mask
+from tile_utils.utils import (BBox, BBoxSettings, BlendMode, Condition, CustomBBox, NoiseInverseCache, Prompt, get_retouch_mask, grid_shift,
+                              shifted_bboxes)
 
 try:  # isinstance targets; absent in a bare test host
     from modules.sd_samplers_kdiffusion import KDiffusionSampler
@@ -41,6 +42,8 @@ class AbstractDiffusion:
 
     # why get_noise never skips tiles (--mdtile-inpaint-skip)
     NOISE_INVERSION_FULL = "Noise Inversion's own evaluations (get_noise) stay full-canvas"
+    # why get_noise never moves the grid (--mdtile-grid-shift)
+    NOISE_INVERSION_UNSHIFTED = "Noise Inversion's own evaluations (get_noise) follow no sampler step"
 
     def __init__(self, p, sampler):
         self.method = type(self).__name__
@@ -78,6 +81,10 @@ class AbstractDiffusion:
         self.wrap_y = False
         self.wrap_ext_y = 0
         self._wrap_copies: Dict[str, tuple] = {}
+        # --mdtile-grid-shift: the wrapped grid moves by step_shift() every sampler step (init_grid_bbox decides; only on a plan that wraps)
+        self.grid_shift = False
+        self._shift_at: Optional[tuple] = None       # (sampler step, (sx, sy), the step's boxes): every evaluation of one step shares them
+        self._shift_notes: set = set()
         # --mdtile-inpaint-skip: decided on the job's first full-size evaluation (inpaint_skip), when the host has computed p.nmask
         self.skip_mode: Optional[str] = None         # None = not decided yet | "full" | "sparse" | "empty" (the mask touches no tile)
         self.sparse_plan: Optional[mdtile.Plan] = None
@@ -213,6 +220,11 @@ class AbstractDiffusion:
         """--mdtile-inpaint-skip (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_inpaint_skip", False))
 
+    @staticmethod
+    def grid_shift_requested() -> bool:
+        """--mdtile-grid-shift (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_grid_shift", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
         self.requested_tile_bs = int(tile_bs)
@@ -232,11 +244,21 @@ class AbstractDiffusion:
                       "itself across the seam; the rows of the plain grid are used.")
             else:
                 self.wrap_y = True
+        self.grid_shift, self._shift_at = False, None
+        if self.grid_shift_requested():
+            if self.wrap_x or self.wrap_y:
+                self.grid_shift = True
+            else:
+                print("[Tiled Diffusion] --mdtile-grid-shift ignored: the grid does not wrap around (--mdtile-wrap-x / --mdtile-wrap-y), there is no "
+                      "circle to move it on; the grid stays where it is.")
         self.plan = mdtile.Plan(self.w, self.h, tile_w, tile_h, overlap, tile_bs, clamp=True, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
         # wrap-x: tiles that span the seam end at x + w > W; the Python slices below cut them from a copy of their source that repeats its
         # first `wrap_ext` columns behind the last one (extended_x)
         self.wrap_ext = max((b[0] + b[2] - self.w for b in self.plan.bboxes), default=0) if self.wrap_x else 0
         self.wrap_ext_y = max((b[1] + b[3] - self.h for b in self.plan.bboxes), default=0) if self.wrap_y else 0
+        if self.grid_shift:      # a shifted tile may start at the last column / row: the whole tile size, fixed for the job (the copies stay valid)
+            self.wrap_ext = self.plan.tile_w if self.wrap_x else 0
+            self.wrap_ext_y = self.plan.tile_h if self.wrap_y else 0
         self._wrap_copies = {}
         if self.wrap_x or self.wrap_y:
             if getattr(self.p, "extra_generation_params", None) is None:
@@ -245,6 +267,8 @@ class AbstractDiffusion:
                 self.p.extra_generation_params["Tiled Diffusion wrap x"] = True
             if self.wrap_y:
                 self.p.extra_generation_params["Tiled Diffusion wrap y"] = True
+            if self.grid_shift:
+                self.p.extra_generation_params["Tiled Diffusion grid shift"] = True
         self.tile_w, self.tile_h = self.plan.tile_w, self.plan.tile_h
         self.num_tiles, self.num_batches, self.tile_bs = self.plan.num_tiles, self.plan.num_batches, self.plan.tile_bs
         tile_weights = self.get_tile_weights()
@@ -269,6 +293,36 @@ class AbstractDiffusion:
         ext = ext.contiguous()
         self._wrap_copies[slot] = (t, t._version, ext)
         return ext
+
+    # ---- --mdtile-grid-shift: the wrapped grid displaced cyclically, anew every sampler step ---------------------------------
+    def job_seed(self) -> int:
+        """The job's first seed: p.all_seeds[0], else p.seed, else 0."""
+        seeds = getattr(self.p, "all_seeds", None)
+        seed = seeds[0] if seeds else getattr(self.p, "seed", None)
+        try:
+            return int(seed)
+        except (TypeError, ValueError):
+            return 0
+
+    def step_shift(self, own_evaluation: Optional[str] = None):
+        """((sx, sy), the boxes of this evaluation).  With the option active: tile_utils.grid_shift of the job's seed and state.sampling_step on
+        the axes that wrap, 0 on the others, and the plan's boxes displaced by it; every evaluation made while the counter keeps its value (cond
+        and uncond calls, the slices of a --lowvram batch) gets the same pair, so that CFG subtracts two results of one tiling.
+        own_evaluation: an evaluation that never moves the grid names itself here -> shift (0, 0), with one line per job."""
+        if not self.grid_shift:
+            return (0, 0), self.batched_bboxes
+        if own_evaluation is not None:
+            if own_evaluation not in self._shift_notes:
+                self._shift_notes.add(own_evaluation)
+                print(f"[Tiled Diffusion] --mdtile-grid-shift not applied: {own_evaluation}; they run on the grid where it is.")
+            return (0, 0), self.batched_bboxes
+        step = int(state.sampling_step)
+        if self._shift_at is None or self._shift_at[0] != step:
+            seed = self.job_seed()
+            sx = grid_shift(seed, step, 0, self.w) if self.wrap_x else 0
+            sy = grid_shift(seed, step, 1, self.h) if self.wrap_y else 0
+            self._shift_at = (step, (sx, sy), shifted_bboxes(self.batched_bboxes, sx, sy, self.w, self.h))
+        return self._shift_at[1], self._shift_at[2]
 
     # ---- --mdtile-inpaint-skip: only the tiles the job's latent mask touches ------------------------------------------------------------
     def _skip_note(self, reason: str):

@@ -85,10 +85,14 @@ class MixtureOfDiffusers(AbstractDiffusion):
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
+        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
+        if self.grid_shift:
+            (sx, sy), batched_bboxes = self.step_shift(self.NOISE_INVERSION_UNSHIFTED if noise_inverse_step >= 0 else None)
 
         tile_outs: List[Tensor] = []
         if self.draw_background:
-            x_tiles = mdtile.gather_all(plan, x_in)                      # K2, one launch
+            # K2, one launch
+            x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
             for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
@@ -131,6 +135,10 @@ class MixtureOfDiffusers(AbstractDiffusion):
         if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MOD, tile_outs, N, C, fill=x_in, tile_w=self.get_tile_weights(),
                                                 rescale=self.rescale_factor)
+            return self.x_buffer
+        if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
+            self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MOD, tile_outs, N, C, sx=sx, sy=sy, tile_w=self.get_tile_weights(),
+                                               rescale=self.rescale_factor)
             return self.x_buffer
         # K4 + K6 + K7 in one launch; pixels nobody paints stay 0, as upstream
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights() if tile_outs else None,

@@ -123,10 +123,14 @@ class MultiDiffusion(AbstractDiffusion):
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
+        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
+        if self.grid_shift:
+            (sx, sy), batched_bboxes = self.step_shift(None if own_evaluation is None else self.NOISE_INVERSION_UNSHIFTED)
 
         tile_outs: List[Tensor] = []
         if self.draw_background:
-            x_tiles = mdtile.gather_all(plan, x_in)                      # K2: every tile batch, one launch
+            # K2: every tile batch, one launch
+            x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
             for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
@@ -152,6 +156,9 @@ class MultiDiffusion(AbstractDiffusion):
 
         if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in, weights=self.weights)
+            return self.x_buffer
+        if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
+            self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MD, tile_outs, N, C, sx=sx, sy=sy, weights=self.weights)
             return self.x_buffer
         # K3 + K5 + K6 + K7 in one launch
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MD, tile_outs, N, C, weights=self.weights,

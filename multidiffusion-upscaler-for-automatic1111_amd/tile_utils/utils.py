@@ -182,6 +182,23 @@ def split_bboxes(w: int, h: int, tile_w: int, tile_h: int, overlap: int = 16,
     return [BBox(*b) for b in plan.bboxes], weight
 
 
+def grid_shift(seed: int, step: int, axis: int, extent: int) -> int:
+    """--mdtile-grid-shift: the cyclic displacement of the wrapped tile grid along one axis (0 = x, 1 = y) at one sampler step, in
+    [0, extent).  A pure integer function (the splitmix64 finaliser on seed + golden-ratio increments): it touches no torch or numpy
+    generator, so the sampler's noise does not depend on whether the option is set."""
+    m = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (2 * int(step) + int(axis) + 1)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    z ^= z >> 31
+    return z % int(extent)
+
+
+def shifted_bboxes(batched_bboxes: List[List[BBox]], sx: int, sy: int, w: int, h: int) -> List[List[BBox]]:
+    """The boxes of a wrap plan with every origin displaced cyclically: ((x + sx) mod w, (y + sy) mod h), same sizes, same order."""
+    return [[BBox((b.x + sx) % w, (b.y + sy) % h, b.w, b.h) for b in batch] for batch in batched_bboxes]
+
+
 def gaussian_weights(tile_w: int, tile_h: int) -> Tensor:
     """Mixture-of-Diffusers tile weight (upstream utils.py:180-194), generated on the GPU in fp64 -> fp32."""
     return mdtile.gaussian_weights(tile_w, tile_h, devices.device)

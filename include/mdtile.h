@@ -631,6 +631,38 @@ int mdtile_vae_assemble_blend(const mdtile_vae_tile* tiles, int rows, int cols, 
 /* idempotent: kernels running on `device` may read memory of `peer` afterwards (MDTILE_E_ARG when the hardware cannot) */
 int mdtile_enable_peer_access(int device, int peer);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Tiled VAE tile skipping (img2img inpainting, decoder): decode only the tiles the job's overlay mask touches and complete the image
+ * without the others.  Nothing upstream corresponds to it.
+ *
+ * mdtile_mask_activity_u8: d_mask uint8 [RH, RW] (row pitch RW bytes), d_boxes4 int32 [n_boxes][4] = (x1, x2, y1, y2) in image px as
+ *   mdtile_vae_split_tiles returns them, d_active int32 [n_boxes], all on the calling device.  active[i] = 1 iff some byte of
+ *   mask[y1:y2, x1:x2] is not zero, else 0.  The call writes every entry (a stream-ordered clear, then ONE kernel over blocks
+ *   (chunk of rows, box): 16-byte reads where the row segment allows, scalar bytes in front of the first and behind the last 16-byte
+ *   boundary, the OR per wave, a wave that saw a non-zero byte stores 1); the caller does not zero d_active.  The boxes are copied to the
+ *   host and checked before anything is written, which waits for `stream` once.  MDTILE_E_ARG, the reason in mdtile_last_error, nothing
+ *   written: a null pointer, RH or RW < 1, n_boxes outside 1 .. MDTILE_MASK_ACTIVITY_MAX_BOXES (4096: an 8K image at decoder tile 48 has 441 tiles),
+ *   a box that is empty or not inside RW x RH.
+ * mdtile_vae_assemble_sparse (decoder: out = in * 8): the tiles go into result [N,C,RH,RW] exactly as mdtile_vae_assemble(...,
+ *   is_decoder = 1, ...) puts them -- its checks, its peer mapping, its kernel, its bits -- and every fill box (x1, x2, y1, y2; host ints) is
+ *   written as
+ *       result[n, c, y, x] = (float)fill[y, x, c] / 127.5f - 1.0f      (one IEEE fp32 division, one subtraction; every n)
+ *   from d_fill_u8, ONE uint8 image [RH, RW, C] (interleaved, on the calling device), or as +0.0f when d_fill_u8 is NULL.  The fill's bytes
+ *   are read as one contiguous run per row, the planes written in 16-byte stores from the row's first 16-byte boundary on.  Checked for the
+ *   whole call before anything is launched (MDTILE_E_ARG, nothing written): mdtile_vae_assemble's tests of every tile; every fill box
+ *   non-empty and inside RW x RH; no fill box equal to a tile's out box; no two boxes (tile out boxes and fill boxes together) overlapping;
+ *   their areas summing to RH * RW; n_tiles + n_fill <= MDTILE_VAE_SPARSE_MAX_BOXES.  Together: the boxes partition the result and every
+ *   pixel is written exactly once (the result need not be zeroed).  n_tiles == 0 (tiles may be NULL) and n_fill == 0 (fill_boxes4 may be
+ *   NULL) are allowed.  The tables travel in the kernel arguments (MDTILE_VAE_ASSEMBLE_CHUNK tiles, MDTILE_VAE_FILL_CHUNK fill boxes per
+ *   launch): stream-ordered, no allocation, no host synchronisation, no host memory referenced after the call returns.
+ * -------------------------------------------------------------------------------------------------------- */
+#define MDTILE_MASK_ACTIVITY_MAX_BOXES 4096
+#define MDTILE_VAE_SPARSE_MAX_BOXES 4096
+#define MDTILE_VAE_FILL_CHUNK 128
+int mdtile_mask_activity_u8(const uint8_t* d_mask, int RH, int RW, const int* d_boxes4, int n_boxes, int* d_active, mdtile_stream_t stream);
+int mdtile_vae_assemble_sparse(const mdtile_vae_tile* tiles, int n_tiles, const int* fill_boxes4, int n_fill, const uint8_t* d_fill_u8, int N, int C,
+                               float* d_result, int RH, int RW, mdtile_stream_t stream);
+
 /* fast-mode estimator input (tilevae.py:545-559): scale_factor = tile_size / max(H, W); nearest-exact resample of
  * z [N,C,H,W] to [N,C,oh,ow] (sizes from mdtile_vae_fast_size), per-channel re-standardisation (unbiased std over
  * N,H,W of both), clamp to [min z, max z].  d_ws: mdtile_vae_fast_ws_size(C) bytes. */

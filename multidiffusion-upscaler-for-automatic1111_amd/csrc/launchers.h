@@ -21,8 +21,15 @@ int walk_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const
 int walk_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                int num_regions, const void* d_fill, hipStream_t s, const int* shift = nullptr);
 
+// ---- vae_assemble.hip: mdtile_vae_assemble in two halves, for vae_skip.hip (mdtile_vae_assemble_sparse pastes its tiles with them).
+// vae_assemble_check: every test of the table and the result, the peer mapping of every source device; errors name `who`.
+int device_of(const void* p);      // the device that owns `p` (device memory of this process), or -1
+int vae_assemble_check(const char* who, const ::mdtile_vae_tile* tiles, int n_tiles, int N, int C, int is_decoder, const float* d_result, int RH,
+                       int RW);
+int vae_assemble_launch(const ::mdtile_vae_tile* tiles, int n_tiles, int N, int C, int is_decoder, float* d_result, int RH, int RW, hipStream_t s);
+
 // ---- plan.hip
-int device_cus();      // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached
+int device_cus();     // multiProcessorCount of the device that was current at the first call (256 if it cannot be read), cached
 
 // ---- vae_conv_bf16x3.hip
 bool conv_bf16x3_eligible(int cout, int cin, int ksize);

@@ -37,6 +37,9 @@ ATTN_V_CHANNEL_MAJOR = 2
 MAX_BATCHES, MAX_REGIONS = 320, 16
 VAE_ASSEMBLE_CHUNK = 32
 VAE_BLEND_CHUNK = 16
+MASK_ACTIVITY_MAX_BOXES = 4096
+VAE_SPARSE_MAX_BOXES = 4096
+VAE_FILL_CHUNK = 128
 
 _DTYPES = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 
@@ -183,6 +186,8 @@ _SIGNATURES = {
     "mdtile_vae_assemble": (c_int, [POINTER(_VaeTile), c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_vae_assemble_blend": (c_int, [POINTER(_VaeTile), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_enable_peer_access": (c_int, [c_int, c_int]),
+    "mdtile_mask_activity_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "mdtile_vae_assemble_sparse": (c_int, [POINTER(_VaeTile), c_int, _IP, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mdtile_vae_fast_size": (c_int, [c_int, c_int, c_int, _IP, _IP]),
     "mdtile_vae_fast_ws_size": (c_size_t, [c_int]),
     "mdtile_vae_fast_input": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -1423,6 +1428,49 @@ def vae_assemble_blend(tiles: Sequence[Tuple[torch.Tensor, Sequence[int], Sequen
         table[k] = _VaeTile(t.data_ptr(), t.shape[2], t.shape[3], (c_int * 4)(*ib), (c_int * 4)(*ob))
     _check(lib().mdtile_vae_assemble_blend(table, int(rows), int(cols), N, C, int(is_decoder), int(band), _p(result), RH, RW, _stream()),
            "mdtile_vae_assemble_blend")
+
+
+def mask_activity_u8(mask: torch.Tensor, boxes: Sequence[Sequence[int]]) -> List[int]:
+    """Per box (x1, x2, y1, y2) in image px, as vae_split_tiles returns them: 1 when some byte of mask[y1:y2, x1:x2] is not zero, else 0.
+    mask: uint8 [RH, RW] on the device.  One launch and one device-to-host copy of the flags; MdtileError for a box outside the mask, no box
+    or more than MASK_ACTIVITY_MAX_BOXES."""
+    _dev_tensor(mask, "mask", torch.uint8)
+    if mask.dim() != 2:
+        raise MdtileError(f"mask_activity_u8: mask {tuple(mask.shape)} is not [RH, RW]")
+    flat = [int(v) for b in boxes for v in b]
+    if len(flat) != 4 * len(boxes):
+        raise MdtileError("mask_activity_u8: every box is (x1, x2, y1, y2)")
+    d_boxes = torch.tensor(flat, dtype=torch.int32).view(-1, 4).to(mask.device)
+    flags = torch.empty(max(1, len(boxes)), dtype=torch.int32, device=mask.device)
+    with torch.cuda.device(mask.device):
+        _check(lib().mdtile_mask_activity_u8(_p(mask), int(mask.shape[0]), int(mask.shape[1]), _p(d_boxes), len(boxes), _p(flags), _stream()),
+               "mdtile_mask_activity_u8")
+    return flags[:len(boxes)].cpu().tolist()
+
+
+def vae_assemble_sparse(tiles: Sequence[Tuple[torch.Tensor, Sequence[int], Sequence[int]]], fill_boxes: Sequence[Sequence[int]],
+                        fill: Optional[torch.Tensor], result: torch.Tensor) -> None:
+    """vae_assemble (decoder) of the tiles that were decoded, and every box of fill_boxes (x1, x2, y1, y2) written from `fill` -- one uint8
+    [RH, RW, C] image on the result's device, as (float)byte / 127.5 - 1 -- or with 0.0 when fill is None.  The tiles' out boxes and the
+    fill boxes must partition the result: every pixel is written once (it need not be zeroed); MdtileError, and nothing written, otherwise."""
+    _dev_tensor(result, "result", torch.float32)
+    N, C, RH, RW = result.shape
+    if fill is not None:
+        _dev_tensor(fill, "fill", torch.uint8)
+        if tuple(fill.shape) != (RH, RW, C) or fill.device != result.device:
+            raise MdtileError(f"vae_assemble_sparse: fill {tuple(fill.shape)} on {fill.device} is not [{RH}, {RW}, {C}] on {result.device}")
+    table = (_VaeTile * max(1, len(tiles)))()
+    for k, (t, ib, ob) in enumerate(tiles):
+        _dev_tensor(t, f"tiles[{k}]", torch.float32)
+        if tuple(t.shape[:2]) != (N, C):
+            raise MdtileError(f"tiles[{k}] has shape {tuple(t.shape)}, the result {tuple(result.shape)}")
+        table[k] = _VaeTile(t.data_ptr(), t.shape[2], t.shape[3], (c_int * 4)(*ib), (c_int * 4)(*ob))
+    flat = [int(v) for b in fill_boxes for v in b]
+    if len(flat) != 4 * len(fill_boxes):
+        raise MdtileError("vae_assemble_sparse: every fill box is (x1, x2, y1, y2)")
+    boxes = (c_int * max(1, len(flat)))(*flat)
+    _check(lib().mdtile_vae_assemble_sparse(table, len(tiles), boxes, len(fill_boxes), _p(fill), N, C, _p(result), RH, RW, _stream()),
+           "mdtile_vae_assemble_sparse")
 
 
 def enable_peer_access(device: int, peer: int) -> None:

@@ -38,6 +38,14 @@ def preload(parser):
              "of the padding that is otherwise decoded and thrown away, instead of pasting the tiles edge to edge. Every decoded tile is kept "
              "until the image is assembled. Default: not set, edge to edge.")
     parser.add_argument(
+        "--mdtile-vae-inpaint-skip", action="store_true",
+        help="img2img inpainting with Tiled VAE's fast decoder: decode only the tiles that the job's overlay mask touches and fill the others "
+             "from the init image. Relies on the host pasting the original image back over the result wherever the overlay mask is zero, as "
+             "the webui does for an inpaint job; a script that composites the decoded image itself (soft inpainting) is outside that premise. "
+             "Not applied (one line says why) with the slow decoder, --mdtile-vae-seam-blend, a process per GPU, wrap-around, 'only masked' "
+             "inpainting, the host's colour correction, a job without overlay mask or overlay images, or a mask of another size than the "
+             "decoded image. Default: off, every tile is decoded.")
+    parser.add_argument(
         "--mdtile-inpaint-skip", action="store_true",
         help="img2img inpainting with Tiled Diffusion (MultiDiffusion, Mixture of Diffusers): run the model only on the grid tiles that the job's "
              "latent mask touches. Relies on the host replacing the model output by the init latent wherever the mask is zero, as the webui's "

@@ -234,6 +234,48 @@ def _cmd_line_seam_blend() -> Optional[int]:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# decode only the tiles an inpaint mask touches (preload.py: --mdtile-vae-inpaint-skip)
+# ---------------------------------------------------------------------------------------------------------------------
+def _cmd_line_vae_inpaint_skip() -> bool:
+    """--mdtile-vae-inpaint-skip (preload.py); False on a host that never heard of the option."""
+    import modules.shared as shared
+    return bool(getattr(shared.cmd_opts, "mdtile_vae_inpaint_skip", False))
+
+
+def inpaint_skip_refusal(p, is_decoder: bool, all_frozen: bool, seam_set: bool, world: int, wrap: bool, size) -> Tuple[Optional[str], object]:
+    """The decision list of --mdtile-vae-inpaint-skip up to the mask itself: (the first reason the skip does not apply, None), or
+    (None, the job's overlay mask as an "L" image of `size` = (8 w, 8 h) of this call's latent).  Every attribute of the host's processing
+    object is read with getattr: what they mean is the webui's StableDiffusionProcessingImg2Img as remembered, not something this
+    extension can verify.  Pure apart from the mask's conversion."""
+    if not is_decoder:
+        return "this is the encoder (the init image is encoded in full)", None
+    if not all_frozen:
+        return "not every norm is frozen (the fast decoder is off, or its estimator fell back to slow mode)", None
+    if seam_set:
+        return "a seam blend is set (--mdtile-vae-seam-blend): a band next to a skipped tile would need that tile's decoded padding", None
+    if world > 1:
+        return "the decode is sharded over processes (one per GPU)", None
+    mask = getattr(p, "mask_for_overlay", None)
+    if mask is None:
+        return "the job has no overlay mask (mask_for_overlay): not an inpaint job", None
+    if not getattr(p, "overlay_images", None):
+        return "the job has no overlay images: nothing says that the host pastes the original back", None
+    if getattr(p, "inpaint_full_res", False):
+        return "inpaint area is 'only masked' (inpaint_full_res): the overlay mask belongs to the whole picture, the decode to the crop", None
+    if getattr(p, "color_corrections", None):
+        return "the host's colour correction is on: it reads the whole decoded image", None
+    if wrap:
+        return "wrap-around is on (--mdtile-wrap-x / --mdtile-wrap-y): the decode runs on a padded canvas", None
+    try:
+        mask = mask if getattr(mask, "mode", None) == "L" else mask.convert("L")
+        mask_size = tuple(mask.size)
+    except Exception as e:     # not an image at all
+        return f"the overlay mask cannot be read as an image ({type(e).__name__})", None
+    if mask_size != tuple(size):
+        return f"the overlay mask is {mask_size[0]} x {mask_size[1]} px, the decoded image {size[0]} x {size[1]}", None
+    return None, mask
+
+
 class VAEHook:
 
     def __init__(self, net, tile_size, is_decoder: bool, fast_decoder: bool, fast_encoder: bool, color_fix: bool,
@@ -267,6 +309,12 @@ class VAEHook:
         # padding crop_valid_region throws away (mdtile_vae_assemble_blend).  Every finished tile then lives until the assembly (at 8K /
         # tile 256 about 16 x 59 MB).  0: upstream's edge-to-edge paste, nothing below changes.
         self.seam_blend: int = 0
+        # decoder only (preload.py: --mdtile-vae-inpaint-skip): the job's processing object.  vae_tile_forward then decodes only the
+        # tiles whose out box the job's overlay mask touches and fills the others from the init image (_inpaint_skip: when, and when
+        # not).  None: every tile is decoded, nothing below changes.  Script.postprocess drops the reference.
+        self.inpaint_job = None
+        self.last_tiles_run: Optional[int] = None           # tiles decoded in the last call (all of them without the skip)
+        self._skip_said = False                             # the "not applied" line is printed once per job (a hook lives one job)
 
     def __call__(self, x):
         original_device = next(self.net.parameters()).device
@@ -746,6 +794,50 @@ class VAEHook:
                 return
             forward = not forward
 
+    # ---- decode only the tiles an inpaint mask touches ------------------------------------------------------------------------------
+    def _inpaint_skip(self, z: Tensor, out_bboxes, all_frozen: bool, seam_set: bool):
+        """--mdtile-vae-inpaint-skip for this call: (one flag per tile, the fill image's bytes on z's device or None), or None when the skip
+        does not apply -- the full decode then runs, bit for bit as without the option, and ONE line per job names the first reason
+        (inpaint_skip_refusal's list, then: every tile active, or none).
+        The premise is the host's overlay paste: for an inpaint job the webui pastes the original image back over the result wherever the
+        overlay mask is zero, so what the decoder writes there is thrown away.  A tile whose out box holds no non-zero mask byte is not
+        decoded; its box is filled from the job's init image -- p.init_images[0] when there is exactly one, "RGB" (or "L", converted) and of
+        the decoded size; its bytes on the device are reused when p.init_image_bytes_md holds that very image -- as byte / 127.5 - 1, or
+        with 0.0 when there is no such image.  The fill exists so that previews, the NaN test and --mdtile-color-fix see a sane image; a
+        host that rounds (x + 1) / 2 * 255 gets every byte back exactly, the webui's truncating astype(uint8) gets 63 of the 256 values one
+        level low, which the overlay hides.  An interrupt that leaves fewer tiles finished than are active pastes what finished and fills
+        the rest (_collect)."""
+        p = self.inpaint_job
+        N, _, h, w = z.shape
+        size = (8 * w, 8 * h)
+        why, mask = inpaint_skip_refusal(p, self.is_decoder, all_frozen, seam_set, self.shard[1], _cmd_line_wrap_x() or _cmd_line_wrap_y(), size)
+        active = None
+        if why is None:
+            from tile_utils.utils import image_to_device
+            active = self.engine.mask_activity_u8(image_to_device(mask).to(z.device).contiguous(), out_bboxes)
+            n_active = sum(1 for a in active if a)
+            if n_active == len(active):
+                why = f"the mask touches all {len(active)} tiles"
+            elif n_active == 0:
+                why = "the mask touches no tile"
+        if why is not None:
+            if not self._skip_said:
+                self._skip_said = True
+                print(f"[Tiled VAE]: --mdtile-vae-inpaint-skip not applied: {why}")
+            return None
+        fill = None
+        images = getattr(p, "init_images", None)
+        if isinstance(images, (list, tuple)) and len(images) == 1 and getattr(images[0], "mode", None) in ("RGB", "L") \
+                and tuple(getattr(images[0], "size", ())) == size:
+            from tile_utils.utils import image_to_device
+            kept = getattr(p, "init_image_bytes_md", None)
+            if images[0].mode == "RGB" and kept is not None and kept[0] is images[0] and tuple(kept[1].shape) == (size[1], size[0], 3):
+                fill = kept[1]
+            else:
+                fill = image_to_device(images[0] if images[0].mode == "RGB" else images[0].convert("RGB"))
+            fill = fill.to(z.device).contiguous()
+        return active, fill
+
     @torch.no_grad()
     def vae_tile_forward(self, z: Tensor) -> Tensor:
         t0 = time()
@@ -792,7 +884,17 @@ class VAEHook:
         # of the frozen statistics); the tiles dealt by area (mdtile/sharding.py: deal_tiles), the same list on every rank
         from mdtile import sharding
         devs = [torch.device("cuda", i) for i in slots] if slots else [dev]
-        owner = sharding.deal_tiles(in_bboxes, len(devs) if slots else world)
+        # (the decision needs the estimator's outcome, and the masks the host computes after Script.process: made here, once per call)
+        skip = self._inpaint_skip(z, out_bboxes, all_frozen, seam is not None) if self.inpaint_job is not None else None
+        if skip is None:
+            owner = sharding.deal_tiles(in_bboxes, len(devs) if slots else world)
+        else:
+            # only the active tiles are gathered, dealt and swept; a skipped tile belongs to no lane (-1)
+            run = [i for i, a in enumerate(skip[0]) if a]
+            owner = [-1] * len(in_bboxes)
+            for i, o in zip(run, sharding.deal_tiles([in_bboxes[i] for i in run], len(devs))):
+                owner[i] = o
+            print(f"[Tiled VAE]: decoding {len(run)} of {len(in_bboxes)} tiles (inpaint mask)")
         self.last_tile_slots = list(owner) if world == 1 else None
         lanes = []
         for k, d in enumerate(devs):
@@ -801,10 +903,11 @@ class VAEHook:
                 lane_frozen = frozen if k == 0 or frozen is None else [(v.to(d), m.to(d)) for v, m in frozen]
                 mine = [i for i, o in enumerate(owner) if o == (k if slots else rank)]
                 lanes.append(VAEHook._Lane(self, z if k == 0 else z.to(d), in_bboxes, out_bboxes, mine, lane_steps, lane_frozen,
-                                           keep_tiles=bool(slots) or seam is not None))
+                                           keep_tiles=bool(slots) or seam is not None or skip is not None))
                 lanes[-1].seam = seam
                 # every norm frozen: the hand-over sweep; else the lockstep sweep, the statistics of the norms behind the frozen ones pooled
                 lanes[-1].route = self._route(lane_steps, all_frozen, () if all_frozen else range(len(frozen or ()), n_norm))
+        self.last_tiles_run = sum(len(lane.mine) for lane in lanes)
         if all_frozen:
             sweeps = [(lane, self._sweep_frozen(lane)) for lane in lanes]
             while sweeps:                                # one chunk of every lane per round: no device waits while another's list is issued
@@ -816,12 +919,15 @@ class VAEHook:
                 sweeps = still
         else:
             self._sweep_lockstep(lanes)
-        return self._collect(lanes, owner, dtype, t0)
+        return self._collect(lanes, owner, dtype, t0, None if skip is None else skip[1], skip is not None)
 
-    def _collect(self, lanes: List["VAEHook._Lane"], owner: List[int], dtype, t0) -> Tensor:
+    def _collect(self, lanes: List["VAEHook._Lane"], owner: List[int], dtype, t0, fill=None, sparse: bool = False) -> Tensor:
         """The result on lane 0's device: the tiles kept by several lanes read into one image (mdtile_vae_assemble, peer reads, after lane
         0's stream has waited for the other devices' -- events, no host synchronize), the NaN test of the image (upstream :633-634), the
-        gather of the other ranks' rectangles, upstream's interrupt results (:644-650); one host synchronize at the end."""
+        gather of the other ranks' rectangles, upstream's interrupt results (:644-650); one host synchronize at the end.
+        sparse (the inpaint skip, _inpaint_skip): the kept tiles are the active ones only; mdtile_vae_assemble_sparse pastes them and fills
+        every other out box from `fill` (the init image's bytes on lane 0's device, or None: 0.0).  After an interrupt the tiles that
+        finished are pasted and the rest filled, active or not."""
         from mdtile import sharding
         z, dev, result = lanes[0].z, lanes[0].device, lanes[0].result
         rank, world = self.shard
@@ -842,6 +948,12 @@ class VAEHook:
                 kept.sort(key=lambda t: (t[2][2], t[2][0]))
                 result = torch.empty(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
                 self.engine.vae_assemble_blend(kept, seam[1], seam[2], result, seam[0], self.is_decoder)
+            elif kept and sparse:
+                # the tiles that were decoded (after an interrupt: those that finished), every other out box filled (sparse: the inpaint skip)
+                done = {tuple(ob) for _, _, ob in kept}
+                result = torch.empty(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
+                self.engine.vae_assemble_sparse(kept, [ob for ob in lanes[0].out_bboxes if tuple(ob) not in done],
+                                                fill if fill is not None and fill.shape[-1] == result.shape[1] else None, result)
             elif kept:
                 result = torch.zeros(self._out_shape(z, kept[0][0].shape[1]), device=dev, dtype=torch.float32)
                 self.engine.vae_assemble(kept, result, self.is_decoder)
@@ -923,6 +1035,7 @@ class Script(scripts.Script):
                 for net in (decoder, getattr(vae, "encoder", None)):
                     if net is not None and isinstance(net.forward, VAEHook):
                         net.forward.net = None
+                        net.forward.inpaint_job = None
                         net.forward = net.original_forward
             self.hooked = False
             self._restore_precision()
@@ -948,6 +1061,9 @@ class Script(scripts.Script):
         if seam_px is not None:                 # the decoder only: the encoder's 4 latent px of padding leave no ramp worth having
             decoder.forward.seam_blend = seam_px
             p.extra_generation_params["Tiled VAE seam blend"] = seam_px
+        if _cmd_line_vae_inpaint_skip():        # the decoder only; nothing of the job is read here (the host computes its masks in p.init())
+            decoder.forward.inpaint_job = p
+            p.extra_generation_params["Tiled VAE inpaint skip"] = True
         encoder = vae.encoder
         if not hasattr(encoder, "original_forward"):
             encoder.original_forward = encoder.forward
@@ -963,4 +1079,5 @@ class Script(scripts.Script):
         for net in (vae.decoder, getattr(vae, "encoder", None)):
             if net is not None and isinstance(net.forward, VAEHook):
                 net.forward.net = None
+                net.forward.inpaint_job = None
                 net.forward = net.original_forward

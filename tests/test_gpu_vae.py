@@ -203,9 +203,10 @@ def test_attention_vs_oracle(plugin, cuda, B, C, T, exact):
 @pytest.mark.parametrize("C,T,spike", [(128, 300, 4.0), (128, 300, 1.0), (512, 700, 2.5), (512, 700, 0.6), (256, 1500, 3.0)])
 def test_attention_online_softmax_rescale_branch(plugin, cuda, exact, C, T, spike):
     """Force the running-max update late in the key sequence (a spike in the last key block) -- bounded random data alone
-    never exercises a wrong rescale.  The split-bf16 kernel takes a key block's exponentials against the maximum as of the PREVIOUS
-    block: the large spikes (> 2^60 over the reference in the log2 domain) go through its redo path in a late block, the small ones
-    through the deferred rescale."""
+    never exercises a wrong rescale.  Both kernels take a key block's exponentials against the running maximum INCLUDING that block
+    (m_new = max(m_run, m_blk)) and rescale acc_o and l_run by alpha = exp(m_run - m_new) in the same block; the split-bf16 kernel skips
+    the multiply of acc_o for a wave whose queries all have alpha == 1.  A spike in a late block gives alpha << 1 there (0 for the
+    large spikes: everything accumulated before is dropped), and the blocks behind T // 2 run with alpha == 1 again."""
     E = plugin.engine
     torch.manual_seed(0)
     B = 1

@@ -272,6 +272,53 @@ int mdtile_plan_active(const mdtile_plan* plan, int* ids);
 int mdtile_blend_sparse(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                         const void* d_fill, mdtile_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * The jittered grid on a plain (bounded) canvas: a new tile grid every sampler step without a plan, a table or a map.  Nothing
+ * upstream corresponds to it.  The grid of a step is a pure function of the integers in mdtile_lattice; the kernels take them by value.
+ *
+ * Per axis (x shown; y likewise with tile_h, h, sy).  Tile and overlap are clamped as mdtile_plan_create(clamp = 1) does; stride st = tw - ov.
+ *   tw >= w: ONE tile at 0, the axis does not move, its shift is ignored (stored as 0).  Otherwise, for a shift s in [1, st]:
+ *     u_k  = s - st + k st,  k = 0 .. K        the lattice origins, u_0 <= 0;   K = max(0, ceil((w - tw - (s - st)) / st)): the first k with u_k + tw >= w
+ *     x'_k = min(max(u_k, 0), w - tw)          the box the model is run on: pushed inside the canvas, full size; strictly increasing in k
+ *   s = st is the lattice at rest (u_0 = 0).  Tile k COVERS x iff u_k <= x < u_k + tw: a tile is evaluated at its pushed-in box but contributes
+ *   only where its lattice box lies, so every tile border is at some u_k or u_k + tw and moves with s.  Every pixel is covered, by the contiguous
+ *   range max(0, floor((x - tw - (s - st)) / st) + 1) .. min(K, floor((x - (s - st)) / st)), and 0 <= x - x'_k < tw for each covering tile.
+ * Tiles are numbered row-major, y outer: t = r cols + c;  num_batches = ceil(T / tile_bs), tile_bs := ceil(T / num_batches).  T may differ by one
+ * column and one row between two shifts.
+ *
+ * mdtile_lattice: host integers only; it owns nothing and is not destroyed.  Fill it with mdtile_lattice_make (works without a GPU); the calls
+ *   below check it again (MDTILE_E_ARG for a struct that mdtile_lattice_make did not write).
+ * mdtile_lattice_bboxes:     xywh[4 * num_tiles] = the pushed-in boxes (x'_c, y'_r, tile_w, tile_h) in tile order.
+ * mdtile_lattice_weight_map: d_weights[h * w] fp32 := wsum (WRITTEN, not added);  wsum[y, x] = sum of w_t over the covering tiles in ascending t, fp32
+ *   from +0.0;  d_tile_w == NULL: w_t = 1.0f (MultiDiffusion), else w_t = d_tile_w[y - v_r, x - u_c] read in LATTICE coordinates (v_r = lattice row
+ *   origin), so that the Gaussian tapers at the moving borders (Mixture of Diffusers).
+ * mdtile_gather_all_lattice: x_tile[ty, tx] = x_in[y'_r + ty, x'_c + tx], tile-major compact batches as mdtile_gather_all; one launch.
+ * mdtile_blend_lattice:      covering tiles in ascending t, fp32 from +0.0, no contraction, the tile's value read at the PUSHED-IN coordinates
+ *   (y - y'_r, x - x'_c):   MD  buf += v;  out = wsum > 1 ? buf / wsum : buf      MoD  buf += v * (tile_w[y - v_r, x - u_c] * (1.0f / wsum))  (IEEE
+ *   division, as mdtile_reciprocal).  Half I/O: fp32 arithmetic on the dtype-rounded inputs, rounded once.  args->d_weights and args->d_rescale must be
+ *   NULL (the kernel forms the weight sum itself), d_tile_w is required for MoD, flags and the row band must be 0; there are no regions.
+ *   At rest on a canvas with (w - tw) % st == 0 and (h - th) % st == 0 the lattice is the plain plan, and all three calls equal
+ *   mdtile_weight_map_add_grid (on zeros) / mdtile_gather_all / mdtile_blend (with the plan's own maps) on it bit for bit.
+ * REFUSED (MDTILE_E_ARG, the text names the reason, nothing is written): a shift outside [1, stride] on a moving axis; num_batches != the
+ *   lattice's or > MDTILE_MAX_BATCHES; non-NULL d_weights / d_rescale; flags or a row band; bad shapes (canvas, tile, N, C, dtype, null pointers,
+ *   overlap == clamped tile, more than 65535 tiles in one gather).
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct mdtile_lattice {
+    int w, h;                    /* canvas (latent px) */
+    int tile_w, tile_h, overlap; /* clamped */
+    int stride_x, stride_y;      /* tile - overlap (meaningful on a moving axis) */
+    int sx, sy;                  /* the shift, in [1, stride] on a moving axis; 0 on an axis that does not move */
+    int cols, rows, num_tiles;
+    int num_batches, tile_bs;
+} mdtile_lattice;
+int mdtile_lattice_make(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int sx, int sy, mdtile_lattice* lat);
+int mdtile_lattice_bboxes(const mdtile_lattice* lat, int* xywh);
+int mdtile_lattice_weight_map(const mdtile_lattice* lat, const float* d_tile_w, float* d_weights, mdtile_stream_t stream);
+int mdtile_gather_all_lattice(const mdtile_lattice* lat, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs, int num_batches,
+                              mdtile_stream_t stream);
+int mdtile_blend_lattice(const mdtile_lattice* lat, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                         mdtile_stream_t stream);
+
 /* Per-region initial noise (scripts/tilediffusion.py:486-529, create_random_tensors_hijack): d_noise [N,C,H,W] fp32 is the job's
  * noise, updated in place.  regions[i].out = the region's own noise [1,C,h,w] fp32 (drawn by the host with the region's CPU
  * seed, shared by all N samples), .mode = MDTILE_REGION_BG / _FG, .weight unused.  Per layer: sum + hit count over the regions

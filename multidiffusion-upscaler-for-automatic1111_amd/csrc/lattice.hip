@@ -1,0 +1,427 @@
+// The jittered tile grid on a plain (bounded) canvas: mdtile_lattice_* , mdtile_gather_all_lattice, mdtile_blend_lattice.
+//
+// Per axis (x shown; y likewise with th, H, sy): stride st = tw - ov, shift s in [1, st], off = s - st in (-st, 0].
+//     u_k  = off + k st,  k = 0 .. K          the LATTICE origins (u_0 <= 0);  K = max(0, ceil((W - tw - off) / st)) = first k with u_k + tw >= W
+//     x'_k = min(max(u_k, 0), W - tw)         the PUSHED-IN box the model is run on: inside the canvas, full size
+// An axis whose tile is as large as the canvas has one tile at 0 and does not move (here: stride 1, off 0, K 0).
+// A tile is EVALUATED at its pushed-in box but CONTRIBUTES only where its lattice box lies: tile k covers x iff u_k <= x < u_k + tw, so every tile
+// border sits at some u_k or u_k + tw and moves with s.  The covering tiles of x are the contiguous range
+//     max(0, floor((x - tw - off) / st) + 1) .. min(K, floor((x - off) / st))
+// (a FLOOR division: the numerators are negative near the left edge), and 0 <= x - x'_k < tw for each of them.
+//
+// Nothing here has a table or a map: the grid of a step is the handful of integers of mdtile_lattice, the kernels take them by value and derive
+// the covering tiles AND the weight sum of a pixel from them.  So a new grid every sampler step costs no allocation, no upload and no extra launch.
+//
+// Arithmetic (what the sequential `+=` loop over the tile list gives, bit for bit; -ffp-contract=off):
+//     wsum[y, x] = sum of w_t over the covering tiles in ascending t = r cols + c (rows outer), fp32 from +0.0;  MultiDiffusion w_t = 1.0f, Mixture of
+//                  Diffusers w_t = tile_w[y - v_r, x - u_c], read in LATTICE coordinates (the Gaussian tapers at the moving borders)
+//     MD : buf += v;                                          out = wsum > 1 ? buf / wsum : buf
+//     MoD: buf += v * (tile_w[y - v_r, x - u_c] * (1.0f / wsum))
+// with v the tile's value at the PUSHED-IN coordinates (y - y'_r, x - x'_c).  All fp32 arithmetic is written on scalars.
+#include "launchers.h"
+
+using namespace mdt;
+
+namespace {
+
+// most blocks along grid.y: kernels walk the planes (n * C + c) from blockIdx.y in steps of gridDim.y, so N * C may pass it
+constexpr int kPlaneBlocks = 64;
+
+// one axis as the kernels see it
+struct LatAxis {
+    int extent, tile;
+    int stride, off, K;       // off = s - stride in (-stride, 0]; an axis that does not move: stride 1, off 0, K 0
+};
+
+struct LatticeParams {
+    LatAxis ax, ay;
+    int cols, tile_bs, N, C;
+};
+struct LatticeGatherParams : LatticeParams {
+    const void* x_in;
+    void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(LatticeGatherParams) <= 4096, "kernel argument block must stay under 4 KiB");
+struct LatticeBlendParams : LatticeParams {
+    const float* tile_w;      // Mixture of Diffusers: the [th, tw] Gaussian; null for MultiDiffusion
+    void* out;
+    const void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(LatticeBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+
+// floor(a / b), b > 0 (C's `/` truncates towards zero: wrong for the negative numerators left of the first stride)
+__host__ __device__ __forceinline__ int floor_div(int a, int b) {
+    const int q = a / b;
+    return a - q * b < 0 ? q - 1 : q;
+}
+__host__ __device__ __forceinline__ int lat_origin(const LatAxis& a, int k) { return a.off + k * a.stride; }
+__host__ __device__ __forceinline__ int lat_pushed(const LatAxis& a, int k) {
+    const int u = lat_origin(a, k), last = a.extent - a.tile;
+    return u < 0 ? 0 : u > last ? last : u;
+}
+// the tiles whose lattice box meets the coordinates [p_lo, p_hi] (p_lo <= p_hi, both on the canvas): lo .. hi, never empty
+struct Cover { int lo, hi; };
+__device__ __forceinline__ Cover lat_cover(const LatAxis& a, int p_lo, int p_hi) {
+    Cover c;
+    c.lo = floor_div(p_lo - a.tile - a.off, a.stride) + 1;
+    if (c.lo < 0) c.lo = 0;
+    c.hi = floor_div(p_hi - a.off, a.stride);
+    if (c.hi > a.K) c.hi = a.K;
+    return c;
+}
+
+// wsum of pixel (y, x): the candidates are the tile rows `rows` (all cover y) and the tile columns `cand` (a superset of those that cover x:
+// the columns of x's quad); ascending tile index, fp32 from +0.0
+template <bool MOD>
+__device__ __forceinline__ float lat_wsum(const LatticeParams& P, int y, int x, Cover rows, Cover cand, const float* __restrict__ tile_w) {
+    float s = 0.0f;
+    for (int r = rows.lo; r <= rows.hi; ++r) {
+        const int wy = y - lat_origin(P.ay, r);
+        for (int c = cand.lo; c <= cand.hi; ++c) {
+            const int d = x - lat_origin(P.ax, c);
+            if (d < 0 || d >= P.ax.tile) continue;
+            if (MOD) s += tile_w[wy * P.ax.tile + d];
+            else s += 1.0f;
+        }
+    }
+    return s;
+}
+
+// weights[y, x] = wsum (written, not added)
+__global__ __launch_bounds__(256) void k_lattice_weight(const LatticeParams P, const float* __restrict__ tile_w, float* __restrict__ weights) {
+    const int W = P.ax.extent, H = P.ay.extent;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= W * H) return;
+    const int y = idx / W, x = idx - y * W;
+    const Cover rows = lat_cover(P.ay, y, y), cols = lat_cover(P.ax, x, x);
+    weights[idx] = tile_w ? lat_wsum<true>(P, y, x, rows, cols, tile_w) : lat_wsum<false>(P, y, x, rows, cols, tile_w);
+}
+
+// the storage type as an integer of its size, and 4 of them at an element-aligned address (one load / store instruction: gfx950 runs in
+// unaligned-access mode)
+template <typename T> struct RawOf { using type = unsigned short; };
+template <> struct RawOf<float> { using type = unsigned int; };
+template <typename R> struct __attribute__((packed, aligned(sizeof(R)))) raw4_u { R v[4]; };
+
+template <typename T> __device__ __forceinline__ typename RawOf<T>::type raw_bits(float v);
+template <> __device__ __forceinline__ unsigned int raw_bits<float>(float v) { return __float_as_uint(v); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__half>(float v) { return __half_as_ushort(__float2half_rn(v)); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__hip_bfloat16>(float v) {
+    const __hip_bfloat16 h = __float2bfloat16(v);
+    unsigned short u;
+    __builtin_memcpy(&u, &h, sizeof(u));
+    return u;
+}
+
+// tile t = r cols + c, tile-major compact batches: x_tile[(t mod tile_bs) N + n, ch, ty, tx] of batch t / tile_bs = x_in[n, ch, y'_r + ty, x'_c + tx].
+// A pushed-in box lies on the canvas, so the copy has no edge case but the last quad of a tile row; the elements move as integers.
+// grid: x = quads over (th rows x ceil(tw / 4)), y = planes (walked in steps of gridDim.y), z = tile
+template <typename T>
+__global__ __launch_bounds__(256) void k_lattice_gather(const LatticeGatherParams P) {
+    using R = typename RawOf<T>::type;
+    const int W = P.ax.extent, H = P.ay.extent, tw = P.ax.tile, th = P.ay.tile;
+    const int tw4 = (tw + 3) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= tw4 * th) return;
+    const int ty = idx / tw4, tx0 = (idx - ty * tw4) << 2;
+    const int t = blockIdx.z;
+    const int r = t / P.cols, c = t - r * P.cols;
+    const int sy = lat_pushed(P.ay, r) + ty, sx = lat_pushed(P.ax, c) + tx0;      // sy < H; sx + nvalid <= W
+    const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+    const int planes = P.N * P.C;
+    const int nvalid = tw - tx0 < 4 ? tw - tx0 : 4;
+    for (int plane = blockIdx.y; plane < planes; plane += gridDim.y) {
+        const R* src = reinterpret_cast<const R*>(P.x_in) + ((size_t)plane * H + sy) * W + sx;
+        R* dst = reinterpret_cast<R*>(P.batch[b]) + (((size_t)i * planes + plane) * th + ty) * tw + tx0;
+        if (nvalid == 4) {
+            *reinterpret_cast<raw4_u<R>*>(dst) = *reinterpret_cast<const raw4_u<R>*>(src);
+        } else {
+            for (int j = 0; j < nvalid; ++j) dst[j] = src[j];
+        }
+    }
+}
+
+// One thread owns one aligned quad (4 consecutive canvas columns of one row) for PP planes at a time, and walks the planes from blockIdx.y * PP
+// in steps of gridDim.y * PP.  The tile rows that cover y and the tile columns that cover ANY pixel of the quad come from the lattice integers;
+// the weight sums of the four pixels are formed once, in front of the plane walk.  Per candidate tile the quad is either one whole piece of the
+// tile's CONTRIBUTING row segment (lattice-relative columns d0 .. d0 + 3 all in [0, tw)) -- one element-aligned vector load per plane (load4:
+// 16 bytes of fp32, 8 of a 16-bit type, at any alignment) -- or it is cut by a lattice border / the canvas edge: per-element loads of the covered
+// pixels only.  The part of a pushed-in tile outside its lattice box is never read.
+template <typename T, int METHOD, int PP>
+__global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams P) {
+    using R = typename RawOf<T>::type;
+    const int W = P.ax.extent, H = P.ay.extent, tw = P.ax.tile, th = P.ay.tile;
+    const int W4 = (W + 3) >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= W4 * H) return;
+    const int y = idx / W4, x0 = (idx - y * W4) << 2;
+    const int nvalid = W - x0 < 4 ? W - x0 : 4;
+    const int planes = P.N * P.C;                              // the host guarantees planes % PP == 0
+    const size_t tile_elems = (size_t)th * tw;
+
+    const Cover rows = lat_cover(P.ay, y, y), cand = lat_cover(P.ax, x0, x0 + nvalid - 1);
+    float wsum[4] = {0.f, 0.f, 0.f, 0.f}, rinv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j >= nvalid) continue;
+        wsum[j] = lat_wsum<METHOD == MDTILE_METHOD_MOD>(P, y, x0 + j, rows, cand, P.tile_w);
+        if (METHOD == MDTILE_METHOD_MOD) rinv[j] = 1.0f / wsum[j];      // IEEE division, as mdtile_reciprocal
+    }
+
+    for (int p0 = blockIdx.y * PP; p0 < planes; p0 += gridDim.y * PP) {
+        float acc[PP][4];
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
+
+        for (int r = rows.lo; r <= rows.hi; ++r) {             // ascending tile index: rows outer, columns inner
+            const int wy = y - lat_origin(P.ay, r);            // row inside the lattice box (and inside the tile-weight map)
+            const int ty = y - lat_pushed(P.ay, r);            // row inside the pushed-in box: where the tile's value lies
+            for (int c = cand.lo; c <= cand.hi; ++c) {
+                const int d0 = x0 - lat_origin(P.ax, c);       // lattice-relative column of the quad's first pixel
+                const int tx = x0 - lat_pushed(P.ax, c);       // pushed-in-relative column of it
+                const int t = r * P.cols + c;
+                const int b = t / P.tile_bs, i = t - b * P.tile_bs;
+                const T* row = reinterpret_cast<const T*>(P.batch[b]) + ((size_t)i * planes + p0) * tile_elems + (size_t)ty * tw;
+                // the four values are consecutive in memory (then 0 <= tx and tx + 3 < tw): one load per plane at whatever alignment the shift and
+                // the batch pointer leave -- an odd shift puts EVERY tile row off its 16-byte boundary, so this is the common case, not the edge
+                if (nvalid == 4 && d0 >= 0 && d0 + 3 < tw) {
+                    float wg[4] = {1.f, 1.f, 1.f, 1.f};
+                    if (METHOD == MDTILE_METHOD_MOD) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) wg[j] = P.tile_w[wy * tw + d0 + j] * rinv[j];
+                    }
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) {
+                        float v[4];
+                        load4<T>(row + (size_t)pp * tile_elems + tx, v);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v[j] * wg[j];
+                            else acc[pp][j] += v[j];
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int dj = d0 + j;
+                        if (j >= nvalid || dj < 0 || dj >= tw) continue;       // outside the lattice box: the tile does not contribute
+                        float wgt = 1.0f;
+                        if (METHOD == MDTILE_METHOD_MOD) wgt = P.tile_w[wy * tw + dj] * rinv[j];
+#pragma unroll
+                        for (int pp = 0; pp < PP; ++pp) {
+                            const float v = to_f32<T>(row[(size_t)pp * tile_elems + tx + j]);
+                            if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
+                            else acc[pp][j] += v;
+                        }
+                    }
+                }
+            }
+        }
+
+        if (METHOD == MDTILE_METHOD_MD) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (wsum[j] > 1.0f) {
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / wsum[j];
+                }
+            }
+        }
+
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp) {
+            R* dst = reinterpret_cast<R*>(P.out) + ((size_t)(p0 + pp) * H + y) * W + x0;
+            if (nvalid == 4) {
+                raw4_u<R> o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o.v[j] = raw_bits<T>(acc[pp][j]);
+                *reinterpret_cast<raw4_u<R>*>(dst) = o;
+            } else {
+                for (int j = 0; j < nvalid; ++j) dst[j] = raw_bits<T>(acc[pp][j]);
+            }
+        }
+    }
+}
+
+// planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as the other blends are sized
+int planes_per_thread(int W, int H, int planes) {
+    const long long work = (long long)H * ((W + 3) / 4) * planes;
+    if (planes % 4 == 0 && work / 4 >= 131072) return 4;
+    return planes % 2 == 0 && work / 2 >= 131072 ? 2 : 1;
+}
+
+using LatticeBlendKernel = void (*)(const LatticeBlendParams);
+template <typename T, int PP>
+LatticeBlendKernel lattice_blend_kernel(int method) {
+    return method == MDTILE_METHOD_MD ? k_lattice_blend<T, MDTILE_METHOD_MD, PP> : k_lattice_blend<T, MDTILE_METHOD_MOD, PP>;
+}
+
+template <typename T>
+void launch_lattice_blend(const LatticeBlendParams& P, int method, hipStream_t s) {
+    const int W = P.ax.extent, H = P.ay.extent, planes = P.N * P.C;
+    const int pp = planes_per_thread(W, H, planes);
+    const LatticeBlendKernel k = pp == 4 ? lattice_blend_kernel<T, 4>(method) : pp == 2 ? lattice_blend_kernel<T, 2>(method) : lattice_blend_kernel<T, 1>(method);
+    const int gy = planes / pp < kPlaneBlocks ? planes / pp : kPlaneBlocks;
+    hipLaunchKernelGGL(k, dim3(cdiv((long long)H * ((W + 3) / 4), 256), gy), dim3(256), 0, s, P);
+}
+
+// ---- host integers ---------------------------------------------------------------------------------------------------------------
+// tiles of a moving axis at shift s: K + 1, K = ceil((extent - tile - (s - stride)) / stride)  (the numerator is positive: tile < extent, s <= stride)
+int axis_tiles(int extent, int tile, int stride, int s) { return (extent - tile - (s - stride) + stride - 1) / stride + 1; }
+
+LatAxis kernel_axis(int extent, int tile, int stride, int s, int count) {
+    LatAxis a;
+    a.extent = extent; a.tile = tile;
+    if (tile >= extent) { a.stride = 1; a.off = 0; a.K = 0; }
+    else { a.stride = stride; a.off = s - stride; a.K = count - 1; }
+    return a;
+}
+
+// Is *lat what mdtile_lattice_make writes?  The struct is the caller's memory: every field the kernels' addresses depend on is checked again.
+int lattice_check(const char* fn, const mdtile_lattice* l) {
+    MDT_CHECK_ARG(l, "%s: null lattice", fn);
+    MDT_CHECK_ARG(l->w > 0 && l->h > 0 && l->w <= 65535 && l->h <= 65535 && l->tile_w > 0 && l->tile_h > 0 && l->tile_w <= l->w && l->tile_h <= l->h &&
+                      l->overlap >= 0 && l->tile_bs > 0,
+                  "%s: bad lattice: canvas %dx%d, tile %dx%d, overlap %d, tile_bs %d (not from mdtile_lattice_make)", fn, l->w, l->h, l->tile_w, l->tile_h,
+                  l->overlap, l->tile_bs);
+    const int extent[2] = {l->w, l->h}, tile[2] = {l->tile_w, l->tile_h}, stride[2] = {l->stride_x, l->stride_y}, s[2] = {l->sx, l->sy},
+              count[2] = {l->cols, l->rows};
+    for (int a = 0; a < 2; ++a) {
+        const char axis = a ? 'y' : 'x';
+        if (tile[a] >= extent[a]) {
+            MDT_CHECK_ARG(count[a] == 1, "%s: bad lattice: %d tiles along %c although the tile spans the canvas", fn, count[a], axis);
+            continue;
+        }
+        MDT_CHECK_ARG(stride[a] == tile[a] - l->overlap && stride[a] > 0, "%s: bad lattice: stride_%c = %d, tile - overlap = %d", fn, axis, stride[a],
+                      tile[a] - l->overlap);
+        MDT_CHECK_ARG(s[a] >= 1 && s[a] <= stride[a], "%s: shift s%c = %d outside [1, %d] (the stride) on an axis that moves", fn, axis, s[a], stride[a]);
+        MDT_CHECK_ARG(count[a] == axis_tiles(extent[a], tile[a], stride[a], s[a]), "%s: bad lattice: %d tiles along %c, the shift gives %d", fn, count[a], axis,
+                      axis_tiles(extent[a], tile[a], stride[a], s[a]));
+    }
+    MDT_CHECK_ARG(l->cols <= 32767 && l->rows <= 32767 && l->num_tiles == l->cols * l->rows, "%s: bad lattice: %d tiles for %d x %d", fn, l->num_tiles, l->cols,
+                  l->rows);
+    MDT_CHECK_ARG(l->num_batches == (l->num_tiles + l->tile_bs - 1) / l->tile_bs && l->num_batches > 0 &&
+                      l->tile_bs == (l->num_tiles + l->num_batches - 1) / l->num_batches,
+                  "%s: bad lattice: %d batches of %d for %d tiles", fn, l->num_batches, l->tile_bs, l->num_tiles);
+    return MDTILE_OK;
+}
+
+void fill_params(LatticeParams& P, const mdtile_lattice* l, int N, int C) {
+    P.ax = kernel_axis(l->w, l->tile_w, l->stride_x, l->sx, l->cols);
+    P.ay = kernel_axis(l->h, l->tile_h, l->stride_y, l->sy, l->rows);
+    P.cols = l->cols; P.tile_bs = l->tile_bs; P.N = N; P.C = C;
+}
+
+// what both calls with batches ask of their count
+int batches_check(const char* fn, const mdtile_lattice* l, int num_batches) {
+    MDT_CHECK_ARG(num_batches == l->num_batches, "%s: %d batches given, the lattice has %d", fn, num_batches, l->num_batches);
+    MDT_CHECK_ARG(num_batches <= MDTILE_MAX_BATCHES, "%s: %d batches > MDTILE_MAX_BATCHES=%d (the lattice has no packed form: raise the tile batch size)", fn,
+                  num_batches, MDTILE_MAX_BATCHES);
+    return MDTILE_OK;
+}
+
+}  // namespace
+
+extern "C" int mdtile_lattice_make(int w, int h, int tile_w, int tile_h, int overlap, int tile_bs, int sx, int sy, mdtile_lattice* lat) {
+    const char* fn = "mdtile_lattice_make";
+    MDT_CHECK_ARG(lat, "%s: null lattice", fn);
+    MDT_CHECK_ARG(w > 0 && h > 0 && tile_w > 0 && tile_h > 0 && tile_bs > 0 && w <= 65535 && h <= 65535, "%s: bad arguments w=%d h=%d tile=%dx%d bs=%d", fn, w, h,
+                  tile_w, tile_h, tile_bs);
+    // the clamp of mdtile_plan_create(clamp = 1)
+    const int tw = tile_w < w ? tile_w : w, th = tile_h < h ? tile_h : h;
+    const int mn = tile_w < tile_h ? tile_w : tile_h;     // requested, not clamped, sizes
+    int ov = overlap < mn - 4 ? overlap : mn - 4;
+    if (ov < 0) ov = 0;
+    MDT_CHECK_ARG(tw - ov != 0 && th - ov != 0, "%s: overlap %d equals the canvas-clamped tile %dx%d (mdtile_plan_create refuses it too)", fn, ov, tw, th);
+    mdtile_lattice l;
+    l.w = w; l.h = h; l.tile_w = tw; l.tile_h = th; l.overlap = ov;
+    l.stride_x = tw - ov; l.stride_y = th - ov;
+    const bool move_x = tw < w, move_y = th < h;          // a moving axis has tile == requested tile, so its stride is >= 4
+    MDT_CHECK_ARG(!move_x || (sx >= 1 && sx <= l.stride_x), "%s: shift sx = %d outside [1, %d] (the stride) on an axis that moves", fn, sx, l.stride_x);
+    MDT_CHECK_ARG(!move_y || (sy >= 1 && sy <= l.stride_y), "%s: shift sy = %d outside [1, %d] (the stride) on an axis that moves", fn, sy, l.stride_y);
+    l.sx = move_x ? sx : 0;
+    l.sy = move_y ? sy : 0;
+    l.cols = move_x ? axis_tiles(w, tw, l.stride_x, sx) : 1;
+    l.rows = move_y ? axis_tiles(h, th, l.stride_y, sy) : 1;
+    MDT_CHECK_ARG(l.cols <= 32767 && l.rows <= 32767, "%s: too many tiles (%d x %d)", fn, l.cols, l.rows);
+    l.num_tiles = l.cols * l.rows;
+    l.num_batches = (l.num_tiles + tile_bs - 1) / tile_bs;
+    l.tile_bs = (l.num_tiles + l.num_batches - 1) / l.num_batches;
+    *lat = l;
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_lattice_bboxes(const mdtile_lattice* lat, int* xywh) {
+    if (int rc = lattice_check("mdtile_lattice_bboxes", lat)) return rc;
+    MDT_CHECK_ARG(xywh, "mdtile_lattice_bboxes: null argument");
+    LatticeParams P;
+    fill_params(P, lat, 1, 1);
+    for (int r = 0; r < lat->rows; ++r)
+        for (int c = 0; c < lat->cols; ++c) {
+            int* o = xywh + 4 * (r * lat->cols + c);
+            o[0] = lat_pushed(P.ax, c); o[1] = lat_pushed(P.ay, r); o[2] = lat->tile_w; o[3] = lat->tile_h;
+        }
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_lattice_weight_map(const mdtile_lattice* lat, const float* d_tile_w, float* d_weights, mdtile_stream_t stream) {
+    if (int rc = lattice_check("mdtile_lattice_weight_map", lat)) return rc;
+    MDT_CHECK_ARG(d_weights, "mdtile_lattice_weight_map: null output");
+    LatticeParams P;
+    fill_params(P, lat, 1, 1);
+    hipLaunchKernelGGL(k_lattice_weight, dim3(cdiv((long long)lat->w * lat->h, 256)), dim3(256), 0, as_stream(stream), P, d_tile_w, d_weights);
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_gather_all_lattice(const mdtile_lattice* lat, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs, int num_batches,
+                                         mdtile_stream_t stream) {
+    const char* fn = "mdtile_gather_all_lattice";
+    if (int rc = lattice_check(fn, lat)) return rc;
+    MDT_CHECK_ARG(d_x_in && batch_ptrs, "%s: null argument", fn);
+    MDT_CHECK_ARG(N > 0 && C > 0 && N * C <= 65535, "%s: bad N=%d C=%d", fn, N, C);
+    MDT_CHECK_ARG(dtype >= 0 && dtype <= 2, "%s: bad dtype %d", fn, dtype);
+    if (int rc = batches_check(fn, lat, num_batches)) return rc;
+    MDT_CHECK_ARG(lat->num_tiles <= 65535, "%s: %d tiles in one launch (at most 65535)", fn, lat->num_tiles);
+    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_ptrs[b], "%s: null batch pointer %d", fn, b);
+    LatticeGatherParams P;
+    memset(&P, 0, sizeof(P));
+    fill_params(P, lat, N, C);
+    P.x_in = d_x_in;
+    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_ptrs[b];
+    const int planes = N * C;
+    dim3 grid(cdiv((long long)lat->tile_h * ((lat->tile_w + 3) / 4), 256), planes < kPlaneBlocks ? planes : kPlaneBlocks, lat->num_tiles), block(256);
+    with_dtype(dtype, [&](auto* tag) { hipLaunchKernelGGL((k_lattice_gather<std::remove_pointer_t<decltype(tag)>>), grid, block, 0, as_stream(stream), P); });
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_blend_lattice(const mdtile_lattice* lat, const mdtile_blend_args* a, const void* const* batch_out, int num_batches,
+                                    mdtile_stream_t stream) {
+    const char* fn = "mdtile_blend_lattice";
+    if (int rc = lattice_check(fn, lat)) return rc;
+    MDT_CHECK_ARG(a && batch_out, "%s: null argument", fn);
+    // what this form does not do, by name
+    MDT_CHECK_ARG(a->flags == 0, "%s: the lattice takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", fn, a->flags);
+    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "%s: the lattice takes no row band [%d,%d): it is not combined with the multi-GPU path", fn, a->row_lo,
+                  a->row_hi);
+    MDT_CHECK_ARG(!a->d_weights && !a->d_rescale, "%s: d_weights and d_rescale must be NULL: the kernel forms the weight sum of the step's grid itself", fn);
+    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "%s: bad N=%d C=%d", fn, a->N, a->C);
+    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "%s: bad method %d", fn, a->method);
+    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "%s: bad dtype %d", fn, a->dtype);
+    MDT_CHECK_ARG(a->d_x_out, "%s: null output", fn);
+    MDT_CHECK_ARG(a->method != MDTILE_METHOD_MOD || a->d_tile_w, "%s: Mixture of Diffusers needs d_tile_w", fn);
+    if (int rc = batches_check(fn, lat, num_batches)) return rc;
+    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "%s: null batch pointer %d", fn, b);
+    LatticeBlendParams P;
+    memset(&P, 0, sizeof(P));
+    fill_params(P, lat, a->N, a->C);
+    P.tile_w = a->method == MDTILE_METHOD_MOD ? a->d_tile_w : nullptr;
+    P.out = a->d_x_out;
+    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
+    with_dtype(a->dtype, [&](auto* tag) { launch_lattice_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, as_stream(stream)); });
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}

@@ -67,6 +67,11 @@ class _BlendArgs(ctypes.Structure):
                 ("d_weights", c_void_p), ("d_tile_w", c_void_p), ("d_rescale", c_void_p), ("d_x_out", c_void_p)]
 
 
+class _Lattice(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("w", "h", "tile_w", "tile_h", "overlap", "stride_x", "stride_y", "sx", "sy", "cols", "rows", "num_tiles",
+                                     "num_batches", "tile_bs")]
+
+
 # every symbol include/mdtile.h declares: name -> (restype, argtypes)
 _IP = POINTER(c_int)
 _SIGNATURES = {
@@ -102,6 +107,11 @@ _SIGNATURES = {
     "mdtile_plan_create_subset": (c_void_p, [c_void_p, _IP, c_int]),
     "mdtile_plan_active": (c_int, [c_void_p, _IP]),
     "mdtile_blend_sparse": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p, c_void_p]),
+    "mdtile_lattice_make": (c_int, [c_int] * 8 + [POINTER(_Lattice)]),
+    "mdtile_lattice_bboxes": (c_int, [POINTER(_Lattice), _IP]),
+    "mdtile_lattice_weight_map": (c_int, [POINTER(_Lattice), c_void_p, c_void_p, c_void_p]),
+    "mdtile_gather_all_lattice": (c_int, [POINTER(_Lattice), c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
+    "mdtile_blend_lattice": (c_int, [POINTER(_Lattice), POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
@@ -372,6 +382,34 @@ class Plan:
             _lib.mdtile_plan_destroy(h)
 
 
+class Lattice:
+    """The jittered grid of one sampler step on a plain canvas (mdtile_lattice, include/mdtile.h): host integers only, no device table, nothing to
+    destroy.  tile / overlap are the REQUESTED values (clamped as Plan(clamp=True) clamps them); sx in [1, stride_x], sy in [1, stride_y] on an
+    axis that moves (tile < canvas), ignored on one that does not; (stride_x, stride_y) is the lattice at rest.  bboxes / batches are the
+    PUSHED-IN boxes the model runs on, in tile order; num_tiles may differ by a column and a row between two shifts.  Raises MdtileError for a
+    shift out of range."""
+
+    def __init__(self, w: int, h: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, sx: int, sy: int):
+        L = lib()
+        self._c = _Lattice()
+        _check(L.mdtile_lattice_make(int(w), int(h), int(tile_w), int(tile_h), int(overlap), int(tile_bs), int(sx), int(sy), ctypes.byref(self._c)),
+               "mdtile_lattice_make")
+        c = self._c
+        self.w, self.h, self.tile_w, self.tile_h, self.overlap = c.w, c.h, c.tile_w, c.tile_h, c.overlap
+        self.stride_x, self.stride_y, self.sx, self.sy = c.stride_x, c.stride_y, c.sx, c.sy
+        self.cols, self.rows, self.num_tiles, self.num_batches, self.tile_bs = c.cols, c.rows, c.num_tiles, c.num_batches, c.tile_bs
+        buf = (c_int * (4 * self.num_tiles))()
+        _check(L.mdtile_lattice_bboxes(ctypes.byref(c), buf), "mdtile_lattice_bboxes")
+        flat = list(buf)
+        self.bboxes = [tuple(flat[4 * i:4 * i + 4]) for i in range(self.num_tiles)]
+        self.batches = [self.bboxes[i * self.tile_bs:(i + 1) * self.tile_bs] for i in range(self.num_batches)]
+
+    @property
+    def ref(self):
+        """The C struct by reference, for a call of the library."""
+        return ctypes.byref(self._c)
+
+
 def tile_activity(plan: Plan, mask: torch.Tensor) -> List[int]:
     """Per tile of the (plain) plan: 1 when some element of mask[:, y:y+h, x:x+w] is not equal to zero (NaN counts, -0.0 does not), else 0.
     mask: fp32 [P, H, W] (or [H, W]) on the device.  One launch and one device-to-host copy of num_tiles ints."""
@@ -407,6 +445,22 @@ def weight_map_add_grid(plan: Plan, tile_w: Optional[torch.Tensor], weights: tor
         assert tuple(tile_w.shape[-2:]) == (plan.tile_h, plan.tile_w)
     assert weights.numel() == plan.w * plan.h
     _check(lib().mdtile_weight_map_add_grid(plan.handle, _p(tile_w), _p(weights), _stream()), "mdtile_weight_map_add_grid")
+
+
+def lattice_weight_map(lat: Lattice, tile_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The weight sum [h, w] of the step's grid, written (not added): the count of covering tiles (tile_w None), or the sum of the [tile_h, tile_w]
+    map read in lattice coordinates.  The blend forms the same numbers itself; this call is for callers that want to look at them."""
+    if tile_w is not None:
+        _dev_tensor(tile_w, "tile_w", torch.float32)
+        assert tuple(tile_w.shape) == (lat.tile_h, lat.tile_w), f"tile_w {tuple(tile_w.shape)}"
+        device = tile_w.device
+    if out is None:
+        assert device is not None
+        out = torch.empty((lat.h, lat.w), dtype=torch.float32, device=device)
+    _dev_tensor(out, "out", torch.float32)
+    assert out.numel() == lat.h * lat.w
+    _check(lib().mdtile_lattice_weight_map(lat.ref, _p(tile_w), _p(out), _stream()), "mdtile_lattice_weight_map")
+    return out
 
 
 def weight_map_add_rect(weights: torch.Tensor, x: int, y: int, w: int, h: int, rect_w: Optional[torch.Tensor] = None,
@@ -715,6 +769,21 @@ def gather_all_shift(plan: Plan, x_in: torch.Tensor, sx: int, sy: int, out: Opti
     return list(out)
 
 
+def gather_all_lattice(lat: Lattice, x_in: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """gather_all on the step's jittered grid: every tile batch cut at the lattice's pushed-in boxes, one launch, no plan."""
+    _dev_tensor(x_in, "x_in")
+    N, C, H, W = x_in.shape
+    assert (H, W) == (lat.h, lat.w)
+    if out is None:
+        out = [torch.empty((len(b) * N, C, lat.tile_h, lat.tile_w), dtype=x_in.dtype, device=x_in.device) for b in lat.batches]
+    for i, t in enumerate(out):
+        _dev_tensor(t, f"out[{i}]", x_in.dtype)
+        assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"out[{i}] {tuple(t.shape)}"
+    ptrs = (c_void_p * max(1, len(out)))(*[t.data_ptr() for t in out])
+    _check(lib().mdtile_gather_all_lattice(lat.ref, dtype_code(x_in.dtype), N, C, _p(x_in), ptrs, len(out), _stream()), "mdtile_gather_all_lattice")
+    return list(out)
+
+
 def gather_range(plan: Plan, x_in: torch.Tensor, packed: torch.Tensor, tile_lo: int, tile_hi: int) -> torch.Tensor:
     """Tiles [tile_lo, tile_hi) into the packed [T*N, C, th, tw] buffer (rows of other tiles are left untouched)."""
     _dev_tensor(x_in, "x_in")
@@ -897,6 +966,22 @@ def blend_shift(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: i
         assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
     out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
     _check(lib().mdtile_blend_shift(plan.handle, ctypes.byref(a), ptrs, len(batch_out), int(sx), int(sy), _stream()), "mdtile_blend_shift")
+    return out
+
+
+def blend_lattice(lat: Lattice, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, tile_w=None, weights=None, rescale=None,
+                  out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
+    """The blend of the step's jittered grid, one launch: every tile contributes where its LATTICE box lies, read at its pushed-in box; the weight
+    sum of the step (MultiDiffusion's count, Mixture of Diffusers' Gaussian sum and its reciprocal) is formed inside the kernel.  tile_w: the
+    [tile_h, tile_w] map, required for METHOD_MOD.  weights / rescale exist only to be refused: the library takes no maps here."""
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    _check(lib().mdtile_blend_lattice(lat.ref, ctypes.byref(a), ptrs, len(batch_out), _stream()), "mdtile_blend_lattice")
     return out
 
 

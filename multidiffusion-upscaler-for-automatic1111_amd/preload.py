@@ -33,6 +33,14 @@ def preload(parser):
              "place for two steps and small or zero overlaps become usable. Ignored on a grid that does not wrap, by Noise Inversion's own "
              "evaluations and by DemoFusion. Default: off, the grid stays where it is.")
     parser.add_argument(
+        "--mdtile-grid-jitter", action="store_true",
+        help="Tiled Diffusion on a plain canvas (MultiDiffusion, Mixture of Diffusers; the usual img2img upscale): lay the tile grid anew every sampler "
+             "step, offset by a function of the job's seed and the step, tiles that would hang over an edge pushed inside, so that no tile border "
+             "stays in place for two steps and small or zero overlaps become usable. The tile count may change by a column and a row between "
+             "steps. The fixed grid runs instead (one line says why) on a canvas that wraps around (use --mdtile-grid-shift there), with region "
+             "control, when --mdtile-inpaint-skip skips tiles, in Noise Inversion's own evaluations, when the tile spans the canvas and beyond "
+             "320 tile batches. DemoFusion does not read it. Default: off, the grid stays where it is.")
+    parser.add_argument(
         "--mdtile-vae-seam-blend", type=int, default=None, metavar="PX",
         help="Tiled VAE decoder: cross-fade neighbouring tiles over PX image pixels per side of a tile border (1-88; 16-32 is a sensible range), out "
              "of the padding that is otherwise decoded and thrown away, instead of pasting the tiles edge to edge. Every decoded tile is kept "

@@ -26,7 +26,7 @@ from modules.processing import opt_f
 
 import mdtile
 from tile_utils.utils import (BBox, BBoxSettings, BlendMode, Condition, CustomBBox, NoiseInverseCache, Prompt, get_retouch_mask, grid_shift,
-                              shifted_bboxes)
+                              lattice_shift, shifted_bboxes)
 
 try:  # isinstance targets; absent in a bare test host
     from modules.sd_samplers_kdiffusion import KDiffusionSampler
@@ -44,6 +44,8 @@ class AbstractDiffusion:
     NOISE_INVERSION_FULL = "Noise Inversion's own evaluations (get_noise) stay full-canvas"
     # why get_noise never moves the grid (--mdtile-grid-shift)
     NOISE_INVERSION_UNSHIFTED = "Noise Inversion's own evaluations (get_noise) follow no sampler step"
+    # why get_noise never jitters the grid (--mdtile-grid-jitter)
+    NOISE_INVERSION_UNJITTERED = "Noise Inversion's own evaluations (get_noise) follow no sampler step"
 
     def __init__(self, p, sampler):
         self.method = type(self).__name__
@@ -85,6 +87,11 @@ class AbstractDiffusion:
         self.grid_shift = False
         self._shift_at: Optional[tuple] = None       # (sampler step, (sx, sy), the step's boxes): every evaluation of one step shares them
         self._shift_notes: set = set()
+        # --mdtile-grid-jitter: the plain grid is laid anew every sampler step (init_grid_bbox decides what the geometry allows, step_lattice the rest)
+        self.grid_jitter = False
+        self.jitter_max_batches = 0                  # most tile batches a step's lattice can have: the progress bar is sized from it
+        self._lattice_at: Optional[tuple] = None     # (sampler step, mdtile.Lattice, the step's boxes): every evaluation of one step shares them
+        self._jitter_notes: set = set()
         # --mdtile-inpaint-skip: decided on the job's first full-size evaluation (inpaint_skip), when the host has computed p.nmask
         self.skip_mode: Optional[str] = None         # None = not decided yet | "full" | "sparse" | "empty" (the mask touches no tile)
         self.sparse_plan: Optional[mdtile.Plan] = None
@@ -142,7 +149,8 @@ class AbstractDiffusion:
             self._refuse_wrap_x_with("custom regions (region prompt control)")
         self.total_bboxes = 0
         if self.enable_grid_bbox:
-            self.total_bboxes += self.num_batches
+            # --mdtile-grid-jitter: a step's lattice may have a column and a row more than the grid at rest; the bar must not overrun
+            self.total_bboxes += max(self.num_batches, self.jitter_max_batches) if self.grid_jitter and not self.enable_custom_bbox else self.num_batches
         if self.enable_custom_bbox:
             self.total_bboxes += len(self.custom_bboxes)
         assert self.total_bboxes > 0, "Nothing to paint! No background to draw and no custom bboxes were provided."
@@ -225,9 +233,15 @@ class AbstractDiffusion:
         """--mdtile-grid-shift (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_grid_shift", False))
 
+    @staticmethod
+    def grid_jitter_requested() -> bool:
+        """--mdtile-grid-jitter (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_grid_jitter", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
         self.requested_tile_bs = int(tile_bs)
+        self.requested_grid = (int(tile_w), int(tile_h), int(overlap))
         self.skip_mode, self.sparse_plan, self.sparse_batched_bboxes = None, None, []      # a new grid: the mask is read again
         # clamps (tile <= canvas; overlap <= min(requested tile) - 4), origins and batching all happen in the plan
         self.wrap_x = False
@@ -274,6 +288,7 @@ class AbstractDiffusion:
         tile_weights = self.get_tile_weights()
         mdtile.weight_map_add_grid(self.plan, tile_weights if isinstance(tile_weights, Tensor) else None, self.weights)
         self.batched_bboxes = [[BBox(*b) for b in batch] for batch in self.plan.batches]
+        self._init_grid_jitter()
 
     def extended_x(self, t: Tensor, slot: str, scale: int = 1) -> Tensor:
         """wrap-x: cat(t, t[..., :E]) with E = scale * wrap_ext, so that the slice / rectangle of a tile that spans the seam is contiguous in
@@ -323,6 +338,57 @@ class AbstractDiffusion:
             sy = grid_shift(seed, step, 1, self.h) if self.wrap_y else 0
             self._shift_at = (step, (sx, sy), shifted_bboxes(self.batched_bboxes, sx, sy, self.w, self.h))
         return self._shift_at[1], self._shift_at[2]
+
+    # ---- --mdtile-grid-jitter: the plain grid laid anew every sampler step, tiles pushed inside the canvas ---------------------
+    def _jitter_note(self, reason: str):
+        """One line per job and reason why the fixed grid runs although the option is set."""
+        if reason not in self._jitter_notes:
+            self._jitter_notes.add(reason)
+            print(f"[Tiled Diffusion] --mdtile-grid-jitter not applied: {reason}; the grid stays where it is.")
+
+    def _init_grid_jitter(self):
+        """What the geometry decides, once the plan is made: a canvas that wraps, no axis able to move, more batches than the lattice carries."""
+        self.grid_jitter, self._lattice_at, self.jitter_max_batches = False, None, 0
+        if not self.grid_jitter_requested():
+            return
+        if self.wrap_x or self.wrap_y:
+            return self._jitter_note("the canvas wraps around on an axis (--mdtile-wrap-x / --mdtile-wrap-y): use --mdtile-grid-shift there")
+        plan = self.plan
+        if plan.tile_w >= self.w and plan.tile_h >= self.h:
+            return self._jitter_note(f"the tile ({plan.tile_w} x {plan.tile_h} latent px) spans the canvas ({self.w} x {self.h}), no axis can move")
+        # the most tiles a shift can give: shift 1 on every moving axis
+        at_most = mdtile.Lattice(self.w, self.h, *self.requested_grid, self.requested_tile_bs, 1, 1)
+        if at_most.num_batches > mdtile.MAX_BATCHES:
+            return self._jitter_note(f"up to {at_most.num_tiles} tiles make {at_most.num_batches} batches at tile batch size {self.requested_tile_bs}, more "
+                                     f"than the {mdtile.MAX_BATCHES} a lattice carries (raise the tile batch size)")
+        self.grid_jitter, self.jitter_max_batches = True, at_most.num_batches
+
+    def step_lattice(self, own_evaluation: Optional[str] = None, skip: str = "full"):
+        """(lattice, its boxes in batches) of this evaluation with --mdtile-grid-jitter applied, or None: the fixed grid runs.  The shifts are
+        tile_utils.lattice_shift of the job's seed and state.sampling_step on the axes that move; every evaluation made while the counter keeps its
+        value (cond and uncond calls, the slices of a --lowvram batch) gets the same lattice, so that CFG subtracts two results of one tiling.
+        own_evaluation: an evaluation that never moves the grid names itself here; skip: what --mdtile-inpaint-skip decided for it.  Each reason
+        is printed once per job."""
+        if not self.grid_jitter:
+            return None
+        if own_evaluation is not None:
+            return self._jitter_note(own_evaluation)
+        if self.enable_custom_bbox or not self.draw_background:
+            return self._jitter_note("region prompt control is enabled (custom regions, or no background to draw)")
+        if skip != "full":
+            return self._jitter_note(f"--mdtile-inpaint-skip decided \"{skip}\" for this job (tiles are skipped on the fixed grid)")
+        step = int(state.sampling_step)
+        if self._lattice_at is None or self._lattice_at[0] != step:
+            seed = self.job_seed()
+            stride_x, stride_y = self.plan.tile_w - self.plan.overlap, self.plan.tile_h - self.plan.overlap
+            sx = lattice_shift(seed, step, 0, stride_x) if self.plan.tile_w < self.w else 0
+            sy = lattice_shift(seed, step, 1, stride_y) if self.plan.tile_h < self.h else 0
+            lat = mdtile.Lattice(self.w, self.h, *self.requested_grid, self.requested_tile_bs, sx, sy)
+            self._lattice_at = (step, lat, [[BBox(*b) for b in batch] for batch in lat.batches])
+            if getattr(self.p, "extra_generation_params", None) is None:
+                self.p.extra_generation_params = {}
+            self.p.extra_generation_params["Tiled Diffusion grid jitter"] = True
+        return self._lattice_at[1], self._lattice_at[2]
 
     # ---- --mdtile-inpaint-skip: only the tiles the job's latent mask touches ------------------------------------------------------------
     def _skip_note(self, reason: str):

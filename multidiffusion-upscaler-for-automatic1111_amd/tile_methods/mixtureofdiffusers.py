@@ -82,17 +82,24 @@ class MixtureOfDiffusers(AbstractDiffusion):
 
         # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
         skip = self.inpaint_skip(self.NOISE_INVERSION_FULL if noise_inverse_step >= 0 else None)
+        # --mdtile-grid-jitter (plain grids only, never with the sparse plan or regions): this step's lattice and its pushed-in boxes, or None
+        jitter = self.step_lattice(self.NOISE_INVERSION_UNJITTERED if noise_inverse_step >= 0 else None, skip)
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
         # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
         if self.grid_shift:
             (sx, sy), batched_bboxes = self.step_shift(self.NOISE_INVERSION_UNSHIFTED if noise_inverse_step >= 0 else None)
+        if jitter is not None:
+            lattice, batched_bboxes = jitter
 
         tile_outs: List[Tensor] = []
         if self.draw_background:
             # K2, one launch
-            x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
+            if jitter is not None:
+                x_tiles = mdtile.gather_all_lattice(lattice, x_in)
+            else:
+                x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
             for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
@@ -135,6 +142,9 @@ class MixtureOfDiffusers(AbstractDiffusion):
         if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MOD, tile_outs, N, C, fill=x_in, tile_w=self.get_tile_weights(),
                                                 rescale=self.rescale_factor)
+            return self.x_buffer
+        if jitter is not None:    # every tile where its lattice box lies, the Gaussian in lattice coordinates; the step's sum and reciprocal in the kernel
+            self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights())
             return self.x_buffer
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MOD, tile_outs, N, C, sx=sx, sy=sy, tile_w=self.get_tile_weights(),

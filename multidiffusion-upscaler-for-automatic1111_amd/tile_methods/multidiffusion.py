@@ -120,17 +120,24 @@ class MultiDiffusion(AbstractDiffusion):
 
         # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
         skip = self.inpaint_skip(own_evaluation)
+        # --mdtile-grid-jitter (plain grids only, never with the sparse plan or regions): this step's lattice and its pushed-in boxes, or None
+        jitter = self.step_lattice(None if own_evaluation is None else self.NOISE_INVERSION_UNJITTERED, skip)
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
         # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
         if self.grid_shift:
             (sx, sy), batched_bboxes = self.step_shift(None if own_evaluation is None else self.NOISE_INVERSION_UNSHIFTED)
+        if jitter is not None:
+            lattice, batched_bboxes = jitter
 
         tile_outs: List[Tensor] = []
         if self.draw_background:
             # K2: every tile batch, one launch
-            x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
+            if jitter is not None:
+                x_tiles = mdtile.gather_all_lattice(lattice, x_in)
+            else:
+                x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
             for batch_id, bboxes in enumerate(batched_bboxes):
                 if state.interrupted:
                     return x_in
@@ -156,6 +163,9 @@ class MultiDiffusion(AbstractDiffusion):
 
         if skip == "sparse":      # live pixels as the full blend has them, x_in everywhere else (no regions on this path)
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in, weights=self.weights)
+            return self.x_buffer
+        if jitter is not None:    # every tile where its lattice box lies; the step's weight sum is formed in the kernel
+            self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MD, tile_outs, N, C)
             return self.x_buffer
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MD, tile_outs, N, C, sx=sx, sy=sy, weights=self.weights)

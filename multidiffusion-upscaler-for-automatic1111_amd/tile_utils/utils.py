@@ -194,6 +194,12 @@ def grid_shift(seed: int, step: int, axis: int, extent: int) -> int:
     return z % int(extent)
 
 
+def lattice_shift(seed: int, step: int, axis: int, stride: int) -> int:
+    """--mdtile-grid-jitter: the shift of the jittered grid along one axis (0 = x, 1 = y) at one sampler step, in [1, stride] (stride = the lattice
+    at rest).  grid_shift's integers moved up by one: no torch or numpy generator is touched."""
+    return 1 + grid_shift(seed, step, axis, stride)
+
+
 def shifted_bboxes(batched_bboxes: List[List[BBox]], sx: int, sy: int, w: int, h: int) -> List[List[BBox]]:
     """The boxes of a wrap plan with every origin displaced cyclically: ((x + sx) mod w, (y + sy) mod h), same sizes, same order."""
     return [[BBox((b.x + sx) % w, (b.y + sy) % h, b.w, b.h) for b in batch] for batch in batched_bboxes]

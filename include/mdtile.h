@@ -243,6 +243,66 @@ int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args
                           const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------------------
+ * Custom regions on a wrap-around canvas (csrc/wrap_regions.hip).  Nothing upstream corresponds to it.  A rectangle (x, y, w, h)
+ * on a canvas W x H with flags (wrap_x, wrap_y) covers the canvas pixels ((y + i) mod H, (x + j) mod W), i in [0, h), j in [0, w); it has ONE
+ * origin and one dense [h, w] (or [N, C, h, w]) tensor whether or not it crosses a seam.  Valid iff 0 <= x < W, 0 <= y < H, 0 < w <= W,
+ * 0 < h <= H, and x + w <= W unless wrap_x, y + h <= H unless wrap_y.  Canvas pixel (yc, xc) is covered iff ry = (yc - y) mod H < h and
+ * rx = (xc - x) mod W < w, and then reads the rectangle's tensor at off = ry * w + rx.  Since w <= W and h <= H no pixel is covered twice by one
+ * rectangle.  mdtile_blend, mdtile_blend_shift, mdtile_blend_finalize and the plain rect calls are unchanged and keep their refusals: regions on a
+ * wrap plan go through the calls below only.
+ *
+ * mdtile_gather_rect_wrap:         out[n, c, i, j] = x_in[n, c, (y + i) mod H, (x + j) mod W], copied as bits (dtype = MDTILE_DT_*).  A rectangle inside
+ *                                  the canvas: mdtile_gather_rect.
+ * mdtile_weight_map_add_rect_wrap: weights[(y + i) mod H, (x + j) mod W] += d_rect_w ? d_rect_w[i, j] : scalar -- mdtile_weight_map_add_rect with the
+ *                                  destination taken mod the canvas; every covered pixel receives exactly one add.
+ * mdtile_region_noise_wrap:        mdtile_region_noise's definition (per layer: sum + hit count over the regions in list order, averaged where the
+ *                                  count > 1; background pasted where its count > 0, foreground on top) with coverage and offsets on the circle.
+ * mdtile_blend_wrap_regions:       plan = a wrap plan (mdtile_plan_create_wrap); batch_out / num_batches as mdtile_blend (0 = no grid is drawn); wr:
+ *     regions      canvas coordinates, list order; .out [N, C, h, w] in args->dtype; .weight [h, w] fp32: FG = the feather mask; BG + Mixture of
+ *                  Diffusers = the region's RAW Gaussian -- NOT premultiplied by a reciprocal map as mdtile_blend takes it: the kernel multiplies it
+ *                  by this pixel's reciprocal; BG + MultiDiffusion: unused, may be NULL
+ *     d_grid_w     [H, W] fp32 in PLAN coordinates: the grid's weight sum (mdtile_weight_map_add_grid on zeros; d_tile_w NULL for MultiDiffusion, the
+ *                  Gaussian for Mixture of Diffusers); NULL iff num_batches == 0
+ *     d_region_w   [H, W] fp32 in CANVAS coordinates: the BG regions' weight sum (mdtile_weight_map_add_rect_wrap on zeros in list order, scalar 1.0 for
+ *                  MultiDiffusion, the raw Gaussians for Mixture of Diffusers); required, all zeros when there is no BG region
+ *     sx, sy       the grid's shift as in mdtile_blend_shift; (0, 0) = the grid at rest
+ *   Two maps because the grid's map travels with the shift while the regions stay on the canvas: their sum is another one every step.
+ *   args->d_weights and args->d_rescale must be NULL (the kernel forms the total and its reciprocal); d_tile_w is required for Mixture of Diffusers
+ *   when num_batches > 0; flags = 0, row_lo = row_hi = 0.
+ *   For canvas pixel (yc, xc), plan pixel (yp, xp) = ((yc - sy) mod H, (xc - sx) mod W) and plane (n, c), in fp32 without contraction (half I/O: fp32
+ *   arithmetic on the dtype-rounded inputs, rounded once at the store):
+ *     wsum = (d_grid_w ? d_grid_w[yp, xp] : 0.0f) + d_region_w[yc, xc];     MoD: resc = 1.0f / wsum (IEEE division; inf at 0, never multiplied there)
+ *     buf  = +0.0;  the grid tiles covering (yp, xp) in ascending tile index, as mdtile_blend on the plan:  MD buf += v;  MoD buf += v * (tile_w[ty, tx] * resc)
+ *            then the BG regions covering (yc, xc) in list order:                                           MD buf += v_r;  MoD buf += v_r * (R.weight[off] * resc)
+ *     MD:    x = wsum > 1 ? buf / wsum : buf;        MoD: x = buf
+ *     FG:    fbuf += v_r, fmask += R.weight[off], fcnt += 1 over the covering FG regions in list order; fbuf and fmask divided by fcnt where fcnt > 1;
+ *            x = x * (1 - fmask) + fbuf * fmask where fcnt > 0
+ *   Every canvas pixel is written exactly once.  With num_regions = 0 and d_region_w all zeros the result equals mdtile_blend_shift with the plan's own
+ *   maps bit for bit (at shift 0: mdtile_blend).  MultiDiffusion's weight sums are small integers, so gw + (c1 + c2) equals the running `+=` of the
+ *   plain path exactly; for Mixture of Diffusers the grouping gw + (c1 + c2) can differ from (gw + c1) + c2 in the last bit where two or more BG
+ *   regions overlap -- this grouping is the definition here, so that the grid at rest and the shifted grid are one definition.
+ * REFUSED (MDTILE_E_ARG, the text names the reason, nothing is written): a rectangle that is not valid as above (w > W, h > H, x or y off the
+ *   canvas, past an edge on an axis whose flag is 0); for the blend also: a sparse plan, a plain plan, a shift out of range or non-zero on an axis
+ *   that does not wrap, more than MDTILE_MAX_REGIONS regions (the noise call too), any MDTILE_BLEND_* flag (MDTILE_BLEND_PACKED included), a row band,
+ *   non-NULL d_weights / d_rescale, NULL d_region_w, d_grid_w that is not NULL iff num_batches == 0, num_batches neither 0 nor the plan's, a missing
+ *   d_tile_w / region output / region weight, a bad mode, N, C, method or dtype; null pointers where one is required in every call.
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct mdtile_wrap_regions {
+    const mdtile_region* regions; int num_regions;   /* canvas coordinates, list order; may cross a seam on a wrapping axis */
+    const float* d_grid_w;    /* [H,W], PLAN coordinates: the grid's weight sum (mdtile_weight_map_add_grid on zeros); NULL iff num_batches == 0 */
+    const float* d_region_w;  /* [H,W], CANVAS coordinates: the BG regions' weight sum (add_rect_wrap on zeros, list order); required */
+    int sx, sy;               /* the grid's shift as in mdtile_blend_shift; 0, 0 = the grid at rest */
+} mdtile_wrap_regions;
+int mdtile_gather_rect_wrap(int dtype, int N, int C, int W, int H, const void* d_x_in, int x, int y, int w, int h, int wrap_x, int wrap_y,
+                            void* d_out, mdtile_stream_t stream);
+int mdtile_weight_map_add_rect_wrap(float* d_weights, int W, int H, int x, int y, int w, int h, const float* d_rect_w, float scalar, int wrap_x,
+                                    int wrap_y, mdtile_stream_t stream);
+int mdtile_region_noise_wrap(float* d_noise, int N, int C, int H, int W, const mdtile_region* regions, int num_regions, int wrap_x, int wrap_y,
+                             mdtile_stream_t stream);
+int mdtile_blend_wrap_regions(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                              const mdtile_wrap_regions* wr, mdtile_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------------------
  * Tile skipping (img2img inpainting): run only the grid tiles a mask touches.  Nothing upstream corresponds to it.
  *
  * mdtile_tile_activity: d_mask fp32 [planes, H, W], d_active int32[T] on the device.  active[t] = 1 iff some element of

@@ -20,6 +20,8 @@ int walk_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const
                 hipStream_t s, const int* shift = nullptr);
 int walk_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                int num_regions, const void* d_fill, hipStream_t s, const int* shift = nullptr);
+// what every shifted entry point (wrap.hip, wrap_regions.hip) asks of the plan and the shift before anything else is looked at; errors name `fn`
+int shift_check(const char* fn, const struct ::mdtile_plan* plan, int sx, int sy);
 
 // ---- vae_assemble.hip: mdtile_vae_assemble in two halves, for vae_skip.hip (mdtile_vae_assemble_sparse pastes its tiles with them).
 // vae_assemble_check: every test of the table and the result, the peer mapping of every source device; errors name `who`.

@@ -23,30 +23,19 @@
 // source coordinate, the blend keeps its threads on PLAN coordinates and adds it to the store address.  Both are compiled under
 // `if constexpr (SHIFT)` into instantiations of their own, with an argument block of their own; the others hold none of it.
 //
-// Not here (refused with an error that names the reason): custom regions, MDTILE_BLEND_* flags, row bands, mdtile_gather_range,
-// mdtile_blend_finalize -- neither wrap-around nor tile skipping is combined with regions or with the multi-GPU partial path.
+// CUSTOM REGIONS on a wrap-around plan (mdtile_blend_wrap_regions and the three rect calls) are in wrap_regions.hip: a blend
+// kernel of its own that walks the grid as k_walk_blend does and then runs the region tail at the quad's CANVAS coordinates.  The kernels here
+// hold none of it, and mdtile_blend / mdtile_blend_shift still refuse regions on such a plan.  walk.h has what both files share.
+//
+// Not here (refused with an error that names the reason): custom regions through mdtile_blend / mdtile_blend_shift, MDTILE_BLEND_* flags, row
+// bands, mdtile_gather_range, mdtile_blend_finalize -- tile skipping is not combined with regions, and neither wrap-around nor tile skipping
+// with the multi-GPU partial path.
 #include "launchers.h"
+#include "walk.h"
 
 using namespace mdt;
 
 namespace {
-
-// the cyclic run (first | count << 16 over a list of `n` tile columns or rows) walked in ascending index: [0, head) then [first, first + count - head)
-struct CyclicRun {
-    int first, count, head;
-    __device__ __forceinline__ CyclicRun(int packed, int n) {
-        first = packed & 0xffff;
-        count = packed >> 16;
-        head = first + count > n ? first + count - n : 0;
-    }
-    __device__ __forceinline__ int at(int k) const { return k < head ? k : first + (k - head); }
-};
-
-// canvas coordinate p relative to a tile origin o, on the circle of `extent` coordinates: in [0, extent); covered by the tile iff < its size
-__device__ __forceinline__ int rel(int p, int o, int extent) {
-    const int d = p - o;
-    return d < 0 ? d + extent : d;
-}
 
 // weights[p] += sum over the covering tiles, ascending tile index (rows outer, columns inner), of tile_w[...] (or 1.0)
 __global__ __launch_bounds__(256) void k_wrap_weight_grid(int W, int H, int tw, int cols, int rows, const int* __restrict__ xs,
@@ -145,38 +134,6 @@ struct WalkBlendShiftParams : WalkBlendParams {
     int shift_x, shift_y;     // 0 <= shift_x < W, 0 <= shift_y < H; 0 on an axis that does not wrap
 };
 static_assert(sizeof(WalkBlendShiftParams) <= 4096, "kernel argument block must stay under 4 KiB");
-
-// the storage type as an integer of its size: what passes `fill` through without a float conversion
-template <typename T> struct RawOf { using type = unsigned short; };
-template <> struct RawOf<float> { using type = unsigned int; };
-template <typename R> struct __attribute__((packed, aligned(sizeof(R)))) raw4_u { R v[4]; };   // 4 elements at an element-aligned address
-
-template <typename T> __device__ __forceinline__ typename RawOf<T>::type raw_bits(float v);
-template <> __device__ __forceinline__ unsigned int raw_bits<float>(float v) { return __float_as_uint(v); }
-template <> __device__ __forceinline__ unsigned short raw_bits<__half>(float v) { return __half_as_ushort(__float2half_rn(v)); }
-template <> __device__ __forceinline__ unsigned short raw_bits<__hip_bfloat16>(float v) {
-    const __hip_bfloat16 h = __float2bfloat16(v);
-    unsigned short u;
-    __builtin_memcpy(&u, &h, sizeof(u));
-    return u;
-}
-
-// 4 consecutive elements at an address aligned to their total size (16 bytes of fp32, 8 bytes of a 16-bit type): one load instruction
-template <typename T> __device__ __forceinline__ void load4_aligned(const T* p, float (&o)[4]);
-template <> __device__ __forceinline__ void load4_aligned<float>(const float* p, float (&o)[4]) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-}
-template <> __device__ __forceinline__ void load4_aligned<__half>(const __half* p, float (&o)[4]) {
-    const ushort4 t = *reinterpret_cast<const ushort4*>(p);
-    o[0] = __half2float(__ushort_as_half(t.x)); o[1] = __half2float(__ushort_as_half(t.y));
-    o[2] = __half2float(__ushort_as_half(t.z)); o[3] = __half2float(__ushort_as_half(t.w));
-}
-template <> __device__ __forceinline__ void load4_aligned<__hip_bfloat16>(const __hip_bfloat16* p, float (&o)[4]) {
-    const ushort4 t = *reinterpret_cast<const ushort4*>(p);
-    o[0] = __uint_as_float((unsigned)t.x << 16); o[1] = __uint_as_float((unsigned)t.y << 16);
-    o[2] = __uint_as_float((unsigned)t.z << 16); o[3] = __uint_as_float((unsigned)t.w << 16);
-}
 
 // One thread owns one quad (4 consecutive canvas columns of one row; rows start at x = 0, so a quad never straddles the seam) for PP planes.
 // The tile rows that cover the canvas row come from rowinfo[y].x and the tile columns that cover ANY pixel of the quad from colquad[xq].x, both
@@ -515,7 +472,7 @@ int mdt::walk_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void
 }
 
 // what both shifted entry points ask of the plan and the shift before anything else is looked at
-static int shift_check(const char* fn, const mdtile_plan* p, int sx, int sy) {
+int mdt::shift_check(const char* fn, const mdtile_plan* p, int sx, int sy) {
     MDT_CHECK_ARG(p, "%s: null plan", fn);
     MDT_CHECK_ARG(!plan_sparse(p), "%s: refused on a sparse plan: the grid shift is not combined with tile skipping", fn);
     MDT_CHECK_ARG(plan_wraps(p), "%s: refused on a plain plan: only a wrap-around plan (mdtile_plan_create_wrap) has a circle to shift the grid on", fn);

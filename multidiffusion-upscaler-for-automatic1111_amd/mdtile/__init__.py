@@ -67,6 +67,10 @@ class _BlendArgs(ctypes.Structure):
                 ("d_weights", c_void_p), ("d_tile_w", c_void_p), ("d_rescale", c_void_p), ("d_x_out", c_void_p)]
 
 
+class _WrapRegions(ctypes.Structure):
+    _fields_ = [("regions", POINTER(_Region)), ("num_regions", c_int), ("d_grid_w", c_void_p), ("d_region_w", c_void_p), ("sx", c_int), ("sy", c_int)]
+
+
 class _Lattice(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("w", "h", "tile_w", "tile_h", "overlap", "stride_x", "stride_y", "sx", "sy", "cols", "rows", "num_tiles",
                                      "num_batches", "tile_bs")]
@@ -103,6 +107,10 @@ _SIGNATURES = {
     "mdtile_blend_shift": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),
     "mdtile_blend_dispatch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _IP]),
     "mdtile_blend_finalize": (c_int, [c_void_p, POINTER(_BlendArgs), c_void_p, POINTER(_Region), c_int, c_void_p]),
+    "mdtile_gather_rect_wrap": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mdtile_weight_map_add_rect_wrap": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p]),
+    "mdtile_region_noise_wrap": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_int, c_int, c_void_p]),
+    "mdtile_blend_wrap_regions": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_WrapRegions), c_void_p]),
     "mdtile_tile_activity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mdtile_plan_create_subset": (c_void_p, [c_void_p, _IP, c_int]),
     "mdtile_plan_active": (c_int, [c_void_p, _IP]),
@@ -474,11 +482,20 @@ def weight_map_add_rect(weights: torch.Tensor, x: int, y: int, w: int, h: int, r
            "mdtile_weight_map_add_rect")
 
 
-def region_noise(noise: torch.Tensor, regions) -> torch.Tensor:
-    """In-place per-region noise paste (tilediffusion.py:486-529).  noise: [N,C,H,W] fp32 on the GPU;
-    regions: [(x, y, w, h, mode, rand)] with rand = that region's own noise [1,C,h,w] fp32 (same device), in list order."""
-    _dev_tensor(noise, "noise", torch.float32)
-    N, C, H, W = noise.shape
+def weight_map_add_rect_wrap(weights: torch.Tensor, x: int, y: int, w: int, h: int, rect_w: Optional[torch.Tensor] = None,
+                             scalar: float = 1.0, *, wrap_x: bool, wrap_y: bool) -> None:
+    """weight_map_add_rect on a canvas closed on the axes whose flag is set: the rectangle's pixels are ((y + i) mod H, (x + j) mod W)."""
+    _dev_tensor(weights, "weights", torch.float32)
+    H, W = weights.shape[-2:]
+    if rect_w is not None:
+        _dev_tensor(rect_w, "rect_w", torch.float32)
+        assert rect_w.numel() == w * h
+    _check(lib().mdtile_weight_map_add_rect_wrap(_p(weights), W, H, int(x), int(y), int(w), int(h), _p(rect_w), scalar, int(bool(wrap_x)),
+                                                 int(bool(wrap_y)), _stream()), "mdtile_weight_map_add_rect_wrap")
+
+
+def _noise_regions_array(noise: torch.Tensor, regions):
+    C = noise.shape[1]
     arr = (_Region * max(1, len(regions)))()
     keep = []
     for i, (x, y, w, h, mode, rand) in enumerate(regions):
@@ -486,6 +503,25 @@ def region_noise(noise: torch.Tensor, regions) -> torch.Tensor:
         assert tuple(rand.shape) == (1, C, h, w), f"region {i}: noise shape {tuple(rand.shape)} != (1, {C}, {h}, {w})"
         keep.append(rand)
         arr[i] = _Region(int(x), int(y), int(w), int(h), int(mode), 0, rand.data_ptr(), None)
+    return arr, keep
+
+
+def region_noise_wrap(noise: torch.Tensor, regions, *, wrap_x: bool, wrap_y: bool) -> torch.Tensor:
+    """region_noise on a canvas closed on the axes whose flag is set: a region may pass the edge there and goes on at the other side."""
+    _dev_tensor(noise, "noise", torch.float32)
+    N, C, H, W = noise.shape
+    arr, _keep = _noise_regions_array(noise, regions)
+    _check(lib().mdtile_region_noise_wrap(_p(noise), N, C, H, W, arr, len(regions), int(bool(wrap_x)), int(bool(wrap_y)), _stream()),
+           "mdtile_region_noise_wrap")
+    return noise
+
+
+def region_noise(noise: torch.Tensor, regions) -> torch.Tensor:
+    """In-place per-region noise paste (tilediffusion.py:486-529).  noise: [N,C,H,W] fp32 on the GPU;
+    regions: [(x, y, w, h, mode, rand)] with rand = that region's own noise [1,C,h,w] fp32 (same device), in list order."""
+    _dev_tensor(noise, "noise", torch.float32)
+    N, C, H, W = noise.shape
+    arr, _keep = _noise_regions_array(noise, regions)
     _check(lib().mdtile_region_noise(_p(noise), N, C, H, W, arr, len(regions), _stream()), "mdtile_region_noise")
     return noise
 
@@ -804,6 +840,19 @@ def gather_rect(x_in: torch.Tensor, x: int, y: int, w: int, h: int) -> torch.Ten
     return out
 
 
+def gather_rect_wrap(x_in: torch.Tensor, x: int, y: int, w: int, h: int, *, wrap_x: bool, wrap_y: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gather_rect on a canvas closed on the axes whose flag is set: out[n, c, i, j] = x_in[n, c, (y + i) mod H, (x + j) mod W]."""
+    _dev_tensor(x_in, "x_in")
+    N, C, H, W = x_in.shape
+    if out is None:
+        out = torch.empty((N, C, h, w), dtype=x_in.dtype, device=x_in.device)
+    _dev_tensor(out, "out", x_in.dtype)
+    assert out.numel() >= N * C * h * w, f"out {tuple(out.shape)}"
+    _check(lib().mdtile_gather_rect_wrap(dtype_code(x_in.dtype), N, C, W, H, _p(x_in), int(x), int(y), int(w), int(h), int(bool(wrap_x)),
+                                         int(bool(wrap_y)), _p(out), _stream()), "mdtile_gather_rect_wrap")
+    return out
+
+
 # ---- blend -----------------------------------------------------------------------------------------------------------
 class RegionSpec:
     """One custom region for the blend: rect, mode, its model output and (optional) weight / feather map."""
@@ -814,8 +863,9 @@ class RegionSpec:
         self.x, self.y, self.w, self.h, self.mode, self.out, self.weight = x, y, w, h, mode, out, weight
 
 
-def _regions_array(regions: Sequence[RegionSpec], dtype):
-    if len(regions) > MAX_REGIONS:
+def _regions_array(regions: Sequence[RegionSpec], dtype, limit: bool = True):
+    """limit False: the count is left to the library (blend_wrap_regions: it refuses by name)."""
+    if limit and len(regions) > MAX_REGIONS:
         raise MdtileError(f"{len(regions)} regions > {MAX_REGIONS}")
     arr = (_Region * max(1, len(regions)))()
     keep = []
@@ -966,6 +1016,35 @@ def blend_shift(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: i
         assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
     out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
     _check(lib().mdtile_blend_shift(plan.handle, ctypes.byref(a), ptrs, len(batch_out), int(sx), int(sy), _stream()), "mdtile_blend_shift")
+    return out
+
+
+def blend_wrap_regions(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, regions: Sequence[RegionSpec] = (),
+                       grid_w: Optional[torch.Tensor], region_w: torch.Tensor, sx: int = 0, sy: int = 0, tile_w=None, weights=None, rescale=None,
+                       out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
+    """The blend of a wrap-around plan WITH custom regions, one launch: the grid (batch_out; empty = no grid is drawn) displaced by (sx, sy), then
+    the regions where they lie on the canvas -- a region may cross a seam on an axis that wraps.  grid_w: the grid's weight sum [H, W] in plan
+    coordinates (None iff batch_out is empty); region_w: the background regions' weight sum [H, W] on the canvas (zeros when there is none).
+    A background region's weight is its RAW Gaussian (Mixture of Diffusers): the kernel forms grid_w + region_w and its reciprocal per pixel.
+    weights / rescale exist only to be refused: the library takes no total map here."""
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    elif len(regions):
+        dtype, device = regions[0].out.dtype, regions[0].out.device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert i >= len(plan.batches) or tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    for nm, t in (("grid_w", grid_w), ("region_w", region_w)):
+        if t is not None:
+            _dev_tensor(t, nm, torch.float32)
+            assert t.numel() == plan.h * plan.w, f"{nm} {tuple(t.shape)}"
+    out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    for i, r in enumerate(regions):
+        assert tuple(r.out.shape) == (N, C, r.h, r.w), f"region[{i}] output {tuple(r.out.shape)} vs [{N}, {C}, {r.h}, {r.w}]"
+    rarr, _keep = _regions_array(regions, dtype, limit=False)
+    wr = _WrapRegions(rarr, len(regions), _p(grid_w).value, _p(region_w).value, int(sx), int(sy))
+    _check(lib().mdtile_blend_wrap_regions(plan.handle, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(wr), _stream()), "mdtile_blend_wrap_regions")
     return out
 
 

@@ -19,13 +19,21 @@ def preload(parser):
     parser.add_argument(
         "--mdtile-wrap-x", action="store_true",
         help="Close the canvas horizontally (360-degree panoramas): Tiled Diffusion lays its tile columns on a circle, so that tiles span the seam "
-             "between the right and the left edge, and Tiled VAE pads its input with the columns of the other edge instead of zeros. Not combined "
-             "with region control. Default: off, the canvas is a strip with two ends.")
+             "between the right and the left edge, and Tiled VAE pads its input with the columns of the other edge instead of zeros. Region "
+             "control on it needs --mdtile-wrap-regions. Default: off, the canvas is a strip with two ends.")
     parser.add_argument(
         "--mdtile-wrap-y", action="store_true",
         help="Close the canvas vertically: tile rows on a circle, tiles span the seam between the bottom and the top edge, and Tiled VAE pads its "
              "input with the rows of the other edge. With --mdtile-wrap-x the canvas is a torus (seamless textures that tile in both directions). "
-             "Not combined with region control. Default: off.")
+             "Region control on it needs --mdtile-wrap-regions. Default: off.")
+    parser.add_argument(
+        "--mdtile-wrap-regions", action="store_true",
+        help="Tiled Diffusion with --mdtile-wrap-x / --mdtile-wrap-y (MultiDiffusion, Mixture of Diffusers): allow region prompt control on the "
+             "closed canvas. A region's rectangle is laid on the circle along every axis that wraps, so it may cross the seam (x + w past the right "
+             "edge goes on at the left one); background and foreground regions, each region's own noise, ControlNet and StableSR follow it, with "
+             "and without --mdtile-grid-shift. Without this option regions on a wrapped canvas are refused, as before. Ignored (one line) when no "
+             "axis wraps. Not combined with Noise Inversion's renoise composite when only regions are painted, nor with the multi-GPU partial "
+             "path; DemoFusion does not read it. Default: off.")
     parser.add_argument(
         "--mdtile-grid-shift", action="store_true",
         help="Tiled Diffusion with --mdtile-wrap-x / --mdtile-wrap-y (MultiDiffusion, Mixture of Diffusers): displace the whole tile grid cyclically "

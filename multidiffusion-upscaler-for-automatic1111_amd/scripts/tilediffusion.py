@@ -25,7 +25,7 @@ from modules.processing import opt_f
 from tile_methods.abstractdiffusion import AbstractDiffusion
 from tile_methods.mixtureofdiffusers import MixtureOfDiffusers
 from tile_methods.multidiffusion import MultiDiffusion
-from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, color_fix_image, splitable,
+from tile_utils.utils import (BlendMode, DEFAULT_BBOX_SETTINGS, Method, NUM_BBOX_PARAMS, build_bbox_settings, color_fix_image, region_rect, splitable,
                               upscale_init_image)
 
 CFG_PATH_NOTE = "region_configs"
@@ -304,17 +304,19 @@ class Script(scripts.Script):
         """Upstream :486-529: the job's noise, with every region's rectangle replaced by that region's own noise
         (`torch.manual_seed(seed)` + CPU `randn`, exactly as upstream draws it); overlapping regions of one kind are
         averaged, foreground goes on top of background.  The sum / count / average / paste runs in ONE engine launch."""
-        import math
         import mdtile
         from modules.processing import get_fixed_seed
         noise = Script.create_random_tensors_original_md(shape, seeds, subseeds, subseed_strength, seed_resize_from_h,
                                                          seed_resize_from_w, p)
         height, width = shape[1], shape[2]
+        # --mdtile-wrap-regions on a canvas that wraps: the delegate (built by the sampler hijack before the noise is drawn) has laid its regions
+        # on the circle, and each region's noise goes where its rectangle is
+        d = self.delegate
+        wrap_x, wrap_y = (d.wrap_x, d.wrap_y) if d is not None and d.wrap_regions else (False, False)
         regions = []
         for i, v in bbox_settings.items():
             seed = get_fixed_seed(v.seed)
-            x, y = max(0, int(v.x * width)), max(0, int(v.y * height))
-            w, h = min(width - x, math.ceil(v.w * width)), min(height - y, math.ceil(v.h * height))
+            x, y, w, h = region_rect(v.x, v.y, v.w, v.h, width, height, wrap_x, wrap_y)
             torch.manual_seed(seed)
             rand = torch.randn((1, noise.shape[1], h, w), device=devices.cpu)
             mode = BlendMode(v.blend_mode)
@@ -326,7 +328,10 @@ class Script(scripts.Script):
             if key in region_info:
                 region_info[key]["seed"] = seed
         work = noise.to(torch.float32).contiguous()
-        mdtile.region_noise(work, regions)
+        if wrap_x or wrap_y:
+            mdtile.region_noise_wrap(work, regions, wrap_x=wrap_x, wrap_y=wrap_y)
+        else:
+            mdtile.region_noise(work, regions)
         return work.to(noise.dtype)
 
     def reset(self, keep_sampler_hijack: bool = False, p=None):

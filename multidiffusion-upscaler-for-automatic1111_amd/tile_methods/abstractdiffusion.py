@@ -13,7 +13,6 @@ land on the same surface.  Everything numerical is delegated to the mdtile engin
 """
 from __future__ import annotations
 
-import math
 from types import MethodType
 from typing import Dict, List, Optional
 
@@ -26,7 +25,7 @@ from modules.processing import opt_f
 
 import mdtile
 from tile_utils.utils import (BBox, BBoxSettings, BlendMode, Condition, CustomBBox, NoiseInverseCache, Prompt, get_retouch_mask, grid_shift,
-                              lattice_shift, shifted_bboxes)
+                              lattice_shift, region_rect, shifted_bboxes)
 
 try:  # isinstance targets; absent in a bare test host
     from modules.sd_samplers_kdiffusion import KDiffusionSampler
@@ -105,6 +104,10 @@ class AbstractDiffusion:
         self.uncond_basis = None
         self.draw_background = True
         self.causal_layers = None
+        # --mdtile-wrap-regions: regions on a canvas that wraps (init_custom_bbox decides).  self.weights then stays the GRID's map
+        # in plan coordinates and region_w holds the background regions' weight sum on the canvas: the blend adds them per pixel, every step
+        self.wrap_regions = False
+        self.region_w: Optional[Tensor] = None
 
         # optional extensions, armed by the init_* calls of the Script
         self.noise_inverse_enabled = False
@@ -145,8 +148,12 @@ class AbstractDiffusion:
         return None
 
     def init_done(self):
-        if self.enable_custom_bbox:
-            self._refuse_wrap_x_with("custom regions (region prompt control)")
+        if self.enable_custom_bbox and not self.wrap_regions:
+            self._refuse_wrap_x_with(self.REGIONS, self.WRAP_REGIONS_HINT)
+        if self.wrap_regions and self.noise_inverse_enabled and not self.enable_grid_bbox and self.noise_inverse_renoise_strength > 0:
+            raise RuntimeError("[Tiled Diffusion] --mdtile-wrap-regions cannot be combined with Noise Inversion's renoise composite when only "
+                               "regions are painted (no background): mdtile_noise_inverse_blend lays its regions on a plain canvas. Draw the "
+                               "background, or set the renoise strength to 0.")
         self.total_bboxes = 0
         if self.enable_grid_bbox:
             # --mdtile-grid-jitter: a step's lattice may have a column and a row more than the grid at rest; the bar must not overrun
@@ -205,7 +212,7 @@ class AbstractDiffusion:
     def slice_icond(self, icond: Tensor, bbox: BBox) -> Tensor:
         """img2img image-conditioning follows the tile (it has the latent's spatial size); txt2img's dummy does not."""
         if tuple(icond.shape[2:]) == (self.h, self.w):
-            return self.extended_x(icond, "icond")[bbox.slicer]      # custom regions never pass the edge; grid tiles of a wrap-x plan may
+            return self.extended_x(icond, "icond")[bbox.slicer]      # grid tiles of a wrap plan and --mdtile-wrap-regions regions may pass the edge
         return icond
 
     # ------------------------------------------------------------------------------------------------ grid
@@ -222,6 +229,11 @@ class AbstractDiffusion:
     def wrap_y_requested() -> bool:
         """--mdtile-wrap-y (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_wrap_y", False))
+
+    @staticmethod
+    def wrap_regions_requested() -> bool:
+        """--mdtile-wrap-regions (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_wrap_regions", False))
 
     @staticmethod
     def inpaint_skip_requested() -> bool:
@@ -459,15 +471,25 @@ class AbstractDiffusion:
             self.pbar.refresh()
         return "sparse"
 
-    def _refuse_wrap_x_with(self, what: str):
+    REGIONS = "custom regions (region prompt control)"
+    WRAP_REGIONS_HINT = " Or pass --mdtile-wrap-regions: region control on the closed canvas, with regions that may cross the seam."
+
+    def _refuse_wrap_x_with(self, what: str, hint: str = ""):
         if self.wrap_x or self.wrap_y:
             opts = " / ".join(o for o, on in (("--mdtile-wrap-x", self.wrap_x), ("--mdtile-wrap-y", self.wrap_y)) if on)
             raise RuntimeError(f"[Tiled Diffusion] {opts} cannot be combined with {what}: the wrap-around blend has no "
-                               "region path. Turn one of them off.")
+                               "region path. Turn one of them off." + hint)
 
     # ------------------------------------------------------------------------------------------------ regions
     def init_custom_bbox(self, bbox_settings: Dict[int, BBoxSettings], draw_background: bool, causal_layers: bool):
-        self._refuse_wrap_x_with("custom regions (region prompt control)")
+        wrap_regions = self.wrap_regions_requested()
+        if wrap_regions and not (self.wrap_x or self.wrap_y):
+            print("[Tiled Diffusion] --mdtile-wrap-regions ignored: no axis of the canvas wraps around (--mdtile-wrap-x / --mdtile-wrap-y); the "
+                  "regions are laid on the plain canvas.")
+            wrap_regions = False
+        if not wrap_regions:
+            self._refuse_wrap_x_with(self.REGIONS, self.WRAP_REGIONS_HINT)
+        self.wrap_regions = wrap_regions
         self.enable_custom_bbox = True
         self.causal_layers = causal_layers
         self.draw_background = draw_background
@@ -480,12 +502,22 @@ class AbstractDiffusion:
             enable, fx, fy, fw, fh, prompt, neg, blend_mode, feather_ratio, seed = s
             if not enable or fx > 1.0 or fy > 1.0 or fw <= 0.0 or fh <= 0.0:
                 continue
-            x, y = max(0, int(fx * self.w)), max(0, int(fy * self.h))
-            w, h = min(self.w - x, math.ceil(fw * self.w)), min(self.h - y, math.ceil(fh * self.h))
+            x, y, w, h = region_rect(fx, fy, fw, fh, self.w, self.h, wrap_regions and self.wrap_x, wrap_regions and self.wrap_y)
             self.custom_bboxes.append(CustomBBox(x, y, w, h, prompt, neg, blend_mode, feather_ratio, seed))
         if not self.custom_bboxes:
             self.enable_custom_bbox = False
+            self.wrap_regions = False
             return
+        if wrap_regions:
+            self.region_w = torch.zeros((1, 1, self.h, self.w), device=devices.device, dtype=torch.float32)
+            # a region that crosses a seam ends at x + w > W (y + h > H): the extended copies the Python slices cut from (extended_x: image
+            # conditioning, ControlNet hints, StableSR) grow to the largest overhang of a tile or a region
+            self.wrap_ext = max([self.wrap_ext] + [b.x + b.w - self.w for b in self.custom_bboxes])
+            self.wrap_ext_y = max([self.wrap_ext_y] + [b.y + b.h - self.h for b in self.custom_bboxes])
+            self._wrap_copies = {}
+            if getattr(self.p, "extra_generation_params", None) is None:
+                self.p.extra_generation_params = {}
+            self.p.extra_generation_params["Tiled Diffusion wrap regions"] = True
         self._init_region_conds()
 
     def _init_region_conds(self):
@@ -515,6 +547,28 @@ class AbstractDiffusion:
             mode = mdtile.REGION_FG if bbox.blend_mode == BlendMode.FOREGROUND else mdtile.REGION_BG
             specs.append(mdtile.RegionSpec(bbox.x, bbox.y, bbox.w, bbox.h, mode, out, wgt))
         return specs
+
+    def gather_region(self, x_in: Tensor, bbox: CustomBBox) -> Tensor:
+        """The region's tile of x_in; --mdtile-wrap-regions: cut on the circle, so a region that crosses a seam is one dense tensor."""
+        if self.wrap_regions:
+            return mdtile.gather_rect_wrap(x_in, bbox.x, bbox.y, bbox.w, bbox.h, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
+        return mdtile.gather_rect(x_in, bbox.x, bbox.y, bbox.w, bbox.h)
+
+    def add_region_weight(self, bbox: CustomBBox, rect_w: Optional[Tensor]):
+        """A background region's weight (rect_w None: 1.0) into the weight sum: self.weights, or with --mdtile-wrap-regions the canvas map region_w."""
+        if self.wrap_regions:
+            mdtile.weight_map_add_rect_wrap(self.region_w, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
+        else:
+            mdtile.weight_map_add_rect(self.weights, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0)
+
+    def blend_wrap_regions(self, method: int, tile_outs: List[Tensor], region_outs: List[Tensor], x_in: Tensor, shift) -> Tensor:
+        """--mdtile-wrap-regions: grid (displaced by this step's shift) and regions in one launch; the weight sum is formed in the kernel from
+        the grid's map and region_w, and Mixture of Diffusers' region weights go in raw."""
+        N, C = x_in.shape[:2]
+        tile_w = self.get_tile_weights() if method == mdtile.METHOD_MOD and tile_outs else None
+        return mdtile.blend_wrap_regions(self.plan, method, tile_outs, N, C, regions=self.region_specs(region_outs),
+                                         grid_w=self.weights if tile_outs else None, region_w=self.region_w, sx=shift[0], sy=shift[1],
+                                         tile_w=tile_w, dtype=x_in.dtype, device=x_in.device)
 
     def region_weights(self) -> List[Optional[Tensor]]:
         """Per region: feather mask (foreground) or the method's background weight (None = 1.0)."""
@@ -666,8 +720,8 @@ class AbstractDiffusion:
         if not self.enable_controlnet or not self.org_control_tensor_batch or not self.custom_bboxes:
             return
         bbox = self.custom_bboxes[bbox_id]
-        for param, hint in zip(self.control_params, self.org_control_tensor_batch):
-            hint = self._hint_on_device(hint).contiguous()
+        for k, (param, hint) in enumerate(zip(self.control_params, self.org_control_tensor_batch)):
+            hint = self._hint_on_device(self.extended_x(hint, f"hint{k}", opt_f)).contiguous()      # a region that crosses a seam is contiguous in the copy
             param.hint_cond = mdtile.gather_rects(hint, [(bbox.x * opt_f, bbox.y * opt_f)], bbox.w * opt_f, bbox.h * opt_f,
                                                   repeat=repeat_size, tile_major=False)
 
@@ -702,7 +756,8 @@ class AbstractDiffusion:
         if not self._stablesr_live() or not self.custom_bboxes:
             return
         bbox = self.custom_bboxes[bbox_id]
-        self.stablesr_script.stablesr_model.latent_image = mdtile.gather_rect(self.stablesr_tensor.contiguous(), bbox.x, bbox.y, bbox.w, bbox.h)
+        t = self.extended_x(self.stablesr_tensor, "stablesr").contiguous()
+        self.stablesr_script.stablesr_model.latent_image = mdtile.gather_rect(t, bbox.x, bbox.y, bbox.w, bbox.h)
 
     # ---- Noise Inversion (upstream :591-747) -----------------------------------------------------------------------------
     def init_noise_inverse(self, steps: int, retouch: float, get_cache_callback, set_cache_callback, renoise_strength: float,

@@ -53,7 +53,7 @@ class MixtureOfDiffusers(AbstractDiffusion):
         for bbox in self.custom_bboxes:
             if bbox.blend_mode == BlendMode.BACKGROUND:
                 cw = self.get_weight(bbox.w, bbox.h)
-                mdtile.weight_map_add_rect(self.weights, bbox.x, bbox.y, bbox.w, bbox.h, cw)
+                self.add_region_weight(bbox, cw)
                 self.custom_weights.append(cw.unsqueeze(0).unsqueeze(0))
             else:
                 self.custom_weights.append(None)
@@ -62,6 +62,8 @@ class MixtureOfDiffusers(AbstractDiffusion):
         super().init_done()
         # Gaussian weights can be ~1e-10: normalise up front (inf where nothing is painted, exactly as upstream)
         self.rescale_factor = mdtile.reciprocal(self.weights)
+        if self.wrap_regions:      # the weight sum changes with the grid's shift: the region weights stay raw, the blend divides per pixel
+            return
         for bbox_id, bbox in enumerate(self.custom_bboxes):
             if bbox.blend_mode == BlendMode.BACKGROUND:
                 mdtile.rect_mul_canvas(self.custom_weights[bbox_id], self.rescale_factor, bbox.x, bbox.y, bbox.w, bbox.h)
@@ -87,7 +89,9 @@ class MixtureOfDiffusers(AbstractDiffusion):
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
-        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
+        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan; with regions only under --mdtile-wrap-regions): this
+        # step's displacement and its boxes
+        sx = sy = 0
         if self.grid_shift:
             (sx, sy), batched_bboxes = self.step_shift(self.NOISE_INVERSION_UNSHIFTED if noise_inverse_step >= 0 else None)
         if jitter is not None:
@@ -125,7 +129,7 @@ class MixtureOfDiffusers(AbstractDiffusion):
             if not self.p.disable_extra_networks:
                 with devices.autocast():
                     extra_networks.activate(self.p, bbox.extra_network_data)
-            x_tile = mdtile.gather_rect(x_in, bbox.x, bbox.y, bbox.w, bbox.h)
+            x_tile = self.gather_region(x_in, bbox)
             if noise_inverse_step < 0:
                 out = self.custom_apply_model(x_tile, t_in, c_in, bbox_id, bbox)
             else:
@@ -145,6 +149,9 @@ class MixtureOfDiffusers(AbstractDiffusion):
             return self.x_buffer
         if jitter is not None:    # every tile where its lattice box lies, the Gaussian in lattice coordinates; the step's sum and reciprocal in the kernel
             self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights())
+            return self.x_buffer
+        if self.wrap_regions:     # the grid where this step's shift puts it, then the regions where they lie on the closed canvas
+            self.x_buffer = self.blend_wrap_regions(mdtile.METHOD_MOD, tile_outs, region_outs, x_in, (sx, sy))
             return self.x_buffer
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MOD, tile_outs, N, C, sx=sx, sy=sy, tile_w=self.get_tile_weights(),

@@ -43,7 +43,7 @@ class MultiDiffusion(AbstractDiffusion):
         super().init_custom_bbox(*args)
         for bbox in self.custom_bboxes:  # a background region counts as one more uniform-weight layer
             if bbox.blend_mode == BlendMode.BACKGROUND:
-                mdtile.weight_map_add_rect(self.weights, bbox.x, bbox.y, bbox.w, bbox.h, None, 1.0)
+                self.add_region_weight(bbox, None)
 
     @torch.no_grad()
     def kdiff_forward(self, x_in: Tensor, sigma_in: Tensor, cond) -> Tensor:
@@ -125,7 +125,9 @@ class MultiDiffusion(AbstractDiffusion):
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
         plan, batched_bboxes = (self.sparse_plan, self.sparse_batched_bboxes) if skip == "sparse" else (self.plan, self.batched_bboxes)
-        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan or regions): this step's displacement and its boxes
+        # --mdtile-grid-shift (wrap-around plans only, so never with the sparse plan; with regions only under --mdtile-wrap-regions): this
+        # step's displacement and its boxes
+        sx = sy = 0
         if self.grid_shift:
             (sx, sy), batched_bboxes = self.step_shift(None if own_evaluation is None else self.NOISE_INVERSION_UNSHIFTED)
         if jitter is not None:
@@ -154,7 +156,7 @@ class MultiDiffusion(AbstractDiffusion):
             if not self.p.disable_extra_networks:
                 with devices.autocast():
                     extra_networks.activate(self.p, bbox.extra_network_data)
-            x_tile = mdtile.gather_rect(x_in, bbox.x, bbox.y, bbox.w, bbox.h)
+            x_tile = self.gather_region(x_in, bbox)
             region_outs.append(custom_func(x_tile, bbox_id, bbox).to(x_in.dtype).contiguous())
             if not self.p.disable_extra_networks:
                 with devices.autocast():
@@ -166,6 +168,9 @@ class MultiDiffusion(AbstractDiffusion):
             return self.x_buffer
         if jitter is not None:    # every tile where its lattice box lies; the step's weight sum is formed in the kernel
             self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MD, tile_outs, N, C)
+            return self.x_buffer
+        if self.wrap_regions:     # the grid where this step's shift puts it, then the regions where they lie on the closed canvas
+            self.x_buffer = self.blend_wrap_regions(mdtile.METHOD_MD, tile_outs, region_outs, x_in, (sx, sy))
             return self.x_buffer
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MD, tile_outs, N, C, sx=sx, sy=sy, weights=self.weights)

@@ -93,6 +93,20 @@ class BBox:
         return f"{type(self).__name__}(x={self.x}, y={self.y}, w={self.w}, h={self.h})"
 
 
+def region_rect(fx: float, fy: float, fw: float, fh: float, W: int, H: int, wrap_x: bool = False, wrap_y: bool = False) -> Tuple[int, int, int, int]:
+    """(x, y, w, h) in latent pixels of a region given as fractions of a W x H canvas -- the one rule for region rectangles.
+    An axis that does not wrap: the origin max(0, int(f * extent)), the size ceil(fs * extent) clipped at the edge (upstream's rule).
+    An axis that wraps (--mdtile-wrap-regions on a closed canvas): the origin int(f * extent) mod extent, the size min(extent, ceil(fs * extent));
+    the region covers the coordinates (origin + i) mod extent, i in [0, size), so origin + size may pass the extent."""
+    def axis(f0: float, fs: float, extent: int, wraps: bool) -> Tuple[int, int]:
+        if wraps:
+            return int(f0 * extent) % extent, min(extent, math.ceil(fs * extent))
+        origin = max(0, int(f0 * extent))
+        return origin, min(extent - origin, math.ceil(fs * extent))
+    (x, w), (y, h) = axis(fx, fw, W, wrap_x), axis(fy, fh, H, wrap_y)
+    return x, y, w, h
+
+
 class CustomBBox(BBox):
     """Region-prompt rectangle.  Foreground regions carry their feather mask (built on the GPU by the engine)."""
 

@@ -379,6 +379,48 @@ int mdtile_gather_all_lattice(const mdtile_lattice* lat, int dtype, int N, int C
 int mdtile_blend_lattice(const mdtile_lattice* lat, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                          mdtile_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Custom regions under the jittered grid (csrc/lattice_regions.hip).  Nothing upstream corresponds to it.  The grid is the step's
+ * lattice; the regions are ordinary rectangles on the canvas that stay where they are -- only the grid moves.  Region R covers pixel (y, x) iff
+ * R.y <= y < R.y + R.h and R.x <= x < R.x + R.w, and then reads its tensors at off = (y - R.y) * R.w + (x - R.x).  mdtile_gather_rect,
+ * mdtile_weight_map_add_rect and mdtile_region_noise serve such regions as they are.
+ *
+ * mdtile_blend_lattice_regions: lat, args, batch_out, num_batches as mdtile_blend_lattice (d_weights, d_rescale NULL; d_tile_w required for Mixture
+ *   of Diffusers; flags and the row band 0); r:
+ *     regions      list order; .out [N, C, h, w] in args->dtype; .weight [h, w] fp32: FG = the feather mask; BG + Mixture of Diffusers = the region's
+ *                  RAW Gaussian -- NOT premultiplied by a reciprocal map as mdtile_blend takes it: the reciprocal changes every step, the kernel
+ *                  multiplies by this pixel's; BG + MultiDiffusion: unused, may be NULL
+ *     d_region_w   [H, W] fp32: the BG regions' weight sum on the canvas, made once per job -- zeros, then per BG region in list order
+ *                  mdtile_weight_map_add_rect with scalar 1.0 (MultiDiffusion) or the region's Gaussian (Mixture of Diffusers); NULL iff the list
+ *                  holds no BG region (a map of zeros is accepted there too)
+ *   For canvas pixel (y, x) and plane (n, c), in fp32 without contraction (half I/O: fp32 arithmetic on the dtype-rounded inputs, rounded once at
+ *   the store):
+ *     gw   = sum of w_t over the grid tiles whose LATTICE box covers (y, x), ascending t, from +0.0: exactly mdtile_lattice_weight_map
+ *     wsum = d_region_w ? gw + d_region_w[y, x] : gw;                 MoD: resc = 1.0f / wsum (IEEE division; the lattice covers every pixel: wsum > 0)
+ *     buf  = +0.0;  the grid tiles in ascending t, the value read at the PUSHED-IN coordinates as mdtile_blend_lattice:
+ *                                                                     MD buf += v;    MoD buf += v * (tile_w[y - v_r, x - u_c] * resc)
+ *            then the BG regions covering (y, x) in list order:       MD buf += v_R;  MoD buf += v_R * (R.weight[off] * resc)
+ *     MD:    out = wsum > 1 ? buf / wsum : buf;                       MoD: out = buf
+ *     FG:    fbuf += v_R, fmask += R.weight[off], fcnt += 1 over the covering FG regions in list order; fbuf and fmask divided by fcnt where fcnt > 1;
+ *            out = out * (1 - fmask) + fbuf * fmask where fcnt > 0
+ *   Every canvas pixel is written exactly once; the part of a pushed-in tile outside its lattice box is never read.  With num_regions = 0 and
+ *   d_region_w NULL or all zeros the result is mdtile_blend_lattice's bit for bit.  At rest on a canvas with (w - tw) % st == 0 and
+ *   (h - th) % st == 0 the result equals mdtile_blend on the plain plan with the same regions (its maps made as the plain path makes them: add_grid
+ *   on zeros, add_rect per BG region, reciprocal, rect_mul_canvas on each BG Gaussian) bit for bit -- for MultiDiffusion always (the weight sums
+ *   are small integers), for Mixture of Diffusers wherever no pixel lies under two or more BG regions: there the definition gives gw + (c1 + c2)
+ *   and the plain path's running sum (gw + c1) + c2, which can differ in the last bit (the grouping of mdtile_blend_wrap_regions, for its reason).
+ * REFUSED (MDTILE_E_ARG, the text names the reason, nothing is written): everything mdtile_blend_lattice refuses; a NULL r; more than
+ *   MDTILE_MAX_REGIONS regions; a rectangle with w < 1, h < 1, x < 0, y < 0, x + w > W or y + h > H; a mode other than BG / FG; a NULL .out; a NULL
+ *   .weight on an FG region, or on a BG region with Mixture of Diffusers; a BG region together with a NULL d_region_w.
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct mdtile_lattice_regions {
+    const mdtile_region* regions;  /* list order; BG+MD: weight NULL; BG+MoD: RAW Gaussian [h,w]; FG: feather mask [h,w] */
+    int num_regions;               /* 0 .. MDTILE_MAX_REGIONS */
+    const float* d_region_w;       /* [H,W] fp32: the BG regions' weight sum on the canvas; NULL iff the list holds no BG region */
+} mdtile_lattice_regions;
+int mdtile_blend_lattice_regions(const mdtile_lattice* lat, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                                 const mdtile_lattice_regions* r, mdtile_stream_t stream);
+
 /* Per-region initial noise (scripts/tilediffusion.py:486-529, create_random_tensors_hijack): d_noise [N,C,H,W] fp32 is the job's
  * noise, updated in place.  regions[i].out = the region's own noise [1,C,h,w] fp32 (drawn by the host with the region's CPU
  * seed, shared by all N samples), .mode = MDTILE_REGION_BG / _FG, .weight unused.  Per layer: sum + hit count over the regions

@@ -1,0 +1,146 @@
+// What the kernels of the jittered grid share (lattice.hip: k_lattice_weight, k_lattice_gather, k_lattice_blend; lattice_regions.hip:
+// k_lattice_blend_regions): the axis as the kernels see it, the covering range and the weight sum of a pixel from the lattice integers, the raw
+// 4-element store, the planes-per-thread rule, and the host checks of a caller's mdtile_lattice.  Moved here from lattice.hip unchanged, and
+// still in an anonymous namespace: each file that includes this header has its own copy, as it had when lattice.hip was the only one.
+// kPlaneBlocks is not here: it stays in lattice.hip, where tests/test_gpu_lattice.py reads it, and lattice_regions.hip states the same number.
+#pragma once
+#include "launchers.h"
+
+namespace {
+
+using namespace mdt;
+
+// one axis as the kernels see it
+struct LatAxis {
+    int extent, tile;
+    int stride, off, K;       // off = s - stride in (-stride, 0]; an axis that does not move: stride 1, off 0, K 0
+};
+
+struct LatticeParams {
+    LatAxis ax, ay;
+    int cols, tile_bs, N, C;
+};
+struct LatticeBlendParams : LatticeParams {
+    const float* tile_w;      // Mixture of Diffusers: the [th, tw] Gaussian; null for MultiDiffusion
+    void* out;
+    const void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(LatticeBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+
+// floor(a / b), b > 0 (C's `/` truncates towards zero: wrong for the negative numerators left of the first stride)
+__host__ __device__ __forceinline__ int floor_div(int a, int b) {
+    const int q = a / b;
+    return a - q * b < 0 ? q - 1 : q;
+}
+__host__ __device__ __forceinline__ int lat_origin(const LatAxis& a, int k) { return a.off + k * a.stride; }
+__host__ __device__ __forceinline__ int lat_pushed(const LatAxis& a, int k) {
+    const int u = lat_origin(a, k), last = a.extent - a.tile;
+    return u < 0 ? 0 : u > last ? last : u;
+}
+// the tiles whose lattice box meets the coordinates [p_lo, p_hi] (p_lo <= p_hi, both on the canvas): lo .. hi, never empty
+struct Cover { int lo, hi; };
+__device__ __forceinline__ Cover lat_cover(const LatAxis& a, int p_lo, int p_hi) {
+    Cover c;
+    c.lo = floor_div(p_lo - a.tile - a.off, a.stride) + 1;
+    if (c.lo < 0) c.lo = 0;
+    c.hi = floor_div(p_hi - a.off, a.stride);
+    if (c.hi > a.K) c.hi = a.K;
+    return c;
+}
+
+// wsum of pixel (y, x): the candidates are the tile rows `rows` (all cover y) and the tile columns `cand` (a superset of those that cover x:
+// the columns of x's quad); ascending tile index, fp32 from +0.0
+template <bool MOD>
+__device__ __forceinline__ float lat_wsum(const LatticeParams& P, int y, int x, Cover rows, Cover cand, const float* __restrict__ tile_w) {
+    float s = 0.0f;
+    for (int r = rows.lo; r <= rows.hi; ++r) {
+        const int wy = y - lat_origin(P.ay, r);
+        for (int c = cand.lo; c <= cand.hi; ++c) {
+            const int d = x - lat_origin(P.ax, c);
+            if (d < 0 || d >= P.ax.tile) continue;
+            if (MOD) s += tile_w[wy * P.ax.tile + d];
+            else s += 1.0f;
+        }
+    }
+    return s;
+}
+
+// the storage type as an integer of its size, and 4 of them at an element-aligned address (one load / store instruction: gfx950 runs in
+// unaligned-access mode)
+template <typename T> struct RawOf { using type = unsigned short; };
+template <> struct RawOf<float> { using type = unsigned int; };
+template <typename R> struct __attribute__((packed, aligned(sizeof(R)))) raw4_u { R v[4]; };
+
+template <typename T> __device__ __forceinline__ typename RawOf<T>::type raw_bits(float v);
+template <> __device__ __forceinline__ unsigned int raw_bits<float>(float v) { return __float_as_uint(v); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__half>(float v) { return __half_as_ushort(__float2half_rn(v)); }
+template <> __device__ __forceinline__ unsigned short raw_bits<__hip_bfloat16>(float v) {
+    const __hip_bfloat16 h = __float2bfloat16(v);
+    unsigned short u;
+    __builtin_memcpy(&u, &h, sizeof(u));
+    return u;
+}
+
+// planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as the other blends are sized
+int planes_per_thread(int W, int H, int planes) {
+    const long long work = (long long)H * ((W + 3) / 4) * planes;
+    if (planes % 4 == 0 && work / 4 >= 131072) return 4;
+    return planes % 2 == 0 && work / 2 >= 131072 ? 2 : 1;
+}
+
+// ---- host integers ---------------------------------------------------------------------------------------------------------------
+// tiles of a moving axis at shift s: K + 1, K = ceil((extent - tile - (s - stride)) / stride)  (the numerator is positive: tile < extent, s <= stride)
+int axis_tiles(int extent, int tile, int stride, int s) { return (extent - tile - (s - stride) + stride - 1) / stride + 1; }
+
+LatAxis kernel_axis(int extent, int tile, int stride, int s, int count) {
+    LatAxis a;
+    a.extent = extent; a.tile = tile;
+    if (tile >= extent) { a.stride = 1; a.off = 0; a.K = 0; }
+    else { a.stride = stride; a.off = s - stride; a.K = count - 1; }
+    return a;
+}
+
+// Is *lat what mdtile_lattice_make writes?  The struct is the caller's memory: every field the kernels' addresses depend on is checked again.
+int lattice_check(const char* fn, const mdtile_lattice* l) {
+    MDT_CHECK_ARG(l, "%s: null lattice", fn);
+    MDT_CHECK_ARG(l->w > 0 && l->h > 0 && l->w <= 65535 && l->h <= 65535 && l->tile_w > 0 && l->tile_h > 0 && l->tile_w <= l->w && l->tile_h <= l->h &&
+                      l->overlap >= 0 && l->tile_bs > 0,
+                  "%s: bad lattice: canvas %dx%d, tile %dx%d, overlap %d, tile_bs %d (not from mdtile_lattice_make)", fn, l->w, l->h, l->tile_w, l->tile_h,
+                  l->overlap, l->tile_bs);
+    const int extent[2] = {l->w, l->h}, tile[2] = {l->tile_w, l->tile_h}, stride[2] = {l->stride_x, l->stride_y}, s[2] = {l->sx, l->sy},
+              count[2] = {l->cols, l->rows};
+    for (int a = 0; a < 2; ++a) {
+        const char axis = a ? 'y' : 'x';
+        if (tile[a] >= extent[a]) {
+            MDT_CHECK_ARG(count[a] == 1, "%s: bad lattice: %d tiles along %c although the tile spans the canvas", fn, count[a], axis);
+            continue;
+        }
+        MDT_CHECK_ARG(stride[a] == tile[a] - l->overlap && stride[a] > 0, "%s: bad lattice: stride_%c = %d, tile - overlap = %d", fn, axis, stride[a],
+                      tile[a] - l->overlap);
+        MDT_CHECK_ARG(s[a] >= 1 && s[a] <= stride[a], "%s: shift s%c = %d outside [1, %d] (the stride) on an axis that moves", fn, axis, s[a], stride[a]);
+        MDT_CHECK_ARG(count[a] == axis_tiles(extent[a], tile[a], stride[a], s[a]), "%s: bad lattice: %d tiles along %c, the shift gives %d", fn, count[a], axis,
+                      axis_tiles(extent[a], tile[a], stride[a], s[a]));
+    }
+    MDT_CHECK_ARG(l->cols <= 32767 && l->rows <= 32767 && l->num_tiles == l->cols * l->rows, "%s: bad lattice: %d tiles for %d x %d", fn, l->num_tiles, l->cols,
+                  l->rows);
+    MDT_CHECK_ARG(l->num_batches == (l->num_tiles + l->tile_bs - 1) / l->tile_bs && l->num_batches > 0 &&
+                      l->tile_bs == (l->num_tiles + l->num_batches - 1) / l->num_batches,
+                  "%s: bad lattice: %d batches of %d for %d tiles", fn, l->num_batches, l->tile_bs, l->num_tiles);
+    return MDTILE_OK;
+}
+
+void fill_params(LatticeParams& P, const mdtile_lattice* l, int N, int C) {
+    P.ax = kernel_axis(l->w, l->tile_w, l->stride_x, l->sx, l->cols);
+    P.ay = kernel_axis(l->h, l->tile_h, l->stride_y, l->sy, l->rows);
+    P.cols = l->cols; P.tile_bs = l->tile_bs; P.N = N; P.C = C;
+}
+
+// what both calls with batches ask of their count
+int batches_check(const char* fn, const mdtile_lattice* l, int num_batches) {
+    MDT_CHECK_ARG(num_batches == l->num_batches, "%s: %d batches given, the lattice has %d", fn, num_batches, l->num_batches);
+    MDT_CHECK_ARG(num_batches <= MDTILE_MAX_BATCHES, "%s: %d batches > MDTILE_MAX_BATCHES=%d (the lattice has no packed form: raise the tile batch size)", fn,
+                  num_batches, MDTILE_MAX_BATCHES);
+    return MDTILE_OK;
+}
+
+}  // namespace

@@ -76,6 +76,10 @@ class _Lattice(ctypes.Structure):
                                      "num_batches", "tile_bs")]
 
 
+class _LatticeRegions(ctypes.Structure):
+    _fields_ = [("regions", POINTER(_Region)), ("num_regions", c_int), ("d_region_w", c_void_p)]
+
+
 # every symbol include/mdtile.h declares: name -> (restype, argtypes)
 _IP = POINTER(c_int)
 _SIGNATURES = {
@@ -120,6 +124,7 @@ _SIGNATURES = {
     "mdtile_lattice_weight_map": (c_int, [POINTER(_Lattice), c_void_p, c_void_p, c_void_p]),
     "mdtile_gather_all_lattice": (c_int, [POINTER(_Lattice), c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
     "mdtile_blend_lattice": (c_int, [POINTER(_Lattice), POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p]),
+    "mdtile_blend_lattice_regions": (c_int, [POINTER(_Lattice), POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_LatticeRegions), c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
@@ -1061,6 +1066,33 @@ def blend_lattice(lat: Lattice, method: int, batch_out: Sequence[torch.Tensor], 
         assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
     out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
     _check(lib().mdtile_blend_lattice(lat.ref, ctypes.byref(a), ptrs, len(batch_out), _stream()), "mdtile_blend_lattice")
+    return out
+
+
+def blend_lattice_regions(lat: Lattice, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, regions: Sequence[RegionSpec] = (),
+                          region_w: Optional[torch.Tensor] = None, tile_w=None, weights=None, rescale=None, out: Optional[torch.Tensor] = None,
+                          dtype=None, device=None) -> torch.Tensor:
+    """blend_lattice WITH custom regions, one launch: the step's jittered grid, then the regions where they lie on the canvas -- only the grid
+    moves.  region_w: the background regions' weight sum [H, W] on the canvas (weight_map_add_rect on zeros in list order: 1.0 each for
+    MultiDiffusion, the raw Gaussians for Mixture of Diffusers), made once per job; None iff there is no background region.  A background
+    region's weight is its RAW Gaussian (Mixture of Diffusers): the kernel forms the step's weight sum + region_w and its reciprocal per pixel.
+    weights / rescale exist only to be refused: the library takes no total map here."""
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    if region_w is not None:
+        _dev_tensor(region_w, "region_w", torch.float32)
+        assert region_w.numel() == lat.h * lat.w, f"region_w {tuple(region_w.shape)}"
+    out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    for i, r in enumerate(regions):
+        assert tuple(r.out.shape) == (N, C, r.h, r.w), f"region[{i}] output {tuple(r.out.shape)} vs [{N}, {C}, {r.h}, {r.w}]"
+    rarr, _keep = _regions_array(regions, dtype, limit=False)
+    lr = _LatticeRegions(rarr, len(regions), _p(region_w).value)
+    _check(lib().mdtile_blend_lattice_regions(lat.ref, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(lr), _stream()),
+           "mdtile_blend_lattice_regions")
     return out
 
 

@@ -46,8 +46,16 @@ def preload(parser):
              "step, offset by a function of the job's seed and the step, tiles that would hang over an edge pushed inside, so that no tile border "
              "stays in place for two steps and small or zero overlaps become usable. The tile count may change by a column and a row between "
              "steps. The fixed grid runs instead (one line says why) on a canvas that wraps around (use --mdtile-grid-shift there), with region "
-             "control, when --mdtile-inpaint-skip skips tiles, in Noise Inversion's own evaluations, when the tile spans the canvas and beyond "
+             "control (unless --mdtile-jitter-regions is set), when --mdtile-inpaint-skip skips tiles, in Noise Inversion's own evaluations, when the tile spans the canvas and beyond "
              "320 tile batches. DemoFusion does not read it. Default: off, the grid stays where it is.")
+    parser.add_argument(
+        "--mdtile-jitter-regions", action="store_true",
+        help="Tiled Diffusion with --mdtile-grid-jitter (MultiDiffusion, Mixture of Diffusers): keep the moving grid when region prompt control "
+             "is enabled. The regions stay where they were drawn, background and foreground alike; only the tile grid of the background moves, "
+             "and each step's weight sum is formed from that step's grid plus the background regions. Without this option a job with regions "
+             "runs the fixed grid, as before. Ignored (one line) without --mdtile-grid-jitter; with no background to draw there is no grid to "
+             "move and the fixed path runs (one line). Noise Inversion's own evaluations, wrap-around canvases, --mdtile-inpaint-skip and the "
+             "multi-GPU partial path stay on the fixed grid; DemoFusion does not read it. Default: off.")
     parser.add_argument(
         "--mdtile-vae-seam-blend", type=int, default=None, metavar="PX",
         help="Tiled VAE decoder: cross-fade neighbouring tiles over PX image pixels per side of a tile border (1-88; 16-32 is a sensible range), out "

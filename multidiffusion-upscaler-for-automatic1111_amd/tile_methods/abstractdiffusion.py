@@ -108,6 +108,10 @@ class AbstractDiffusion:
         # in plan coordinates and region_w holds the background regions' weight sum on the canvas: the blend adds them per pixel, every step
         self.wrap_regions = False
         self.region_w: Optional[Tensor] = None
+        # --mdtile-jitter-regions: regions under the jittered grid (init_custom_bbox decides).  self.weights keeps the fixed grid's
+        # sum WITH the regions (Noise Inversion's own evaluations and every other fixed-grid evaluation of the job need it), region_w holds the
+        # background regions' sum alone: the lattice blend adds it to the step's grid sum per pixel
+        self.jitter_regions = False
 
         # optional extensions, armed by the init_* calls of the Script
         self.noise_inverse_enabled = False
@@ -157,7 +161,8 @@ class AbstractDiffusion:
         self.total_bboxes = 0
         if self.enable_grid_bbox:
             # --mdtile-grid-jitter: a step's lattice may have a column and a row more than the grid at rest; the bar must not overrun
-            self.total_bboxes += max(self.num_batches, self.jitter_max_batches) if self.grid_jitter and not self.enable_custom_bbox else self.num_batches
+            moves = self.grid_jitter and (not self.enable_custom_bbox or self.jitter_regions)
+            self.total_bboxes += max(self.num_batches, self.jitter_max_batches) if moves else self.num_batches
         if self.enable_custom_bbox:
             self.total_bboxes += len(self.custom_bboxes)
         assert self.total_bboxes > 0, "Nothing to paint! No background to draw and no custom bboxes were provided."
@@ -249,6 +254,11 @@ class AbstractDiffusion:
     def grid_jitter_requested() -> bool:
         """--mdtile-grid-jitter (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_grid_jitter", False))
+
+    @staticmethod
+    def jitter_regions_requested() -> bool:
+        """--mdtile-jitter-regions (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_jitter_regions", False))
 
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
@@ -358,10 +368,22 @@ class AbstractDiffusion:
             self._jitter_notes.add(reason)
             print(f"[Tiled Diffusion] --mdtile-grid-jitter not applied: {reason}; the grid stays where it is.")
 
+    NO_BACKGROUND_TO_MOVE = "--mdtile-jitter-regions has no grid to move, no background is drawn (the regions are painted where they are)"
+
+    def _jitter_regions_alone(self) -> bool:
+        """--mdtile-jitter-regions without --mdtile-grid-jitter means nothing: one line per job says so."""
+        if not self.jitter_regions_requested() or self.grid_jitter_requested():
+            return False
+        if "alone" not in self._jitter_notes:
+            self._jitter_notes.add("alone")
+            print("[Tiled Diffusion] --mdtile-jitter-regions ignored: it only acts together with --mdtile-grid-jitter; the grid stays where it is.")
+        return True
+
     def _init_grid_jitter(self):
         """What the geometry decides, once the plan is made: a canvas that wraps, no axis able to move, more batches than the lattice carries."""
         self.grid_jitter, self._lattice_at, self.jitter_max_batches = False, None, 0
         if not self.grid_jitter_requested():
+            self._jitter_regions_alone()
             return
         if self.wrap_x or self.wrap_y:
             return self._jitter_note("the canvas wraps around on an axis (--mdtile-wrap-x / --mdtile-wrap-y): use --mdtile-grid-shift there")
@@ -385,7 +407,9 @@ class AbstractDiffusion:
             return None
         if own_evaluation is not None:
             return self._jitter_note(own_evaluation)
-        if self.enable_custom_bbox or not self.draw_background:
+        if not self.jitter_regions and (self.enable_custom_bbox or not self.draw_background):
+            if self.jitter_regions_requested() and not self.draw_background:
+                return self._jitter_note(self.NO_BACKGROUND_TO_MOVE)
             return self._jitter_note("region prompt control is enabled (custom regions, or no background to draw)")
         if skip != "full":
             return self._jitter_note(f"--mdtile-inpaint-skip decided \"{skip}\" for this job (tiles are skipped on the fixed grid)")
@@ -400,6 +424,8 @@ class AbstractDiffusion:
             if getattr(self.p, "extra_generation_params", None) is None:
                 self.p.extra_generation_params = {}
             self.p.extra_generation_params["Tiled Diffusion grid jitter"] = True
+            if self.jitter_regions:
+                self.p.extra_generation_params["Tiled Diffusion jitter regions"] = True
         return self._lattice_at[1], self._lattice_at[2]
 
     # ---- --mdtile-inpaint-skip: only the tiles the job's latent mask touches ------------------------------------------------------------
@@ -490,6 +516,7 @@ class AbstractDiffusion:
         if not wrap_regions:
             self._refuse_wrap_x_with(self.REGIONS, self.WRAP_REGIONS_HINT)
         self.wrap_regions = wrap_regions
+        self.jitter_regions = False
         self.enable_custom_bbox = True
         self.causal_layers = causal_layers
         self.draw_background = draw_background
@@ -518,6 +545,15 @@ class AbstractDiffusion:
             if getattr(self.p, "extra_generation_params", None) is None:
                 self.p.extra_generation_params = {}
             self.p.extra_generation_params["Tiled Diffusion wrap regions"] = True
+        # --mdtile-jitter-regions applies when init_grid_bbox decided that this job's grid moves and there is a background to move.  Fixed-grid
+        # evaluations still happen in such a job (Noise Inversion's own, the hires pass of another size), so self.weights and the premultiplied
+        # region weights are kept as they are and region_w is built beside them
+        if self.jitter_regions_requested() and not self._jitter_regions_alone():
+            if not draw_background:
+                self._jitter_note(self.NO_BACKGROUND_TO_MOVE)
+            elif self.grid_jitter:
+                self.jitter_regions = True
+                self.region_w = torch.zeros((1, 1, self.h, self.w), device=devices.device, dtype=torch.float32)
         self._init_region_conds()
 
     def _init_region_conds(self):
@@ -540,10 +576,10 @@ class AbstractDiffusion:
             self.plan = mdtile.Plan(self.w, self.h, self.w, self.h, 0, 1, clamp=True)
         return self.plan
 
-    def region_specs(self, outs: List[Tensor]) -> List[mdtile.RegionSpec]:
-        """Pair every custom bbox with its model output for the fused blend launch."""
+    def region_specs(self, outs: List[Tensor], raw: bool = False) -> List[mdtile.RegionSpec]:
+        """Pair every custom bbox with its model output for the fused blend launch.  raw: the weights of the lattice path (region_weights)."""
         specs = []
-        for bbox, out, wgt in zip(self.custom_bboxes, outs, self.region_weights()):
+        for bbox, out, wgt in zip(self.custom_bboxes, outs, self.region_weights(raw)):
             mode = mdtile.REGION_FG if bbox.blend_mode == BlendMode.FOREGROUND else mdtile.REGION_BG
             specs.append(mdtile.RegionSpec(bbox.x, bbox.y, bbox.w, bbox.h, mode, out, wgt))
         return specs
@@ -555,11 +591,14 @@ class AbstractDiffusion:
         return mdtile.gather_rect(x_in, bbox.x, bbox.y, bbox.w, bbox.h)
 
     def add_region_weight(self, bbox: CustomBBox, rect_w: Optional[Tensor]):
-        """A background region's weight (rect_w None: 1.0) into the weight sum: self.weights, or with --mdtile-wrap-regions the canvas map region_w."""
+        """A background region's weight (rect_w None: 1.0) into the weight sum: self.weights, or with --mdtile-wrap-regions the canvas map region_w;
+        with --mdtile-jitter-regions both -- self.weights for the fixed-grid evaluations, region_w for the lattice blend."""
         if self.wrap_regions:
             mdtile.weight_map_add_rect_wrap(self.region_w, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
         else:
             mdtile.weight_map_add_rect(self.weights, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0)
+            if self.jitter_regions:
+                mdtile.weight_map_add_rect(self.region_w, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0)
 
     def blend_wrap_regions(self, method: int, tile_outs: List[Tensor], region_outs: List[Tensor], x_in: Tensor, shift) -> Tensor:
         """--mdtile-wrap-regions: grid (displaced by this step's shift) and regions in one launch; the weight sum is formed in the kernel from
@@ -570,8 +609,18 @@ class AbstractDiffusion:
                                          grid_w=self.weights if tile_outs else None, region_w=self.region_w, sx=shift[0], sy=shift[1],
                                          tile_w=tile_w, dtype=x_in.dtype, device=x_in.device)
 
-    def region_weights(self) -> List[Optional[Tensor]]:
-        """Per region: feather mask (foreground) or the method's background weight (None = 1.0)."""
+    def blend_lattice_regions(self, method: int, lattice, tile_outs: List[Tensor], region_outs: List[Tensor], x_in: Tensor) -> Tensor:
+        """--mdtile-jitter-regions: the step's lattice and the regions in one launch; the weight sum is formed in the kernel from the lattice
+        integers and region_w, and Mixture of Diffusers' region weights go in raw."""
+        N, C = x_in.shape[:2]
+        has_bg = any(b.blend_mode != BlendMode.FOREGROUND for b in self.custom_bboxes)
+        return mdtile.blend_lattice_regions(lattice, method, tile_outs, N, C, regions=self.region_specs(region_outs, raw=True),
+                                            region_w=self.region_w if has_bg else None,
+                                            tile_w=self.get_tile_weights() if method == mdtile.METHOD_MOD else None)
+
+    def region_weights(self, raw: bool = False) -> List[Optional[Tensor]]:
+        """Per region: feather mask (foreground) or the method's background weight (None = 1.0).  raw: what the lattice path takes
+        (--mdtile-jitter-regions) -- the same here, MultiDiffusion's background weight is the scalar 1.0 either way."""
         return [b.feather_mask if b.blend_mode == BlendMode.FOREGROUND else None for b in self.custom_bboxes]
 
     # ---- region-prompt forwards (upstream :232-451) --------------------------------------------------------------------

@@ -27,6 +27,7 @@ class MixtureOfDiffusers(AbstractDiffusion):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.custom_weights: List[Optional[Tensor]] = []   # per region: Gaussian [1,1,h,w] (background) or None
+        self.raw_custom_weights: List[Optional[Tensor]] = []   # --mdtile-jitter-regions: the same Gaussians, never premultiplied (the lattice path)
         self.get_weight = gaussian_weights
         self.rescale_factor: Optional[Tensor] = None
 
@@ -55,8 +56,10 @@ class MixtureOfDiffusers(AbstractDiffusion):
                 cw = self.get_weight(bbox.w, bbox.h)
                 self.add_region_weight(bbox, cw)
                 self.custom_weights.append(cw.unsqueeze(0).unsqueeze(0))
+                self.raw_custom_weights.append(cw.clone().unsqueeze(0).unsqueeze(0) if self.jitter_regions else None)
             else:
                 self.custom_weights.append(None)
+                self.raw_custom_weights.append(None)
 
     def init_done(self):
         super().init_done()
@@ -68,9 +71,10 @@ class MixtureOfDiffusers(AbstractDiffusion):
             if bbox.blend_mode == BlendMode.BACKGROUND:
                 mdtile.rect_mul_canvas(self.custom_weights[bbox_id], self.rescale_factor, bbox.x, bbox.y, bbox.w, bbox.h)
 
-    def region_weights(self):
-        return [b.feather_mask if b.blend_mode == BlendMode.FOREGROUND else self.custom_weights[i]
-                for i, b in enumerate(self.custom_bboxes)]
+    def region_weights(self, raw: bool = False):
+        """raw: the Gaussians as they were made, for the lattice path (--mdtile-jitter-regions); else premultiplied by rescale_factor (init_done)."""
+        bg = self.raw_custom_weights if raw else self.custom_weights
+        return [b.feather_mask if b.blend_mode == BlendMode.FOREGROUND else bg[i] for i, b in enumerate(self.custom_bboxes)]
 
     # ---- the hot path ----------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -84,7 +88,8 @@ class MixtureOfDiffusers(AbstractDiffusion):
 
         # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
         skip = self.inpaint_skip(self.NOISE_INVERSION_FULL if noise_inverse_step >= 0 else None)
-        # --mdtile-grid-jitter (plain grids only, never with the sparse plan or regions): this step's lattice and its pushed-in boxes, or None
+        # --mdtile-grid-jitter (plain grids only, never with the sparse plan; with regions only under --mdtile-jitter-regions): this step's lattice
+        # and its pushed-in boxes, or None
         jitter = self.step_lattice(self.NOISE_INVERSION_UNJITTERED if noise_inverse_step >= 0 else None, skip)
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
@@ -148,7 +153,10 @@ class MixtureOfDiffusers(AbstractDiffusion):
                                                 rescale=self.rescale_factor)
             return self.x_buffer
         if jitter is not None:    # every tile where its lattice box lies, the Gaussian in lattice coordinates; the step's sum and reciprocal in the kernel
-            self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights())
+            if self.jitter_regions:      # then the regions, where they are, their Gaussians raw: only the grid moves
+                self.x_buffer = self.blend_lattice_regions(mdtile.METHOD_MOD, lattice, tile_outs, region_outs, x_in)
+            else:
+                self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights())
             return self.x_buffer
         if self.wrap_regions:     # the grid where this step's shift puts it, then the regions where they lie on the closed canvas
             self.x_buffer = self.blend_wrap_regions(mdtile.METHOD_MOD, tile_outs, region_outs, x_in, (sx, sy))

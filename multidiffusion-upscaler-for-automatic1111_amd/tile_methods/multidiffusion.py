@@ -120,7 +120,8 @@ class MultiDiffusion(AbstractDiffusion):
 
         # --mdtile-inpaint-skip: only the tiles the job's mask touches run (the sparse plan); the host discards the result everywhere else
         skip = self.inpaint_skip(own_evaluation)
-        # --mdtile-grid-jitter (plain grids only, never with the sparse plan or regions): this step's lattice and its pushed-in boxes, or None
+        # --mdtile-grid-jitter (plain grids only, never with the sparse plan; with regions only under --mdtile-jitter-regions): this step's lattice
+        # and its pushed-in boxes, or None
         jitter = self.step_lattice(None if own_evaluation is None else self.NOISE_INVERSION_UNJITTERED, skip)
         if skip == "empty":
             return x_in.clone()      # a fresh tensor, as every other path returns: the caller may work on the result in place
@@ -167,7 +168,10 @@ class MultiDiffusion(AbstractDiffusion):
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in, weights=self.weights)
             return self.x_buffer
         if jitter is not None:    # every tile where its lattice box lies; the step's weight sum is formed in the kernel
-            self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MD, tile_outs, N, C)
+            if self.jitter_regions:      # then the regions, where they are: only the grid moves
+                self.x_buffer = self.blend_lattice_regions(mdtile.METHOD_MD, lattice, tile_outs, region_outs, x_in)
+            else:
+                self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MD, tile_outs, N, C)
             return self.x_buffer
         if self.wrap_regions:     # the grid where this step's shift puts it, then the regions where they lie on the closed canvas
             self.x_buffer = self.blend_wrap_regions(mdtile.METHOD_MD, tile_outs, region_outs, x_in, (sx, sy))

@@ -243,7 +243,7 @@ int mdtile_blend_finalize(const mdtile_plan* plan, const mdtile_blend_args* args
                           const mdtile_region* regions, int num_regions, mdtile_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------------------
- * Custom regions on a wrap-around canvas (csrc/wrap_regions.hip).  Nothing upstream corresponds to it.  A rectangle (x, y, w, h)
+ * Custom regions on a wrap-around canvas (csrc/wrap_regions.hip, the blend kernel in csrc/wrap.hip).  Nothing upstream corresponds to it.  A rectangle (x, y, w, h)
  * on a canvas W x H with flags (wrap_x, wrap_y) covers the canvas pixels ((y + i) mod H, (x + j) mod W), i in [0, h), j in [0, w); it has ONE
  * origin and one dense [h, w] (or [N, C, h, w]) tensor whether or not it crosses a seam.  Valid iff 0 <= x < W, 0 <= y < H, 0 < w <= W,
  * 0 < h <= H, and x + w <= W unless wrap_x, y + h <= H unless wrap_y.  Canvas pixel (yc, xc) is covered iff ry = (yc - y) mod H < h and
@@ -380,7 +380,7 @@ int mdtile_blend_lattice(const mdtile_lattice* lat, const mdtile_blend_args* arg
                          mdtile_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------------------
- * Custom regions under the jittered grid (csrc/lattice_regions.hip).  Nothing upstream corresponds to it.  The grid is the step's
+ * Custom regions under the jittered grid (csrc/lattice.hip).  Nothing upstream corresponds to it.  The grid is the step's
  * lattice; the regions are ordinary rectangles on the canvas that stay where they are -- only the grid moves.  Region R covers pixel (y, x) iff
  * R.y <= y < R.y + R.h and R.x <= x < R.x + R.w, and then reads its tensors at off = (y - R.y) * R.w + (x - R.x).  mdtile_gather_rect,
  * mdtile_weight_map_add_rect and mdtile_region_noise serve such regions as they are.

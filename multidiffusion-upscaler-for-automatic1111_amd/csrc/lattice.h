@@ -1,10 +1,9 @@
-// What the kernels of the jittered grid share (lattice.hip: k_lattice_weight, k_lattice_gather, k_lattice_blend; lattice_regions.hip:
-// k_lattice_blend_regions): the axis as the kernels see it, the covering range and the weight sum of a pixel from the lattice integers, the raw
-// 4-element store, the planes-per-thread rule, and the host checks of a caller's mdtile_lattice.  Moved here from lattice.hip unchanged, and
-// still in an anonymous namespace: each file that includes this header has its own copy, as it had when lattice.hip was the only one.
-// kPlaneBlocks is not here: it stays in lattice.hip, where tests/test_gpu_lattice.py reads it, and lattice_regions.hip states the same number.
+// What the kernels of the jittered grid (lattice.hip: k_lattice_weight, k_lattice_gather, k_lattice_blend) are written on: the axis as the kernels
+// see it, their argument blocks, the covering range and the weight sum of a pixel from the lattice integers, and the host checks of a caller's
+// mdtile_lattice.  The raw 4-element store and the planes-per-thread rule are walk.h's.
 #pragma once
 #include "launchers.h"
+#include "walk.h"
 
 namespace {
 
@@ -26,6 +25,13 @@ struct LatticeBlendParams : LatticeParams {
     const void* batch[MDTILE_MAX_BATCHES];
 };
 static_assert(sizeof(LatticeBlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// with custom regions (mdtile_blend_lattice_regions)
+struct LatticeRegionsParams : LatticeBlendParams {
+    int num_regions, num_fg;
+    const float* region_w;    // [H, W] on the canvas; null iff the list holds no background region
+    mdtile_region regions[MDTILE_MAX_REGIONS];
+};
+static_assert(sizeof(LatticeRegionsParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
 // floor(a / b), b > 0 (C's `/` truncates towards zero: wrong for the negative numerators left of the first stride)
 __host__ __device__ __forceinline__ int floor_div(int a, int b) {
@@ -63,29 +69,6 @@ __device__ __forceinline__ float lat_wsum(const LatticeParams& P, int y, int x, 
         }
     }
     return s;
-}
-
-// the storage type as an integer of its size, and 4 of them at an element-aligned address (one load / store instruction: gfx950 runs in
-// unaligned-access mode)
-template <typename T> struct RawOf { using type = unsigned short; };
-template <> struct RawOf<float> { using type = unsigned int; };
-template <typename R> struct __attribute__((packed, aligned(sizeof(R)))) raw4_u { R v[4]; };
-
-template <typename T> __device__ __forceinline__ typename RawOf<T>::type raw_bits(float v);
-template <> __device__ __forceinline__ unsigned int raw_bits<float>(float v) { return __float_as_uint(v); }
-template <> __device__ __forceinline__ unsigned short raw_bits<__half>(float v) { return __half_as_ushort(__float2half_rn(v)); }
-template <> __device__ __forceinline__ unsigned short raw_bits<__hip_bfloat16>(float v) {
-    const __hip_bfloat16 h = __float2bfloat16(v);
-    unsigned short u;
-    __builtin_memcpy(&u, &h, sizeof(u));
-    return u;
-}
-
-// planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as the other blends are sized
-int planes_per_thread(int W, int H, int planes) {
-    const long long work = (long long)H * ((W + 3) / 4) * planes;
-    if (planes % 4 == 0 && work / 4 >= 131072) return 4;
-    return planes % 2 == 0 && work / 2 >= 131072 ? 2 : 1;
 }
 
 // ---- host integers ---------------------------------------------------------------------------------------------------------------

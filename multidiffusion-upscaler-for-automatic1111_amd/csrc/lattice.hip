@@ -1,4 +1,5 @@
-// The jittered tile grid on a plain (bounded) canvas: mdtile_lattice_* , mdtile_gather_all_lattice, mdtile_blend_lattice.
+// The jittered tile grid on a plain (bounded) canvas: mdtile_lattice_* , mdtile_gather_all_lattice, mdtile_blend_lattice, and
+// region prompt control under it: mdtile_blend_lattice_regions.
 //
 // Per axis (x shown; y likewise with th, H, sy): stride st = tw - ov, shift s in [1, st], off = s - st in (-st, 0].
 //     u_k  = off + k st,  k = 0 .. K          the LATTICE origins (u_0 <= 0);  K = max(0, ceil((W - tw - off) / st)) = first k with u_k + tw >= W
@@ -18,6 +19,17 @@
 //     MD : buf += v;                                          out = wsum > 1 ? buf / wsum : buf
 //     MoD: buf += v * (tile_w[y - v_r, x - u_c] * (1.0f / wsum))
 // with v the tile's value at the PUSHED-IN coordinates (y - y'_r, x - x'_c).  All fp32 arithmetic is written on scalars.
+//
+// WITH REGIONS (k_lattice_blend<..., REGIONS = true>; the other instantiations hold none of it) the regions are ordinary rectangles that stay where
+// the user put them on the canvas.  The weight sum of a pixel is another one every step -- the set of covering tiles moves, the regions do not --
+// so it is formed per pixel:
+//     gw   = lat_wsum(...)                         exactly what mdtile_lattice_weight_map writes and the kernel without regions divides by
+//     wsum = region_w ? gw + region_w[y, x] : gw   region_w: the background regions' weight sum on the canvas, made once per job
+//     Mixture of Diffusers: rinv = 1.0f / wsum     IEEE division; the lattice covers every pixel, so wsum > 0
+// Region weights arrive RAW and are multiplied by rinv here -- mdtile_blend takes them premultiplied by its per-job reciprocal map, which cannot
+// hold when the reciprocal changes every step (the same convention, for the same reason, as mdtile_blend_wrap_regions, wrap.hip).
+// Order: the grid tiles as above, then the background regions in list order, the MultiDiffusion division, then the foreground composite over the
+// foreground regions in list order (blend_tail's arithmetic, blend.hip).  One thread writes each canvas pixel once; no LDS, no atomics.
 #include "launchers.h"
 #include "lattice.h"
 
@@ -77,9 +89,11 @@ __global__ __launch_bounds__(256) void k_lattice_gather(const LatticeGatherParam
 // tile's CONTRIBUTING row segment (lattice-relative columns d0 .. d0 + 3 all in [0, tw)) -- one element-aligned vector load per plane (load4:
 // 16 bytes of fp32, 8 of a 16-bit type, at any alignment) -- or it is cut by a lattice border / the canvas edge: per-element loads of the covered
 // pixels only.  The part of a pushed-in tile outside its lattice box is never read.
-template <typename T, int METHOD, int PP>
-__global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams P) {
-    using R = typename RawOf<T>::type;
+// REGIONS: region_w is added to the four weight sums in front of the plane walk, and the region tail runs behind the tile walk, per element at
+// plain canvas coordinates.
+template <typename T, int METHOD, int PP, bool REGIONS = false>
+__global__ __launch_bounds__(256) void k_lattice_blend(const std::conditional_t<REGIONS, LatticeRegionsParams, LatticeBlendParams> P) {
+    using Raw = typename RawOf<T>::type;
     const int W = P.ax.extent, H = P.ay.extent, tw = P.ax.tile, th = P.ay.tile;
     const int W4 = (W + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -90,11 +104,14 @@ __global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams 
     const size_t tile_elems = (size_t)th * tw;
 
     const Cover rows = lat_cover(P.ay, y, y), cand = lat_cover(P.ax, x0, x0 + nvalid - 1);
-    float wsum[4] = {0.f, 0.f, 0.f, 0.f}, rinv[4] = {0.f, 0.f, 0.f, 0.f};
+    float wsum[4] = {0.f, 0.f, 0.f, 0.f}, rinv[4] = {0.f, 0.f, 0.f, 0.f};      // pixels past the canvas (j >= nvalid) keep 0 and are never used
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (j >= nvalid) continue;
         wsum[j] = lat_wsum<METHOD == MDTILE_METHOD_MOD>(P, y, x0 + j, rows, cand, P.tile_w);
+        if constexpr (REGIONS) {
+            if (P.region_w) wsum[j] = wsum[j] + P.region_w[(size_t)y * W + x0 + j];
+        }
         if (METHOD == MDTILE_METHOD_MOD) rinv[j] = 1.0f / wsum[j];      // IEEE division, as mdtile_reciprocal
     }
 
@@ -150,6 +167,33 @@ __global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams 
             }
         }
 
+        // background regions, in list order, after every grid tile; Mixture of Diffusers: the region's RAW weight times this pixel's reciprocal
+        if constexpr (REGIONS) {
+            for (int k = 0; k < P.num_regions; ++k) {
+                const mdtile_region& R = P.regions[k];
+                if (R.mode != MDTILE_REGION_BG) continue;
+                const int ry = y - R.y;
+                if (ry < 0 || ry >= R.h) continue;
+                const size_t rplane = (size_t)R.h * R.w;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int rx = x0 + j - R.x;
+                    if (j >= nvalid || rx < 0 || rx >= R.w) continue;
+                    const size_t off = (size_t)ry * R.w + rx;
+                    const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
+                    float wgt = 1.0f;
+                    if (METHOD == MDTILE_METHOD_MOD) wgt = R.weight[off] * rinv[j];
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) {
+                        const float v = to_f32<T>(src[(size_t)pp * rplane]);
+                        if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
+                        else acc[pp][j] += v;
+                    }
+                }
+            }
+        }
+
+        // MD normalisation: x = wsum > 1 ? buf / wsum : buf
         if (METHOD == MDTILE_METHOD_MD) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -160,14 +204,49 @@ __global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams 
             }
         }
 
+        // foreground feather composite: blend_tail's (blend.hip)
+        if constexpr (REGIONS) {
+            if (P.num_fg > 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j >= nvalid) continue;
+                    float fbuf[PP], fmask = 0.0f, fcnt = 0.0f;
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) fbuf[pp] = 0.0f;
+                    for (int k = 0; k < P.num_regions; ++k) {
+                        const mdtile_region& R = P.regions[k];
+                        if (R.mode != MDTILE_REGION_FG) continue;
+                        const int ry = y - R.y, rx = x0 + j - R.x;
+                        if (ry < 0 || ry >= R.h || rx < 0 || rx >= R.w) continue;
+                        const size_t rplane = (size_t)R.h * R.w, off = (size_t)ry * R.w + rx;
+                        const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
+#pragma unroll
+                        for (int pp = 0; pp < PP; ++pp) fbuf[pp] += to_f32<T>(src[(size_t)pp * rplane]);
+                        fmask += R.weight[off];
+                        fcnt += 1.0f;
+                    }
+                    if (fcnt > 0.0f) {
+                        if (fcnt > 1.0f) fmask = fmask / fcnt;
+#pragma unroll
+                        for (int pp = 0; pp < PP; ++pp) {
+                            float fb = fbuf[pp];
+                            if (fcnt > 1.0f) fb = fb / fcnt;
+                            acc[pp][j] = acc[pp][j] * (1.0f - fmask) + fb * fmask;
+                        }
+                    }
+                }
+            }
+        }
+
+        // one element-aligned group of four, or the row end's elements
 #pragma unroll
         for (int pp = 0; pp < PP; ++pp) {
-            R* dst = reinterpret_cast<R*>(P.out) + ((size_t)(p0 + pp) * H + y) * W + x0;
+            Raw* dst = reinterpret_cast<Raw*>(P.out) + ((size_t)(p0 + pp) * H + y) * W + x0;
             if (nvalid == 4) {
-                raw4_u<R> o;
+                raw4_u<Raw> o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o.v[j] = raw_bits<T>(acc[pp][j]);
-                *reinterpret_cast<raw4_u<R>*>(dst) = o;
+                *reinterpret_cast<raw4_u<Raw>*>(dst) = o;
             } else {
                 for (int j = 0; j < nvalid; ++j) dst[j] = raw_bits<T>(acc[pp][j]);
             }
@@ -175,19 +254,46 @@ __global__ __launch_bounds__(256) void k_lattice_blend(const LatticeBlendParams 
     }
 }
 
-using LatticeBlendKernel = void (*)(const LatticeBlendParams);
-template <typename T, int PP>
-LatticeBlendKernel lattice_blend_kernel(int method) {
-    return method == MDTILE_METHOD_MD ? k_lattice_blend<T, MDTILE_METHOD_MD, PP> : k_lattice_blend<T, MDTILE_METHOD_MOD, PP>;
+template <bool REGIONS> using LatticeBlendArgs = std::conditional_t<REGIONS, LatticeRegionsParams, LatticeBlendParams>;
+
+template <typename T, int PP, bool REGIONS>
+auto lattice_blend_kernel(int method) {
+    return method == MDTILE_METHOD_MD ? k_lattice_blend<T, MDTILE_METHOD_MD, PP, REGIONS> : k_lattice_blend<T, MDTILE_METHOD_MOD, PP, REGIONS>;
 }
 
-template <typename T>
-void launch_lattice_blend(const LatticeBlendParams& P, int method, hipStream_t s) {
+// PP is sized for the walk alone; whether another size pays with the region tail behind it is not measured
+template <typename T, bool REGIONS>
+void launch_lattice_blend(const LatticeBlendArgs<REGIONS>& P, int method, hipStream_t s) {
     const int W = P.ax.extent, H = P.ay.extent, planes = P.N * P.C;
     const int pp = planes_per_thread(W, H, planes);
-    const LatticeBlendKernel k = pp == 4 ? lattice_blend_kernel<T, 4>(method) : pp == 2 ? lattice_blend_kernel<T, 2>(method) : lattice_blend_kernel<T, 1>(method);
+    const auto k = pp == 4 ? lattice_blend_kernel<T, 4, REGIONS>(method) : pp == 2 ? lattice_blend_kernel<T, 2, REGIONS>(method) : lattice_blend_kernel<T, 1, REGIONS>(method);
     const int gy = planes / pp < kPlaneBlocks ? planes / pp : kPlaneBlocks;
     hipLaunchKernelGGL(k, dim3(cdiv((long long)H * ((W + 3) / 4), 256), gy), dim3(256), 0, s, P);
+}
+
+// What mdtile_blend_lattice and mdtile_blend_lattice_regions ask of the arguments they share, and the (zeroed) argument block filled from them;
+// errors name `fn`
+int lattice_blend_args(const char* fn, const mdtile_lattice* lat, const mdtile_blend_args* a, const void* const* batch_out, int num_batches,
+                       LatticeBlendParams& P) {
+    if (int rc = lattice_check(fn, lat)) return rc;
+    MDT_CHECK_ARG(a && batch_out, "%s: null argument", fn);
+    // what this form does not do, by name (DESIGN.md 3.18)
+    MDT_CHECK_ARG(a->flags == 0, "%s: the lattice takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", fn, a->flags);
+    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "%s: the lattice takes no row band [%d,%d): it is not combined with the multi-GPU path", fn, a->row_lo,
+                  a->row_hi);
+    MDT_CHECK_ARG(!a->d_weights && !a->d_rescale, "%s: d_weights and d_rescale must be NULL: the kernel forms the weight sum of the step's grid itself", fn);
+    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "%s: bad N=%d C=%d", fn, a->N, a->C);
+    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "%s: bad method %d", fn, a->method);
+    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "%s: bad dtype %d", fn, a->dtype);
+    MDT_CHECK_ARG(a->d_x_out, "%s: null output", fn);
+    MDT_CHECK_ARG(a->method != MDTILE_METHOD_MOD || a->d_tile_w, "%s: Mixture of Diffusers needs d_tile_w", fn);
+    if (int rc = batches_check(fn, lat, num_batches)) return rc;
+    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "%s: null batch pointer %d", fn, b);
+    fill_params(P, lat, a->N, a->C);
+    P.tile_w = a->method == MDTILE_METHOD_MOD ? a->d_tile_w : nullptr;
+    P.out = a->d_x_out;
+    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
+    return MDTILE_OK;
 }
 
 }  // namespace
@@ -268,28 +374,41 @@ extern "C" int mdtile_gather_all_lattice(const mdtile_lattice* lat, int dtype, i
 
 extern "C" int mdtile_blend_lattice(const mdtile_lattice* lat, const mdtile_blend_args* a, const void* const* batch_out, int num_batches,
                                     mdtile_stream_t stream) {
-    const char* fn = "mdtile_blend_lattice";
-    if (int rc = lattice_check(fn, lat)) return rc;
-    MDT_CHECK_ARG(a && batch_out, "%s: null argument", fn);
-    // what this form does not do, by name (DESIGN.md 3.18)
-    MDT_CHECK_ARG(a->flags == 0, "%s: the lattice takes no MDTILE_BLEND_* flags (flags=%d): no partial sums, tile range or packed buffer", fn, a->flags);
-    MDT_CHECK_ARG(a->row_lo == 0 && a->row_hi == 0, "%s: the lattice takes no row band [%d,%d): it is not combined with the multi-GPU path", fn, a->row_lo,
-                  a->row_hi);
-    MDT_CHECK_ARG(!a->d_weights && !a->d_rescale, "%s: d_weights and d_rescale must be NULL: the kernel forms the weight sum of the step's grid itself", fn);
-    MDT_CHECK_ARG(a->N > 0 && a->C > 0 && a->N * a->C <= 65535, "%s: bad N=%d C=%d", fn, a->N, a->C);
-    MDT_CHECK_ARG(a->method == MDTILE_METHOD_MD || a->method == MDTILE_METHOD_MOD, "%s: bad method %d", fn, a->method);
-    MDT_CHECK_ARG(a->dtype >= 0 && a->dtype <= 2, "%s: bad dtype %d", fn, a->dtype);
-    MDT_CHECK_ARG(a->d_x_out, "%s: null output", fn);
-    MDT_CHECK_ARG(a->method != MDTILE_METHOD_MOD || a->d_tile_w, "%s: Mixture of Diffusers needs d_tile_w", fn);
-    if (int rc = batches_check(fn, lat, num_batches)) return rc;
-    for (int b = 0; b < num_batches; ++b) MDT_CHECK_ARG(batch_out[b], "%s: null batch pointer %d", fn, b);
     LatticeBlendParams P;
     memset(&P, 0, sizeof(P));
-    fill_params(P, lat, a->N, a->C);
-    P.tile_w = a->method == MDTILE_METHOD_MOD ? a->d_tile_w : nullptr;
-    P.out = a->d_x_out;
-    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
-    with_dtype(a->dtype, [&](auto* tag) { launch_lattice_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, as_stream(stream)); });
+    if (int rc = lattice_blend_args("mdtile_blend_lattice", lat, a, batch_out, num_batches, P)) return rc;
+    with_dtype(a->dtype, [&](auto* tag) { launch_lattice_blend<std::remove_pointer_t<decltype(tag)>, false>(P, a->method, as_stream(stream)); });
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+extern "C" int mdtile_blend_lattice_regions(const mdtile_lattice* lat, const mdtile_blend_args* a, const void* const* batch_out, int num_batches,
+                                            const mdtile_lattice_regions* r, mdtile_stream_t stream) {
+    const char* fn = "mdtile_blend_lattice_regions";
+    LatticeRegionsParams P;
+    memset(&P, 0, sizeof(P));
+    if (int rc = lattice_blend_args(fn, lat, a, batch_out, num_batches, P)) return rc;
+    MDT_CHECK_ARG(r, "%s: null regions block (mdtile_blend_lattice is the call without regions)", fn);
+    MDT_CHECK_ARG(r->num_regions >= 0 && r->num_regions <= MDTILE_MAX_REGIONS, "%s: %d regions (max %d)", fn, r->num_regions, MDTILE_MAX_REGIONS);
+    MDT_CHECK_ARG(r->num_regions == 0 || r->regions, "%s: null regions", fn);
+    int num_fg = 0, num_bg = 0;
+    for (int k = 0; k < r->num_regions; ++k) {
+        const mdtile_region& R = r->regions[k];
+        // the kernel reads R.out / R.weight at (y - R.y) * R.w + (x - R.x) for the canvas pixels inside the rectangle: it must lie on the canvas
+        MDT_CHECK_ARG(R.w >= 1 && R.h >= 1 && R.x >= 0 && R.y >= 0 && R.w <= lat->w - R.x && R.h <= lat->h - R.y,
+                      "%s: region %d (%d,%d,%d,%d) does not lie on the %dx%d canvas: w >= 1, h >= 1, x >= 0, y >= 0, x + w <= W, y + h <= H", fn, k, R.x, R.y,
+                      R.w, R.h, lat->w, lat->h);
+        MDT_CHECK_ARG(R.mode == MDTILE_REGION_BG || R.mode == MDTILE_REGION_FG, "%s: region %d bad mode %d", fn, k, R.mode);
+        MDT_CHECK_ARG(R.out, "%s: region %d has no output", fn, k);
+        if (R.mode == MDTILE_REGION_FG) MDT_CHECK_ARG(R.weight, "%s: region %d (foreground) needs its feather mask", fn, k);
+        else if (a->method == MDTILE_METHOD_MOD) MDT_CHECK_ARG(R.weight, "%s: region %d (background, Mixture of Diffusers) needs its raw Gaussian weight", fn, k);
+        num_fg += R.mode == MDTILE_REGION_FG;
+        num_bg += R.mode == MDTILE_REGION_BG;
+    }
+    MDT_CHECK_ARG(num_bg == 0 || r->d_region_w, "%s: null d_region_w with %d background region(s): their weight sum on the canvas is required", fn, num_bg);
+    P.num_regions = r->num_regions; P.num_fg = num_fg; P.region_w = r->d_region_w;
+    for (int k = 0; k < r->num_regions; ++k) P.regions[k] = r->regions[k];
+    with_dtype(a->dtype, [&](auto* tag) { launch_lattice_blend<std::remove_pointer_t<decltype(tag)>, true>(P, a->method, as_stream(stream)); });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

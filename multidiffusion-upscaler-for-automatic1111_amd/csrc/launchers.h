@@ -20,6 +20,10 @@ int walk_gather(const struct ::mdtile_plan* plan, int dtype, int N, int C, const
                 hipStream_t s, const int* shift = nullptr);
 int walk_blend(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                int num_regions, const void* d_fill, hipStream_t s, const int* shift = nullptr);
+// the blend with custom regions on a wrap-around plan: mdtile_blend_wrap_regions (wrap_regions.hip) has checked the arguments and counted the
+// foreground regions
+int walk_blend_regions(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                       const ::mdtile_wrap_regions* wr, int num_fg, hipStream_t s);
 // what every shifted entry point (wrap.hip, wrap_regions.hip) asks of the plan and the shift before anything else is looked at; errors name `fn`
 int shift_check(const char* fn, const struct ::mdtile_plan* plan, int sx, int sy);
 

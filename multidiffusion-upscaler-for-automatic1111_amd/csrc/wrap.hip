@@ -23,9 +23,18 @@
 // source coordinate, the blend keeps its threads on PLAN coordinates and adds it to the store address.  Both are compiled under
 // `if constexpr (SHIFT)` into instantiations of their own, with an argument block of their own; the others hold none of it.
 //
-// CUSTOM REGIONS on a wrap-around plan (mdtile_blend_wrap_regions and the three rect calls) are in wrap_regions.hip: a blend
-// kernel of its own that walks the grid as k_walk_blend does and then runs the region tail at the quad's CANVAS coordinates.  The kernels here
-// hold none of it, and mdtile_blend / mdtile_blend_shift still refuse regions on such a plan.  walk.h has what both files share.
+// CUSTOM REGIONS on a wrap-around plan (mdtile_blend_wrap_regions; wrap_regions.hip has the entry point and the three rect calls)
+// are k_walk_blend<..., REGIONS = true>: the walk of the shifted grid on the thread's quad of PLAN coordinates, then the region tail of blend_tail
+// (blend.hip) at the quad's CANVAS coordinates.  The other instantiations hold none of it, and mdtile_blend / mdtile_blend_shift still refuse
+// regions on such a plan.  A region R covers canvas pixel (yc, xc) iff ry = rel(yc, R.y, H) < R.h and rx = rel(xc, R.x, W) < R.w; its value and
+// weight are read at ry * R.w + rx.  The host has checked 0 <= R.x < W, 0 < R.w <= W (likewise y) and that a region passes an edge only on an axis
+// that wraps, so on an axis that does not wrap rel() of a pixel in front of the region is >= extent - R.x >= R.w: not covered, with the same
+// arithmetic.  The weight sum is formed in the kernel, per pixel: the grid's map travels with the shift (plan coordinates), the background
+// regions' map stays on the canvas, so their sum is another one every step and nothing made once per job holds it:
+//     wsum = grid_w[yp, xp] + region_w[yc, xc];   Mixture of Diffusers: resc = 1.0f / wsum   (IEEE division, as mdtile_reciprocal and k_lattice_blend)
+// Region weights arrive RAW and are multiplied by resc here -- mdtile_blend takes them premultiplied by its per-job reciprocal map.  Order: the
+// grid tiles as above, then the background regions in list order, the MultiDiffusion division, then the foreground composite over the foreground
+// regions in list order.  One thread writes each canvas pixel once; no LDS, no atomics.
 //
 // Not here (refused with an error that names the reason): custom regions through mdtile_blend / mdtile_blend_shift, MDTILE_BLEND_* flags, row
 // bands, mdtile_gather_range, mdtile_blend_finalize -- tile skipping is not combined with regions, and neither wrap-around nor tile skipping
@@ -134,6 +143,24 @@ struct WalkBlendShiftParams : WalkBlendParams {
     int shift_x, shift_y;     // 0 <= shift_x < W, 0 <= shift_y < H; 0 on an axis that does not wrap
 };
 static_assert(sizeof(WalkBlendShiftParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// the shifted grid with custom regions (mdtile_blend_wrap_regions): an argument block of its own
+struct WrapRegionsParams {
+    int W, H, tw, th, cols, rows, tile_bs, N, C;
+    int num_batches;          // 0: no grid is drawn (grid_w null), only regions
+    int num_regions, num_fg;
+    int shift_x, shift_y;     // 0 <= shift_x < W, 0 <= shift_y < H; 0 on an axis that does not wrap
+    const int *xs, *ys;
+    const int4 *colquad, *rowinfo;
+    const float* grid_w;      // [H, W] in PLAN coordinates
+    const float* region_w;    // [H, W] in CANVAS coordinates
+    const float* tile_w;
+    void* out;
+    mdtile_region regions[MDTILE_MAX_REGIONS];
+    const void* batch[MDTILE_MAX_BATCHES];
+};
+static_assert(sizeof(WrapRegionsParams) <= 4096, "kernel argument block must stay under 4 KiB");
+template <bool SHIFT, bool REGIONS>
+using WalkBlendArgs = std::conditional_t<REGIONS, WrapRegionsParams, std::conditional_t<SHIFT, WalkBlendShiftParams, WalkBlendParams>>;
 
 // One thread owns one quad (4 consecutive canvas columns of one row; rows start at x = 0, so a quad never straddles the seam) for PP planes.
 // The tile rows that cover the canvas row come from rowinfo[y].x and the tile columns that cover ANY pixel of the quad from colquad[xq].x, both
@@ -153,9 +180,14 @@ static_assert(sizeof(WalkBlendShiftParams) <= 4096, "kernel argument block must 
 // rescale loads and the tile loads are those above -- and only its store moves: to row (y + shift_y) mod H, columns (x0 + shift_x + j) mod W.
 // The displaced quad is in general not aligned and, on a wrapped x, may be cut by the seam: one element-aligned group of four when it is not
 // cut, per element with the column taken mod W when it is.
-template <typename T, int METHOD, int PP, bool SPARSE, bool SHIFT>
-__global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHIFT, WalkBlendShiftParams, WalkBlendParams> P) {
+//
+// REGIONS (always SHIFT, at rest with shift 0): both weight maps are loaded, and for Mixture of Diffusers divided, in front of the walk, which is
+// skipped when no grid is drawn (num_batches == 0); the region tail runs per element at the canvas columns xc[j], so a region that crosses a seam
+// and a quad that the shift cut take the same path.
+template <typename T, int METHOD, int PP, bool SPARSE, bool SHIFT, bool REGIONS = false>
+__global__ __launch_bounds__(256) void k_walk_blend(const WalkBlendArgs<SHIFT, REGIONS> P) {
     static_assert(!(SPARSE && SHIFT), "a sparse plan is never shifted");
+    static_assert(!REGIONS || (SHIFT && !SPARSE), "regions come with the shifted grid's store, never on a sparse plan");
     const int W4 = (P.W + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= W4 * P.H) return;
@@ -165,19 +197,54 @@ __global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHI
     const int nvalid = P.W - x0 < 4 ? P.W - x0 : 4;
     const size_t tile_elems = (size_t)P.th * P.tw;
 
+    // SHIFT: the quad's canvas pixels are row yc, columns xc[j] = (xd + j) mod W -- consecutive in memory unless the seam cuts the displaced quad
+    // (`uncut`).  REGIONS place the quad here; SHIFT alone does in front of its store (here it changes hipcc's schedule of those kernels).
+    [[maybe_unused]] int yc, xd, xc[4];
+    [[maybe_unused]] bool uncut;
+    // the weight sum and, for Mixture of Diffusers, its reciprocal; pixels past the canvas (j >= nvalid) keep 0 and are never used
+    [[maybe_unused]] float wsum[4] = {0.f, 0.f, 0.f, 0.f};
+    float resc[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (REGIONS) {
+        yc = onto(y + P.shift_y, P.H);                     // y < H, shift_y < H
+        xd = onto(x0 + P.shift_x, P.W);                    // x0 < W, shift_x < W
+        uncut = nvalid == 4 && xd + 3 < P.W;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xc[j] = onto(xd + j, P.W);
+
+        // wsum = grid_w[yp, xp] + region_w[yc, xc]
+        float gw[4] = {0.f, 0.f, 0.f, 0.f}, rw[4] = {0.f, 0.f, 0.f, 0.f};
+        const float* rrow = P.region_w + (size_t)yc * P.W;
+        if (uncut) {
+            load4<float>(rrow + xd, rw);
+            if (P.grid_w) load4<float>(P.grid_w + (size_t)y * P.W + x0, gw);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= nvalid) continue;
+                rw[j] = rrow[xc[j]];
+                if (P.grid_w) gw[j] = P.grid_w[(size_t)y * P.W + x0 + j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= nvalid) continue;
+            wsum[j] = gw[j] + rw[j];
+            if (METHOD == MDTILE_METHOD_MOD) resc[j] = 1.0f / wsum[j];      // inf where nothing covers the pixel: never multiplied there
+        }
+    }
+
     float acc[PP][4];
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[pp][j] = 0.f;
 
-    const CyclicRun run(P.colquad[xq].x, P.cols), rrun(P.rowinfo[y].x, P.rows);
-
     // which pixels of the quad get a blended value (`SPARSE ? live[j] : j < nvalid` below): those on the canvas, and of them, on a sparse plan,
     // the live ones
     [[maybe_unused]] bool live[4];
     bool all_live = true, any_live = true;                 // of the pixels on the canvas; not sparse: every tile has an output
     if constexpr (SPARSE) {
+        const CyclicRun run(P.colquad[xq].x, P.cols), rrun(P.rowinfo[y].x, P.rows);
 #pragma unroll
         for (int j = 0; j < 4; ++j) live[j] = j < nvalid;
         for (int kr = 0; kr < rrun.count; ++kr) {
@@ -197,12 +264,16 @@ __global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHI
         all_live = live[0] && live[1] && live[2] && live[3];   // then nvalid == 4
         any_live = live[0] || live[1] || live[2] || live[3];
     }
-    if (any_live) {
-        float resc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (METHOD == MDTILE_METHOD_MOD) {
+    bool walk = any_live;
+    if constexpr (REGIONS) walk = P.num_batches > 0;       // 0: no grid is drawn, and the plan's tables are not read
+    if (walk) {
+        const CyclicRun run(P.colquad[xq].x, P.cols), rrun(P.rowinfo[y].x, P.rows);      // (SPARSE: the liveness pass's, loaded once)
+        if constexpr (!REGIONS) {
+            if (METHOD == MDTILE_METHOD_MOD) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (SPARSE ? live[j] : j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
+                for (int j = 0; j < 4; ++j)
+                    if (SPARSE ? live[j] : j < nvalid) resc[j] = P.rescale[(size_t)y * P.W + x0 + j];
+            }
         }
 
         for (int kr = 0; kr < rrun.count; ++kr) {          // ascending tile index: rows outer, columns inner
@@ -260,39 +331,110 @@ __global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHI
         }
 
         // MD normalisation: x = where(weights > 1, buf / weights, buf) (a sparse plan: the parent's full weight map)
+        if constexpr (!REGIONS) {
+            if (METHOD == MDTILE_METHOD_MD) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!(SPARSE ? live[j] : j < nvalid)) continue;
+                    const float w = P.weights[(size_t)y * P.W + x0 + j];
+                    if (w > 1.0f) {
+#pragma unroll
+                        for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
+                    }
+                }
+            }
+        }
+    }
+
+    if constexpr (REGIONS) {
+        // background regions, in list order, after every grid tile; Mixture of Diffusers: the region's RAW weight times this pixel's reciprocal
+        for (int k = 0; k < P.num_regions; ++k) {
+            const mdtile_region& R = P.regions[k];
+            if (R.mode != MDTILE_REGION_BG) continue;
+            const int ry = rel(yc, R.y, P.H);
+            if (ry >= R.h) continue;
+            const size_t rplane = (size_t)R.h * R.w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= nvalid) continue;
+                const int rx = rel(xc[j], R.x, P.W);
+                if (rx >= R.w) continue;
+                const size_t off = (size_t)ry * R.w + rx;
+                const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
+                float wgt = 1.0f;
+                if (METHOD == MDTILE_METHOD_MOD) wgt = R.weight[off] * resc[j];
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) {
+                    const float v = to_f32<T>(src[(size_t)pp * rplane]);
+                    if (METHOD == MDTILE_METHOD_MOD) acc[pp][j] += v * wgt;
+                    else acc[pp][j] += v;
+                }
+            }
+        }
+
+        // MD normalisation: x = wsum > 1 ? buf / wsum : buf
         if (METHOD == MDTILE_METHOD_MD) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (!(SPARSE ? live[j] : j < nvalid)) continue;
-                const float w = P.weights[(size_t)y * P.W + x0 + j];
-                if (w > 1.0f) {
+                if (j >= nvalid || !(wsum[j] > 1.0f)) continue;
 #pragma unroll
-                    for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / w;
+                for (int pp = 0; pp < PP; ++pp) acc[pp][j] = acc[pp][j] / wsum[j];
+            }
+        }
+
+        // foreground feather composite: blend_tail's (blend.hip), the coverage on the circle
+        if (P.num_fg > 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= nvalid) continue;
+                float fbuf[PP], fmask = 0.0f, fcnt = 0.0f;
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) fbuf[pp] = 0.0f;
+                for (int k = 0; k < P.num_regions; ++k) {
+                    const mdtile_region& R = P.regions[k];
+                    if (R.mode != MDTILE_REGION_FG) continue;
+                    const int ry = rel(yc, R.y, P.H), rx = rel(xc[j], R.x, P.W);
+                    if (ry >= R.h || rx >= R.w) continue;
+                    const size_t rplane = (size_t)R.h * R.w, off = (size_t)ry * R.w + rx;
+                    const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) fbuf[pp] += to_f32<T>(src[(size_t)pp * rplane]);
+                    fmask += R.weight[off];
+                    fcnt += 1.0f;
+                }
+                if (fcnt > 0.0f) {
+                    if (fcnt > 1.0f) fmask = fmask / fcnt;
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) {
+                        float fb = fbuf[pp];
+                        if (fcnt > 1.0f) fb = fb / fcnt;
+                        acc[pp][j] = acc[pp][j] * (1.0f - fmask) + fb * fmask;
+                    }
                 }
             }
         }
     }
 
     if constexpr (SHIFT) {
-        using R = typename RawOf<T>::type;
-        int yd = y + P.shift_y;                            // y < H, shift_y < H: one subtraction
-        if (yd >= P.H) yd -= P.H;
-        int xd = x0 + P.shift_x;                           // x0 < W, shift_x < W: likewise
-        if (xd >= P.W) xd -= P.W;
-        const bool uncut = nvalid == 4 && xd + 3 < P.W;    // the four destination columns are consecutive in memory
+        using Raw = typename RawOf<T>::type;
+        if constexpr (!REGIONS) {
+            yc = onto(y + P.shift_y, P.H);
+            xd = onto(x0 + P.shift_x, P.W);
+            uncut = nvalid == 4 && xd + 3 < P.W;
+        }
 #pragma unroll
         for (int pp = 0; pp < PP; ++pp) {
-            R* drow = reinterpret_cast<R*>(P.out) + ((size_t)(p0 + pp) * P.H + yd) * P.W;
+            Raw* drow = reinterpret_cast<Raw*>(P.out) + ((size_t)(p0 + pp) * P.H + yc) * P.W;
             if (uncut) {
-                raw4_u<R> o;
+                raw4_u<Raw> o;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o.v[j] = raw_bits<T>(acc[pp][j]);
-                *reinterpret_cast<raw4_u<R>*>(drow + xd) = o;
+                *reinterpret_cast<raw4_u<Raw>*>(drow + xd) = o;
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (j >= nvalid) continue;
-                    const int xj = xd + j < P.W ? xd + j : xd + j - P.W;
+                    const int xj = REGIONS ? xc[j] : onto(xd + j, P.W);       // SHIFT alone forms the columns here, where the seam cut the quad
                     drow[xj] = raw_bits<T>(acc[pp][j]);
                 }
             }
@@ -333,43 +475,19 @@ __global__ __launch_bounds__(256) void k_walk_blend(const std::conditional_t<SHI
     }
 }
 
-// planes per thread: 4 while that leaves >= ~128k threads (2 per lane of the chip) and divides N*C, as blend.hip sizes k_blend
-int planes_per_thread(const WalkBlendParams& P) {
-    const int planes = P.N * P.C;
-    const long long work = (long long)P.H * ((P.W + 3) / 4) * planes;
-    if (planes % 4 == 0 && work / 4 >= 131072) return 4;
-    return planes % 2 == 0 && work / 2 >= 131072 ? 2 : 1;
+template <typename T, int PP, bool SPARSE, bool SHIFT, bool REGIONS>
+auto walk_blend_kernel(int method) {
+    return method == MDTILE_METHOD_MD ? k_walk_blend<T, MDTILE_METHOD_MD, PP, SPARSE, SHIFT, REGIONS> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, SPARSE, SHIFT, REGIONS>;
 }
 
-using WalkBlendKernel = void (*)(const WalkBlendParams);
-template <typename T, int PP>
-WalkBlendKernel walk_blend_kernel(int method, bool sparse) {
-    if (method == MDTILE_METHOD_MD) return sparse ? k_walk_blend<T, MDTILE_METHOD_MD, PP, true, false> : k_walk_blend<T, MDTILE_METHOD_MD, PP, false, false>;
-    return sparse ? k_walk_blend<T, MDTILE_METHOD_MOD, PP, true, false> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false, false>;
-}
-
-dim3 walk_blend_grid(const WalkBlendParams& P, int pp) { return dim3(cdiv((long long)P.H * ((P.W + 3) / 4), 256), (P.N * P.C) / pp); }
-
-template <typename T>
-void launch_walk_blend(const WalkBlendParams& P, int method, hipStream_t s) {
-    const int pp = planes_per_thread(P);
-    const bool sparse = P.slot != nullptr;
-    const WalkBlendKernel k = pp == 4 ? walk_blend_kernel<T, 4>(method, sparse) : pp == 2 ? walk_blend_kernel<T, 2>(method, sparse) : walk_blend_kernel<T, 1>(method, sparse);
-    hipLaunchKernelGGL(k, walk_blend_grid(P, pp), dim3(256), 0, s, P);
-}
-
-// the shifted forms: the same launch shape, the kernels compiled with SHIFT
-using WalkBlendShiftKernel = void (*)(const WalkBlendShiftParams);
-template <typename T, int PP>
-WalkBlendShiftKernel walk_blend_shift_kernel(int method) {
-    return method == MDTILE_METHOD_MD ? k_walk_blend<T, MDTILE_METHOD_MD, PP, false, true> : k_walk_blend<T, MDTILE_METHOD_MOD, PP, false, true>;
-}
-
-template <typename T>
-void launch_walk_blend_shift(const WalkBlendShiftParams& P, int method, hipStream_t s) {
-    const int pp = planes_per_thread(P);
-    const WalkBlendShiftKernel k = pp == 4 ? walk_blend_shift_kernel<T, 4>(method) : pp == 2 ? walk_blend_shift_kernel<T, 2>(method) : walk_blend_shift_kernel<T, 1>(method);
-    hipLaunchKernelGGL(k, walk_blend_grid(P, pp), dim3(256), 0, s, P);
+// one launch shape for every form; with REGIONS PP is sized as without: whether another size pays with the region tail behind the walk is not
+// measured
+template <typename T, bool SPARSE, bool SHIFT, bool REGIONS = false>
+void launch_walk_blend(const WalkBlendArgs<SHIFT, REGIONS>& P, int method, hipStream_t s) {
+    const int planes = P.N * P.C, pp = planes_per_thread(P.W, P.H, planes);
+    const auto k = pp == 4 ? walk_blend_kernel<T, 4, SPARSE, SHIFT, REGIONS>(method) : pp == 2 ? walk_blend_kernel<T, 2, SPARSE, SHIFT, REGIONS>(method)
+                                                                                       : walk_blend_kernel<T, 1, SPARSE, SHIFT, REGIONS>(method);
+    hipLaunchKernelGGL(k, dim3(cdiv((long long)P.H * ((P.W + 3) / 4), 256), planes / pp), dim3(256), 0, s, P);
 }
 
 }  // namespace
@@ -461,12 +579,34 @@ int mdt::walk_blend(const mdtile_plan* p, const mdtile_blend_args* a, const void
     P.weights = a->d_weights; P.tile_w = a->d_tile_w; P.rescale = a->d_rescale; P.out = a->d_x_out;
     if (sparse) { P.slot = p->d_slot; P.fill = d_fill; }
     for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
-    if (shift) {
-        P.shift_x = shift[0]; P.shift_y = shift[1];
-        with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend_shift<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
-    } else {
-        with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend<std::remove_pointer_t<decltype(tag)>>(P, a->method, s); });
-    }
+    with_dtype(a->dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        if (shift) {
+            P.shift_x = shift[0]; P.shift_y = shift[1];
+            launch_walk_blend<T, false, true>(P, a->method, s);
+        } else if (sparse) {
+            launch_walk_blend<T, true, false>(P, a->method, s);
+        } else {
+            launch_walk_blend<T, false, false>(P, a->method, s);
+        }
+    });
+    MDT_LAUNCH_CHECK();
+    return MDTILE_OK;
+}
+
+// mdtile_blend_wrap_regions (wrap_regions.hip, which has checked every argument and counted the foreground regions) -> the REGIONS kernels
+int mdt::walk_blend_regions(const mdtile_plan* p, const mdtile_blend_args* a, const void* const* batch_out, int num_batches, const mdtile_wrap_regions* wr,
+                            int num_fg, hipStream_t s) {
+    if (int rc = plan_upload(p)) return rc;
+    WrapRegionsParams P;
+    memset(&P, 0, sizeof(P));
+    P.W = p->w; P.H = p->h; P.tw = p->tw; P.th = p->th; P.cols = p->cols; P.rows = p->rows; P.tile_bs = p->tile_bs; P.N = a->N; P.C = a->C;
+    P.num_batches = num_batches; P.num_regions = wr->num_regions; P.num_fg = num_fg; P.shift_x = wr->sx; P.shift_y = wr->sy;
+    P.xs = p->d_xs; P.ys = p->d_ys; P.colquad = p->d_colquad; P.rowinfo = p->d_rowinfo;
+    P.grid_w = wr->d_grid_w; P.region_w = wr->d_region_w; P.tile_w = a->d_tile_w; P.out = a->d_x_out;
+    for (int k = 0; k < wr->num_regions; ++k) P.regions[k] = wr->regions[k];
+    for (int b = 0; b < num_batches; ++b) P.batch[b] = batch_out[b];
+    with_dtype(a->dtype, [&](auto* tag) { launch_walk_blend<std::remove_pointer_t<decltype(tag)>, false, true, true>(P, a->method, s); });
     MDT_LAUNCH_CHECK();
     return MDTILE_OK;
 }

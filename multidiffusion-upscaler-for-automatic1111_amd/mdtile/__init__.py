@@ -1009,16 +1009,34 @@ def blend(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C:
                      device=device, partial=partial, tile_range=tile_range, row_range=row_range, packed=packed)()
 
 
+def _batch_operands(grid, batch_out, N: int, C: int, dtype, device, strict: bool, regions=()):
+    """What the one-launch blends ask of batch_out first: dtype and device (the first batch's, else the first region output's, else as given), and
+    every tensor on the device, in that dtype, shaped as the batch of `grid` (a Plan or a Lattice) at its index.  strict False: a tensor past the
+    grid's batches goes unchecked -- the library refuses the count by name.  -> (dtype, device)"""
+    if len(batch_out):
+        dtype, device = batch_out[0].dtype, batch_out[0].device
+    elif len(regions):
+        dtype, device = regions[0].out.dtype, regions[0].out.device
+    assert dtype is not None and device is not None
+    for i, t in enumerate(batch_out):
+        _dev_tensor(t, f"batch_out[{i}]", dtype)
+        assert (not strict and i >= len(grid.batches)) or tuple(t.shape) == (len(grid.batches[i]) * N, C, grid.tile_h, grid.tile_w), \
+            f"batch_out[{i}] {tuple(t.shape)}"
+    return dtype, device
+
+
+def _region_operands(regions: Sequence[RegionSpec], N: int, C: int, dtype):
+    """The region array of the blends that take raw region weights: every output [N, C, h, w]; the count is left to the library."""
+    for i, r in enumerate(regions):
+        assert tuple(r.out.shape) == (N, C, r.h, r.w), f"region[{i}] output {tuple(r.out.shape)} vs [{N}, {C}, {r.h}, {r.w}]"
+    return _regions_array(regions, dtype, limit=False)
+
+
 def blend_shift(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, sx: int, sy: int, weights=None, tile_w=None,
                 rescale=None, out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
     """blend on a wrap-around plan with the grid displaced cyclically by (sx, sy): roll(blend(...), (+sy, +sx)) bit for bit, in one launch.
     weights / tile_w / rescale are the plan's unshifted maps."""
-    if len(batch_out):
-        dtype, device = batch_out[0].dtype, batch_out[0].device
-    assert dtype is not None and device is not None
-    for i, t in enumerate(batch_out):
-        _dev_tensor(t, f"batch_out[{i}]", dtype)
-        assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    dtype, device = _batch_operands(plan, batch_out, N, C, dtype, device, strict=True)
     out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
     _check(lib().mdtile_blend_shift(plan.handle, ctypes.byref(a), ptrs, len(batch_out), int(sx), int(sy), _stream()), "mdtile_blend_shift")
     return out
@@ -1032,24 +1050,32 @@ def blend_wrap_regions(plan: Plan, method: int, batch_out: Sequence[torch.Tensor
     coordinates (None iff batch_out is empty); region_w: the background regions' weight sum [H, W] on the canvas (zeros when there is none).
     A background region's weight is its RAW Gaussian (Mixture of Diffusers): the kernel forms grid_w + region_w and its reciprocal per pixel.
     weights / rescale exist only to be refused: the library takes no total map here."""
-    if len(batch_out):
-        dtype, device = batch_out[0].dtype, batch_out[0].device
-    elif len(regions):
-        dtype, device = regions[0].out.dtype, regions[0].out.device
-    assert dtype is not None and device is not None
-    for i, t in enumerate(batch_out):
-        _dev_tensor(t, f"batch_out[{i}]", dtype)
-        assert i >= len(plan.batches) or tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    dtype, device = _batch_operands(plan, batch_out, N, C, dtype, device, strict=False, regions=regions)
     for nm, t in (("grid_w", grid_w), ("region_w", region_w)):
         if t is not None:
             _dev_tensor(t, nm, torch.float32)
             assert t.numel() == plan.h * plan.w, f"{nm} {tuple(t.shape)}"
     out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
-    for i, r in enumerate(regions):
-        assert tuple(r.out.shape) == (N, C, r.h, r.w), f"region[{i}] output {tuple(r.out.shape)} vs [{N}, {C}, {r.h}, {r.w}]"
-    rarr, _keep = _regions_array(regions, dtype, limit=False)
+    rarr, _keep = _region_operands(regions, N, C, dtype)
     wr = _WrapRegions(rarr, len(regions), _p(grid_w).value, _p(region_w).value, int(sx), int(sy))
     _check(lib().mdtile_blend_wrap_regions(plan.handle, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(wr), _stream()), "mdtile_blend_wrap_regions")
+    return out
+
+
+def _blend_lattice(lat: Lattice, method: int, batch_out, N: int, C: int, tile_w, weights, rescale, out, dtype, device, regions=None, region_w=None):
+    """blend_lattice (regions None) and blend_lattice_regions (a sequence, which may be empty)."""
+    dtype, device = _batch_operands(lat, batch_out, N, C, dtype, device, strict=False)
+    if region_w is not None:
+        _dev_tensor(region_w, "region_w", torch.float32)
+        assert region_w.numel() == lat.h * lat.w, f"region_w {tuple(region_w.shape)}"
+    out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    if regions is None:
+        _check(lib().mdtile_blend_lattice(lat.ref, ctypes.byref(a), ptrs, len(batch_out), _stream()), "mdtile_blend_lattice")
+        return out
+    rarr, _keep = _region_operands(regions, N, C, dtype)
+    lr = _LatticeRegions(rarr, len(regions), _p(region_w).value)
+    _check(lib().mdtile_blend_lattice_regions(lat.ref, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(lr), _stream()),
+           "mdtile_blend_lattice_regions")
     return out
 
 
@@ -1058,15 +1084,7 @@ def blend_lattice(lat: Lattice, method: int, batch_out: Sequence[torch.Tensor], 
     """The blend of the step's jittered grid, one launch: every tile contributes where its LATTICE box lies, read at its pushed-in box; the weight
     sum of the step (MultiDiffusion's count, Mixture of Diffusers' Gaussian sum and its reciprocal) is formed inside the kernel.  tile_w: the
     [tile_h, tile_w] map, required for METHOD_MOD.  weights / rescale exist only to be refused: the library takes no maps here."""
-    if len(batch_out):
-        dtype, device = batch_out[0].dtype, batch_out[0].device
-    assert dtype is not None and device is not None
-    for i, t in enumerate(batch_out):
-        _dev_tensor(t, f"batch_out[{i}]", dtype)
-        assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
-    out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
-    _check(lib().mdtile_blend_lattice(lat.ref, ctypes.byref(a), ptrs, len(batch_out), _stream()), "mdtile_blend_lattice")
-    return out
+    return _blend_lattice(lat, method, batch_out, N, C, tile_w, weights, rescale, out, dtype, device)
 
 
 def blend_lattice_regions(lat: Lattice, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, regions: Sequence[RegionSpec] = (),
@@ -1077,23 +1095,7 @@ def blend_lattice_regions(lat: Lattice, method: int, batch_out: Sequence[torch.T
     MultiDiffusion, the raw Gaussians for Mixture of Diffusers), made once per job; None iff there is no background region.  A background
     region's weight is its RAW Gaussian (Mixture of Diffusers): the kernel forms the step's weight sum + region_w and its reciprocal per pixel.
     weights / rescale exist only to be refused: the library takes no total map here."""
-    if len(batch_out):
-        dtype, device = batch_out[0].dtype, batch_out[0].device
-    assert dtype is not None and device is not None
-    for i, t in enumerate(batch_out):
-        _dev_tensor(t, f"batch_out[{i}]", dtype)
-        assert i >= len(lat.batches) or tuple(t.shape) == (len(lat.batches[i]) * N, C, lat.tile_h, lat.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
-    if region_w is not None:
-        _dev_tensor(region_w, "region_w", torch.float32)
-        assert region_w.numel() == lat.h * lat.w, f"region_w {tuple(region_w.shape)}"
-    out, a, ptrs = _blend_operands(lat, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
-    for i, r in enumerate(regions):
-        assert tuple(r.out.shape) == (N, C, r.h, r.w), f"region[{i}] output {tuple(r.out.shape)} vs [{N}, {C}, {r.h}, {r.w}]"
-    rarr, _keep = _regions_array(regions, dtype, limit=False)
-    lr = _LatticeRegions(rarr, len(regions), _p(region_w).value)
-    _check(lib().mdtile_blend_lattice_regions(lat.ref, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(lr), _stream()),
-           "mdtile_blend_lattice_regions")
-    return out
+    return _blend_lattice(lat, method, batch_out, N, C, tile_w, weights, rescale, out, dtype, device, regions=list(regions), region_w=region_w)
 
 
 def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, fill: torch.Tensor, weights=None, tile_w=None,
@@ -1103,12 +1105,7 @@ def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: 
     weights / rescale are the parent's full maps."""
     if not plan.sparse:
         raise MdtileError("blend_sparse needs a sparse plan (Plan.subset); the blend of a full plan is blend()")
-    if len(batch_out):
-        dtype, device = batch_out[0].dtype, batch_out[0].device
-    assert dtype is not None and device is not None
-    for i, t in enumerate(batch_out):
-        _dev_tensor(t, f"batch_out[{i}]", dtype)
-        assert tuple(t.shape) == (len(plan.batches[i]) * N, C, plan.tile_h, plan.tile_w), f"batch_out[{i}] {tuple(t.shape)}"
+    dtype, device = _batch_operands(plan, batch_out, N, C, dtype, device, strict=True)
     _dev_tensor(fill, "fill", dtype)
     assert tuple(fill.shape) == (N, C, plan.h, plan.w), f"fill {tuple(fill.shape)}"
     out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)

@@ -1,4 +1,4 @@
-"""A/B of region control under the jittered grid (csrc/lattice_regions.hip: k_lattice_blend_regions) against the calls of before,
+"""A/B of region control under the jittered grid (csrc/lattice.hip: k_lattice_blend<..., REGIONS>) against the calls of before,
 the protocol of probes/shift_ab.py: one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache), 20 back-to-back
 evaluations per HIP-event pair, median of 7 rounds, the arms ALTERNATING inside every round in an order rotated per round -- at latent 1024^2,
 tile 128 / overlap 0 and 128 / 8, fp32 and fp16, N = 2, C = 4, MultiDiffusion and Mixture of Diffusers, at rest and at the shift (5, 3).  One

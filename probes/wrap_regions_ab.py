@@ -1,4 +1,4 @@
-"""A/B of region control on a wrap-around canvas (csrc/wrap_regions.hip: k_walk_blend_regions and the rect kernels) against the calls
+"""A/B of region control on a wrap-around canvas (csrc/wrap.hip: k_walk_blend<..., REGIONS>; csrc/wrap_regions.hip: the rect kernels) against the calls
 of before, the protocol of probes/shift_ab.py: one process, COLD (rotating buffer sets larger than the 256 MiB Infinity Cache), 20 back-to-back
 evaluations per HIP-event pair, median of 7 rounds, the arms ALTERNATING inside every round -- at latent 1024^2 closed in both axes and
 1024 x 512 closed in x, tile 128 / overlap 8 and 96 / 48, fp32 and fp16, N = 2, C = 4, MultiDiffusion and Mixture of Diffusers.  One evaluation =

@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""Did a source change alter the code of a kernel that was meant to stay as it is?   usage: python tools/isa_diff.py <git-rev> [file.hip ...]
+"""Did a source change alter the code of a kernel that was meant to stay as it is?
+usage: python tools/isa_diff.py <git-rev> [--rename REGEX=REPL ...] [file.hip | old.hip:new.hip ...]
 Compiles the named csrc/*.hip files (default: the conv / attention kernel files) to gfx950 device assembly twice -- as they are in the working
 tree and as they were at <git-rev> (checked out into a scratch directory with the headers of that revision) -- with the build's own flags
 (mdtile/build.py: HIPCC_FLAGS), and compares every kernel both sides have instruction by instruction.  Basic-block label numbers are
 normalised (they count functions of the file); a template parameter a kernel gained with a default value (`..., false>`) is matched to the
-old name.  Prints one line per kernel: IDENTICAL, or the number of differing lines and the first few.
+old name; kernels are matched by name and template arguments, not by the types of their arguments (an argument block may have been renamed).
+A kernel that was renamed or moved: `old.hip:new.hip` compares the kernels of <git-rev>'s old.hip with those of the working tree's new.hip, and
+every --rename (a regular expression and its replacement, on the mangled name) is applied to the old names first; of such a pair only the
+kernels that have a counterpart are reported.  Prints one line per kernel: IDENTICAL, or the number of differing lines and the first few.
 Round 5 used it to show that the statistics variants of the record kernels (k_conv3x3_rec_st, k_upconv_rec_st: the same text included a
 second time) left the shipping kernels' code untouched: the only difference is the kernarg offset of the implicit arguments (0xd0 -> 0xd8,
 ConvRParams grew by one pointer).  CPU-only (hipcc cross-compiles)."""
@@ -51,36 +55,54 @@ def norm(line: str) -> str:
     return re.sub(r"\.LBB\d+_", ".LBBx_", line)
 
 
+def key(name: str) -> str:
+    """the mangled name of a template kernel up to the end of its template arguments and the `void`: without the argument types"""
+    return name[:name.index("EEv") + 3] if "EEv" in name else name
+
+
 def main() -> int:
-    if len(sys.argv) < 2:
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
+    if not args:
         print(__doc__)
         return 2
-    rev, files = sys.argv[1], sys.argv[2:] or DEFAULT
+    rev, files = args[0], args[1:] or DEFAULT
     changed = 0
     with tempfile.TemporaryDirectory() as old_root:
         checkout(rev, old_root)
         for f in files:
-            old_src = os.path.join(old_root, PKG, "csrc", f)
+            fo, _, fn = f.partition(":")
+            moved, fn = bool(fn), fn or fo
+            old_src = os.path.join(old_root, PKG, "csrc", fo)
             if not os.path.exists(old_src):
-                print(f"{f}: not in {rev}")
+                print(f"{fo}: not in {rev}")
                 continue
-            old, new = asm(old_src), asm(os.path.join(ROOT, PKG, "csrc", f))
+            old, new = asm(old_src), {key(k): v for k, v in asm(os.path.join(ROOT, PKG, "csrc", fn)).items()}
             alias = {re.sub(r"ELb0EEEv", "EEEv", k): k for k in new}      # a new trailing `false` template argument
+            seen = set()
             for k, a in old.items():
-                kk = k if k in new else alias.get(k)
+                kk = key(k)
+                for pat, repl in renames:
+                    kk = re.sub(pat, repl, kk)
+                kk = kk if kk in new else alias.get(kk)
                 if kk is None:
-                    print(f"{f}: {k[:90]}  -- gone")
-                    changed += 1
+                    if not moved:
+                        print(f"{f}: {k[:90]}  -- gone")
+                        changed += 1
                     continue
+                seen.add(kk)
                 b = new[kk]
                 d = [(x, y) for x, y in zip(map(norm, a), map(norm, b)) if x != y]
                 if len(a) == len(b) and not d:
-                    print(f"{f}: {k[:90]}  {len(a)} instr  IDENTICAL")
+                    print(f"{f}: {k[:90]}  {len(a)} instr  IDENTICAL" + (f"  (now {kk[:90]})" if kk != key(k) else ""))
                 else:
                     changed += 1
                     print(f"{f}: {k[:90]}  {len(a)} -> {len(b)} instr, {len(d)} differing lines: {d[:3]}")
             for k in new:
-                if k not in old and re.sub(r"ELb0EEEv", "EEEv", k) not in old:
+                if k not in seen and not moved:
                     print(f"{f}: {k[:90]}  -- new ({len(new[k])} instr)")
     return 1 if changed else 0
 

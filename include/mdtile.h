@@ -421,6 +421,57 @@ typedef struct mdtile_lattice_regions {
 int mdtile_blend_lattice_regions(const mdtile_lattice* lat, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                                  const mdtile_lattice_regions* r, mdtile_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Inpaint tile skipping under the jittered grid (csrc/lattice.hip).  Nothing upstream corresponds to it.  For a lattice `lat`
+ * (fields as mdtile_lattice_make writes them) tile t = r cols + c has lattice origin (v_r, u_c) and pushed-in box (y'_r, x'_c).
+ *
+ * Its CONTRIBUTING box is its lattice box clipped to the canvas, [max(v_r, 0), min(v_r + th, H)) x [max(u_c, 0), min(u_c + tw, W)): the only
+ *   place where the tile's output enters the blend.
+ * ACTIVITY  active[t] = 1 iff some element of mask[:, contributing box of t] satisfies !(v == 0.0f), the test of mdtile_tile_activity: NaN,
+ *   denormals, negatives and fractions count, +0.0 and -0.0 do not.  The test runs on the contributing box, NOT the pushed-in box: a tile pushed in
+ *   from the edge is evaluated over pixels it never writes, and those do not make it active.  Every pixel with a non-zero mask lies in the
+ *   contributing box of each tile that covers it, so every such pixel is live (below).
+ * COMPACT NUMBERING  slot[t] = number of active t' < t if t is active, else -1;  Ta = number of active tiles;  num_batches = ceil(Ta / tile_bs
+ *   requested), tile_bs := ceil(Ta / num_batches): the rule of mdtile_plan_create_subset.  Active tile number s occupies rows (s mod tile_bs) * N ...
+ *   of batch s / tile_bs.
+ * GATHER  the compact batches hold, for each active tile, exactly what mdtile_gather_all_lattice puts into that tile's rows: the pushed-in box,
+ *   copied as bits.
+ * BLEND   a pixel is LIVE iff every lattice tile that covers it is active.  At a live pixel the output is, bit for bit, what mdtile_blend_lattice
+ *   writes there given the same outputs for the active tiles: covering tiles in ascending t, fp32 from +0.0, no contraction, the weight sum over all
+ *   covering tiles, MD wsum > 1 ? buf / wsum : buf, MoD v * (tile_w[lattice coords] * (1.0f / wsum)), half I/O rounded once.  At any other pixel the
+ *   output is the bit pattern of d_fill[n, c, y, x], and no tile output is read for it.  Every canvas pixel is written exactly once.
+ *
+ * mdtile_lattice_activity: d_mask fp32 [planes, H, W]; d_active, d_slot device int32[lat->num_tiles].  Two launches (the per-tile reduction, then
+ *   the ranks) write every entry of both, no pre-clearing; at most 65535 tiles.
+ * mdtile_lattice_subset_make: host integers only.  h_active = lat->num_tiles host ints (non-zero = active); fills *sub with the lattice, Ta and the
+ *   compact batching for `tile_bs`, and keeps d_slot (caller-owned device memory, not read here).
+ * mdtile_lattice_subset_bboxes: xywh[4 * Ta] = the pushed-in boxes of the active tiles, ids[Ta] = their tile indices, both in ascending t (ids may
+ *   be NULL); h_active must hold exactly sub->num_active non-zero flags.
+ * d_slot must hold the ranks of the same flags mdtile_lattice_subset_make was given -- from mdtile_lattice_activity, or the caller's own upload.
+ *   The library cannot check that without a synchronisation, so the kernels treat any slot[t] < 0 or slot[t] >= num_active as "not active": a wrong
+ *   table can give pixels that are not live (or, where two tiles claim one slot, the wrong tile's values) but never an access outside a batch.
+ * mdtile_gather_all_lattice_sparse / mdtile_blend_lattice_sparse: batch_ptrs / batch_out = the sub->num_batches COMPACT batches; args as
+ *   mdtile_blend_lattice; d_fill [N, C, H, W] of args->dtype, required.  One launch each.  Ta == num_tiles is allowed.
+ * REFUSED (MDTILE_E_ARG, the text names the function and the reason, before any device is touched, nothing is written): everything
+ *   mdtile_blend_lattice / mdtile_gather_all_lattice refuse (flags, a row band, non-NULL d_weights / d_rescale, MoD without d_tile_w, bad N / C / dtype /
+ *   method, null pointers); a sub->lat that mdtile_lattice_make did not write; num_active outside 1 .. num_tiles (no active tile: nothing to run);
+ *   num_batches, tile_bs that are not the rule's for num_active; num_batches different from the call's argument, or above MDTILE_MAX_BATCHES; NULL
+ *   d_slot or d_fill; planes < 1 (or above 65535); more than 65535 tiles in the activity or the gather.
+ * -------------------------------------------------------------------------------------------------------- */
+typedef struct mdtile_lattice_subset {
+    mdtile_lattice lat;          /* the step's full lattice */
+    int num_active;              /* Ta, 1 .. lat.num_tiles */
+    int num_batches, tile_bs;    /* of the compact batches */
+    const int* d_slot;           /* device int32[lat.num_tiles], caller-owned */
+} mdtile_lattice_subset;
+int mdtile_lattice_activity(const mdtile_lattice* lat, const float* d_mask, int planes, int* d_active, int* d_slot, mdtile_stream_t stream);
+int mdtile_lattice_subset_make(const mdtile_lattice* lat, const int* h_active, int tile_bs, const int* d_slot, mdtile_lattice_subset* sub);
+int mdtile_lattice_subset_bboxes(const mdtile_lattice_subset* sub, const int* h_active, int* xywh, int* ids);
+int mdtile_gather_all_lattice_sparse(const mdtile_lattice_subset* sub, int dtype, int N, int C, const void* d_x_in, void* const* batch_ptrs,
+                                     int num_batches, mdtile_stream_t stream);
+int mdtile_blend_lattice_sparse(const mdtile_lattice_subset* sub, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                                const void* d_fill, mdtile_stream_t stream);
+
 /* Per-region initial noise (scripts/tilediffusion.py:486-529, create_random_tensors_hijack): d_noise [N,C,H,W] fp32 is the job's
  * noise, updated in place.  regions[i].out = the region's own noise [1,C,h,w] fp32 (drawn by the host with the region's CPU
  * seed, shared by all N samples), .mode = MDTILE_REGION_BG / _FG, .weight unused.  Per layer: sum + hit count over the regions

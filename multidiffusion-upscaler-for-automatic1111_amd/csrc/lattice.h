@@ -32,6 +32,13 @@ struct LatticeRegionsParams : LatticeBlendParams {
     mdtile_region regions[MDTILE_MAX_REGIONS];
 };
 static_assert(sizeof(LatticeRegionsParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// with tile skipping (mdtile_blend_lattice_sparse): tile_bs is the COMPACT batches', `batch` holds those
+struct LatticeSparseParams : LatticeBlendParams {
+    const int* slot;          // slot[t] = place of tile t in the compact batches; anything outside [0, num_active) = the tile is not active
+    const void* fill;         // [N, C, H, W] in the storage type: the value of every pixel that is not live
+    int num_active;
+};
+static_assert(sizeof(LatticeSparseParams) <= 4096, "kernel argument block must stay under 4 KiB");
 
 // floor(a / b), b > 0 (C's `/` truncates towards zero: wrong for the negative numerators left of the first stride)
 __host__ __device__ __forceinline__ int floor_div(int a, int b) {
@@ -123,6 +130,28 @@ int batches_check(const char* fn, const mdtile_lattice* l, int num_batches) {
     MDT_CHECK_ARG(num_batches == l->num_batches, "%s: %d batches given, the lattice has %d", fn, num_batches, l->num_batches);
     MDT_CHECK_ARG(num_batches <= MDTILE_MAX_BATCHES, "%s: %d batches > MDTILE_MAX_BATCHES=%d (the lattice has no packed form: raise the tile batch size)", fn,
                   num_batches, MDTILE_MAX_BATCHES);
+    return MDTILE_OK;
+}
+
+// Is *sub what mdtile_lattice_subset_make writes?  The flags it was made from are not kept, so what can be checked is the lattice, the count and
+// the batching rule on it; the slot table is the device's, and the kernels treat every entry outside [0, num_active) as "not active".
+int subset_check(const char* fn, const mdtile_lattice_subset* sub) {
+    MDT_CHECK_ARG(sub, "%s: null subset", fn);
+    if (int rc = lattice_check(fn, &sub->lat)) return rc;
+    MDT_CHECK_ARG(sub->num_active >= 1 && sub->num_active <= sub->lat.num_tiles, "%s: bad subset: num_active = %d outside [1, %d] (the lattice's tiles)", fn,
+                  sub->num_active, sub->lat.num_tiles);
+    MDT_CHECK_ARG(sub->num_batches > 0 && sub->tile_bs > 0 && sub->num_batches == (sub->num_active - 1) / sub->tile_bs + 1 &&
+                      sub->tile_bs == (sub->num_active - 1) / sub->num_batches + 1,      // ceil without a sum that could pass INT_MAX
+                  "%s: bad subset: %d batches of %d for %d active tiles (not the rule num_batches = ceil(Ta / tile_bs), tile_bs = ceil(Ta / num_batches))", fn,
+                  sub->num_batches, sub->tile_bs, sub->num_active);
+    MDT_CHECK_ARG(sub->d_slot, "%s: null d_slot: the blend and the gather find an active tile's place in the compact batches there", fn);
+    return MDTILE_OK;
+}
+
+int subset_batches_check(const char* fn, const mdtile_lattice_subset* sub, int num_batches) {
+    MDT_CHECK_ARG(num_batches == sub->num_batches, "%s: %d batches given, the subset has %d", fn, num_batches, sub->num_batches);
+    MDT_CHECK_ARG(num_batches <= MDTILE_MAX_BATCHES, "%s: %d batches > MDTILE_MAX_BATCHES=%d (raise the tile batch size, or run the full lattice)", fn, num_batches,
+                  MDTILE_MAX_BATCHES);
     return MDTILE_OK;
 }
 

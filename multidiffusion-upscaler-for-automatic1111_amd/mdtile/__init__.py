@@ -80,6 +80,10 @@ class _LatticeRegions(ctypes.Structure):
     _fields_ = [("regions", POINTER(_Region)), ("num_regions", c_int), ("d_region_w", c_void_p)]
 
 
+class _LatticeSubset(ctypes.Structure):
+    _fields_ = [("lat", _Lattice), ("num_active", c_int), ("num_batches", c_int), ("tile_bs", c_int), ("d_slot", c_void_p)]
+
+
 # every symbol include/mdtile.h declares: name -> (restype, argtypes)
 _IP = POINTER(c_int)
 _SIGNATURES = {
@@ -125,6 +129,11 @@ _SIGNATURES = {
     "mdtile_gather_all_lattice": (c_int, [POINTER(_Lattice), c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
     "mdtile_blend_lattice": (c_int, [POINTER(_Lattice), POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p]),
     "mdtile_blend_lattice_regions": (c_int, [POINTER(_Lattice), POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_LatticeRegions), c_void_p]),
+    "mdtile_lattice_activity": (c_int, [POINTER(_Lattice), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mdtile_lattice_subset_make": (c_int, [POINTER(_Lattice), _IP, c_int, c_void_p, POINTER(_LatticeSubset)]),
+    "mdtile_lattice_subset_bboxes": (c_int, [POINTER(_LatticeSubset), _IP, _IP, _IP]),
+    "mdtile_gather_all_lattice_sparse": (c_int, [POINTER(_LatticeSubset), c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
+    "mdtile_blend_lattice_sparse": (c_int, [POINTER(_LatticeSubset), POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
@@ -421,6 +430,55 @@ class Lattice:
     def ref(self):
         """The C struct by reference, for a call of the library."""
         return ctypes.byref(self._c)
+
+
+class LatticeSubset:
+    """The active tiles of one step's lattice (mdtile_lattice_subset, include/mdtile.h): flags = one per lattice tile (as lattice_activity returns
+    them), slot = the device int32 table of their ranks (lattice_activity's second result, or the caller's own upload; kept alive here).  ids =
+    the active tile indices in ascending order, bboxes / batches = their PUSHED-IN boxes in the compact batches, num_tiles = num_active = Ta.
+    Raises MdtileError when no tile is active and beyond MAX_BATCHES batches.  Host integers only: nothing to destroy."""
+
+    def __init__(self, lat: Lattice, flags: Sequence[int], tile_bs: int, slot: torch.Tensor):
+        L = lib()
+        if len(flags) != lat.num_tiles:
+            raise MdtileError(f"LatticeSubset: {len(flags)} flags for {lat.num_tiles} tiles")
+        _dev_tensor(slot, "slot", torch.int32)
+        if slot.numel() != lat.num_tiles:
+            raise MdtileError(f"LatticeSubset: slot table of {slot.numel()} entries for {lat.num_tiles} tiles")
+        h_active = (c_int * max(1, len(flags)))(*[1 if a else 0 for a in flags])
+        self._c = _LatticeSubset()
+        _check(L.mdtile_lattice_subset_make(lat.ref, h_active, int(tile_bs), _p(slot), ctypes.byref(self._c)), "mdtile_lattice_subset_make")
+        self.lat, self.slot = lat, slot
+        self.num_active = self.num_tiles = self._c.num_active
+        self.num_batches, self.tile_bs = self._c.num_batches, self._c.tile_bs
+        self.w, self.h, self.tile_w, self.tile_h = lat.w, lat.h, lat.tile_w, lat.tile_h
+        boxes, ids = (c_int * (4 * self.num_active))(), (c_int * self.num_active)()
+        _check(L.mdtile_lattice_subset_bboxes(ctypes.byref(self._c), h_active, boxes, ids), "mdtile_lattice_subset_bboxes")
+        flat = list(boxes)
+        self.ids = tuple(ids)
+        self.bboxes = [tuple(flat[4 * i:4 * i + 4]) for i in range(self.num_active)]
+        self.batches = [self.bboxes[i * self.tile_bs:(i + 1) * self.tile_bs] for i in range(self.num_batches)]
+
+    @property
+    def ref(self):
+        """The C struct by reference, for a call of the library."""
+        return ctypes.byref(self._c)
+
+
+def lattice_activity(lat: Lattice, mask: torch.Tensor) -> Tuple[List[int], torch.Tensor]:
+    """Per tile of the step's lattice: 1 when some element of mask[:, contributing box] is not equal to zero (NaN counts, -0.0 does not), else 0
+    -- the contributing box is the tile's LATTICE box clipped to the canvas, not the pushed-in box the model runs on.  -> (the flags on the host,
+    the device int32 table of their ranks: slot[t] = number of active t' < t, or -1).  mask: fp32 [P, H, W] (or [H, W]) on the device.  Two
+    launches and one device-to-host copy of num_tiles ints."""
+    _dev_tensor(mask, "mask", torch.float32)
+    if mask.dim() == 2:
+        mask = mask.unsqueeze(0)
+    if mask.dim() != 3 or tuple(mask.shape[-2:]) != (lat.h, lat.w):
+        raise MdtileError(f"lattice_activity: mask {tuple(mask.shape)} is not [planes, {lat.h}, {lat.w}]")
+    flags = torch.empty(lat.num_tiles, dtype=torch.int32, device=mask.device)
+    slot = torch.empty(lat.num_tiles, dtype=torch.int32, device=mask.device)
+    _check(lib().mdtile_lattice_activity(lat.ref, _p(mask), int(mask.shape[0]), _p(flags), _p(slot), _stream()), "mdtile_lattice_activity")
+    return flags.cpu().tolist(), slot
 
 
 def tile_activity(plan: Plan, mask: torch.Tensor) -> List[int]:
@@ -825,6 +883,22 @@ def gather_all_lattice(lat: Lattice, x_in: torch.Tensor, out: Optional[Sequence[
     return list(out)
 
 
+def gather_all_lattice_sparse(sub: LatticeSubset, x_in: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """gather_all_lattice of the active tiles only, into the subset's compact batches: one launch."""
+    _dev_tensor(x_in, "x_in")
+    N, C, H, W = x_in.shape
+    assert (H, W) == (sub.h, sub.w)
+    if out is None:
+        out = [torch.empty((len(b) * N, C, sub.tile_h, sub.tile_w), dtype=x_in.dtype, device=x_in.device) for b in sub.batches]
+    for i, t in enumerate(out):
+        _dev_tensor(t, f"out[{i}]", x_in.dtype)
+        assert i >= len(sub.batches) or tuple(t.shape) == (len(sub.batches[i]) * N, C, sub.tile_h, sub.tile_w), f"out[{i}] {tuple(t.shape)}"
+    ptrs = (c_void_p * max(1, len(out)))(*[t.data_ptr() for t in out])
+    _check(lib().mdtile_gather_all_lattice_sparse(sub.ref, dtype_code(x_in.dtype), N, C, _p(x_in), ptrs, len(out), _stream()),
+           "mdtile_gather_all_lattice_sparse")
+    return list(out)
+
+
 def gather_range(plan: Plan, x_in: torch.Tensor, packed: torch.Tensor, tile_lo: int, tile_hi: int) -> torch.Tensor:
     """Tiles [tile_lo, tile_hi) into the packed [T*N, C, th, tw] buffer (rows of other tiles are left untouched)."""
     _dev_tensor(x_in, "x_in")
@@ -1096,6 +1170,19 @@ def blend_lattice_regions(lat: Lattice, method: int, batch_out: Sequence[torch.T
     region's weight is its RAW Gaussian (Mixture of Diffusers): the kernel forms the step's weight sum + region_w and its reciprocal per pixel.
     weights / rescale exist only to be refused: the library takes no total map here."""
     return _blend_lattice(lat, method, batch_out, N, C, tile_w, weights, rescale, out, dtype, device, regions=list(regions), region_w=region_w)
+
+
+def blend_lattice_sparse(sub: LatticeSubset, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, fill: torch.Tensor, tile_w=None,
+                         weights=None, rescale=None, out: Optional[torch.Tensor] = None, dtype=None, device=None) -> torch.Tensor:
+    """The blend of the active tiles of the step's lattice, one launch: batch_out = the model outputs of the subset's compact batches.  Where every
+    covering lattice tile is active the result is blend_lattice()'s on the full lattice, bit for bit; everywhere else it is `fill` ([N, C, H, W],
+    the outputs' dtype), bit for bit.  weights / rescale exist only to be refused: the library takes no maps here."""
+    dtype, device = _batch_operands(sub, batch_out, N, C, dtype, device, strict=False)
+    _dev_tensor(fill, "fill", dtype)
+    assert tuple(fill.shape) == (N, C, sub.h, sub.w), f"fill {tuple(fill.shape)}"
+    out, a, ptrs = _blend_operands(sub, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale)
+    _check(lib().mdtile_blend_lattice_sparse(sub.ref, ctypes.byref(a), ptrs, len(batch_out), _p(fill), _stream()), "mdtile_blend_lattice_sparse")
+    return out
 
 
 def blend_sparse(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, fill: torch.Tensor, weights=None, tile_w=None,

@@ -46,7 +46,7 @@ def preload(parser):
              "step, offset by a function of the job's seed and the step, tiles that would hang over an edge pushed inside, so that no tile border "
              "stays in place for two steps and small or zero overlaps become usable. The tile count may change by a column and a row between "
              "steps. The fixed grid runs instead (one line says why) on a canvas that wraps around (use --mdtile-grid-shift there), with region "
-             "control (unless --mdtile-jitter-regions is set), when --mdtile-inpaint-skip skips tiles, in Noise Inversion's own evaluations, when the tile spans the canvas and beyond "
+             "control (unless --mdtile-jitter-regions is set), when --mdtile-inpaint-skip skips tiles (unless --mdtile-jitter-inpaint-skip is set), in Noise Inversion's own evaluations, when the tile spans the canvas and beyond "
              "320 tile batches. DemoFusion does not read it. Default: off, the grid stays where it is.")
     parser.add_argument(
         "--mdtile-jitter-regions", action="store_true",
@@ -74,4 +74,13 @@ def preload(parser):
         help="img2img inpainting with Tiled Diffusion (MultiDiffusion, Mixture of Diffusers): run the model only on the grid tiles that the job's "
              "latent mask touches. Relies on the host replacing the model output by the init latent wherever the mask is zero, as the webui's "
              "CFGDenoiser does; the masked area comes out bit-identical. Not applied with region control, wrap-around, Noise Inversion's own "
-             "evaluations or DemoFusion. Default: off, every tile runs.")
+             "evaluations or DemoFusion. With --mdtile-grid-jitter the tiles are skipped on the fixed grid, unless --mdtile-jitter-inpaint-skip is "
+             "set. Default: off, every tile runs.")
+    parser.add_argument(
+        "--mdtile-jitter-inpaint-skip", action="store_true",
+        help="Tiled Diffusion with both --mdtile-grid-jitter and --mdtile-inpaint-skip (MultiDiffusion, Mixture of Diffusers): keep the moving "
+             "grid when the inpaint mask lets tiles be skipped. Every sampler step asks which tiles of that step's grid the mask touches -- a tile "
+             "counts where it contributes, not where it was pushed inside the canvas -- and runs the model on those only; the count changes from "
+             "step to step. Without this option such a job skips tiles on the fixed grid, as before. Ignored (one line) without one of the two "
+             "options it builds on. Region control, wrap-around canvases and a job without a mask run as with --mdtile-grid-jitter alone; Noise "
+             "Inversion's own evaluations stay on the fixed grid with every tile; DemoFusion does not read it. Default: off.")

@@ -92,10 +92,15 @@ class AbstractDiffusion:
         self._lattice_at: Optional[tuple] = None     # (sampler step, mdtile.Lattice, the step's boxes): every evaluation of one step shares them
         self._jitter_notes: set = set()
         # --mdtile-inpaint-skip: decided on the job's first full-size evaluation (inpaint_skip), when the host has computed p.nmask
-        self.skip_mode: Optional[str] = None         # None = not decided yet | "full" | "sparse" | "empty" (the mask touches no tile)
+        self.skip_mode: Optional[str] = None         # None = not decided yet | "full" | "sparse" | "empty" (the mask touches no tile) | "lattice" (below)
         self.sparse_plan: Optional[mdtile.Plan] = None
         self.sparse_batched_bboxes: List[List[BBox]] = []
         self._skip_notes: set = set()
+        # --mdtile-jitter-inpaint-skip: the skip under the jittered grid.  skip_mode "lattice": the active set is another one
+        # every step, decided in step_lattice from the job's mask (uploaded once, kept here) and that step's lattice
+        self.skip_mask: Optional[Tensor] = None
+        self._subset_at: Optional[tuple] = None      # (sampler step, mdtile.LatticeSubset | mdtile.Lattice, its boxes | None): shared like _lattice_at
+        self._bar_budget = 0                         # tile batches per step the progress bar was sized with (init_done)
 
         # region prompt control
         self.enable_custom_bbox = False
@@ -166,6 +171,7 @@ class AbstractDiffusion:
         if self.enable_custom_bbox:
             self.total_bboxes += len(self.custom_bboxes)
         assert self.total_bboxes > 0, "Nothing to paint! No background to draw and no custom bboxes were provided."
+        self._bar_budget = self.total_bboxes
         try:
             from tqdm import tqdm
             self.pbar = tqdm(total=self.total_bboxes * state.sampling_steps, desc=f"{self.method} Sampling: ",
@@ -260,11 +266,17 @@ class AbstractDiffusion:
         """--mdtile-jitter-regions (preload.py); False on a host that never heard of the option."""
         return bool(getattr(shared.cmd_opts, "mdtile_jitter_regions", False))
 
+    @staticmethod
+    def jitter_inpaint_skip_requested() -> bool:
+        """--mdtile-jitter-inpaint-skip (preload.py); False on a host that never heard of the option."""
+        return bool(getattr(shared.cmd_opts, "mdtile_jitter_inpaint_skip", False))
+
     def init_grid_bbox(self, tile_w: int, tile_h: int, overlap: int, tile_bs: int):
         self.enable_grid_bbox = True
         self.requested_tile_bs = int(tile_bs)
         self.requested_grid = (int(tile_w), int(tile_h), int(overlap))
         self.skip_mode, self.sparse_plan, self.sparse_batched_bboxes = None, None, []      # a new grid: the mask is read again
+        self.skip_mask, self._subset_at = None, None
         # clamps (tile <= canvas; overlap <= min(requested tile) - 4), origins and batching all happen in the plan
         self.wrap_x = False
         if self.wrap_x_requested():
@@ -379,9 +391,26 @@ class AbstractDiffusion:
             print("[Tiled Diffusion] --mdtile-jitter-regions ignored: it only acts together with --mdtile-grid-jitter; the grid stays where it is.")
         return True
 
+    def _jitter_inpaint_skip_alone(self) -> bool:
+        """--mdtile-jitter-inpaint-skip without --mdtile-grid-jitter or without --mdtile-inpaint-skip means nothing: one line per job says so."""
+        if not self.jitter_inpaint_skip_requested() or (self.grid_jitter_requested() and self.inpaint_skip_requested()):
+            return False
+        if "skip alone" not in self._jitter_notes:
+            self._jitter_notes.add("skip alone")
+            missing = " and ".join(o for o, on in (("--mdtile-grid-jitter", self.grid_jitter_requested()),
+                                                   ("--mdtile-inpaint-skip", self.inpaint_skip_requested())) if not on)
+            print(f"[Tiled Diffusion] --mdtile-jitter-inpaint-skip ignored: it only acts together with both --mdtile-grid-jitter and "
+                  f"--mdtile-inpaint-skip ({missing} is not set); the job runs as without it.")
+        return True
+
+    def jitter_inpaint_skip_active(self) -> bool:
+        """The three options are set and the geometry lets this job's grid move."""
+        return self.grid_jitter and self.inpaint_skip_requested() and self.jitter_inpaint_skip_requested()
+
     def _init_grid_jitter(self):
         """What the geometry decides, once the plan is made: a canvas that wraps, no axis able to move, more batches than the lattice carries."""
         self.grid_jitter, self._lattice_at, self.jitter_max_batches = False, None, 0
+        self._jitter_inpaint_skip_alone()
         if not self.grid_jitter_requested():
             self._jitter_regions_alone()
             return
@@ -402,7 +431,10 @@ class AbstractDiffusion:
         tile_utils.lattice_shift of the job's seed and state.sampling_step on the axes that move; every evaluation made while the counter keeps its
         value (cond and uncond calls, the slices of a --lowvram batch) gets the same lattice, so that CFG subtracts two results of one tiling.
         own_evaluation: an evaluation that never moves the grid names itself here; skip: what --mdtile-inpaint-skip decided for it.  Each reason
-        is printed once per job."""
+        is printed once per job.
+        skip "lattice" (--mdtile-jitter-inpaint-skip): the first element is the step's mdtile.LatticeSubset and the boxes are its active tiles'
+        -- or the full lattice where every tile is active (or the active ones make too many batches), or boxes None where none is: the caller
+        returns a copy of its input and calls no model."""
         if not self.grid_jitter:
             return None
         if own_evaluation is not None:
@@ -411,7 +443,7 @@ class AbstractDiffusion:
             if self.jitter_regions_requested() and not self.draw_background:
                 return self._jitter_note(self.NO_BACKGROUND_TO_MOVE)
             return self._jitter_note("region prompt control is enabled (custom regions, or no background to draw)")
-        if skip != "full":
+        if skip not in ("full", "lattice"):
             return self._jitter_note(f"--mdtile-inpaint-skip decided \"{skip}\" for this job (tiles are skipped on the fixed grid)")
         step = int(state.sampling_step)
         if self._lattice_at is None or self._lattice_at[0] != step:
@@ -426,7 +458,39 @@ class AbstractDiffusion:
             self.p.extra_generation_params["Tiled Diffusion grid jitter"] = True
             if self.jitter_regions:
                 self.p.extra_generation_params["Tiled Diffusion jitter regions"] = True
+        if skip == "lattice":
+            return self._step_subset(step)
         return self._lattice_at[1], self._lattice_at[2]
+
+    def _step_subset(self, step: int):
+        """The active tiles of this step's lattice under the job's mask: decided once per sampler step, next to the lattice itself."""
+        if self._subset_at is None or self._subset_at[0] != step:
+            lat, boxes = self._lattice_at[1], self._lattice_at[2]
+            flags, slot = mdtile.lattice_activity(lat, self.skip_mask)
+            Ta, T = sum(1 for a in flags if a), len(flags)
+            if "first step" not in self._skip_notes:
+                self._skip_notes.add("first step")
+                print(f"[Tiled Diffusion] inpaint mask touches {Ta} of {T} tiles of the first step's grid (the grid and the count change every step)")
+            self.p.extra_generation_params["Tiled Diffusion jitter inpaint skip"] = True
+            batches = -(-Ta // max(1, self.requested_tile_bs))
+            if Ta == 0:
+                grid, boxes = lat, None
+            elif Ta == T:
+                grid = lat
+            elif batches > mdtile.MAX_BATCHES:      # the full lattice passed this limit in _init_grid_jitter with its own, larger, tile batches
+                self._skip_note(f"a step's {Ta} touched tiles make {batches} batches at tile batch size {self.requested_tile_bs}, more than the "
+                                f"{mdtile.MAX_BATCHES} a lattice subset carries (raise the tile batch size)")
+                grid = lat
+            else:
+                grid = mdtile.LatticeSubset(lat, flags, self.requested_tile_bs, slot)
+                boxes = [[BBox(*b) for b in batch] for batch in grid.batches]
+            self._subset_at = (step, grid, boxes)
+            # the progress bar follows the calls actually made: this step's batches instead of the budget it was sized with
+            self.total_bboxes = len(boxes) if boxes is not None else 0
+            if self.pbar is not None:
+                self.pbar.total += self.total_bboxes - self._bar_budget
+                self.pbar.refresh()
+        return self._subset_at[1], self._subset_at[2]
 
     # ---- --mdtile-inpaint-skip: only the tiles the job's latent mask touches ------------------------------------------------------------
     def _skip_note(self, reason: str):
@@ -453,7 +517,8 @@ class AbstractDiffusion:
 
     def inpaint_skip(self, own_evaluation: Optional[str] = None) -> str:
         """How this full-size evaluation runs: "full" (every tile), "sparse" (self.sparse_plan / self.sparse_batched_bboxes: the tiles the mask
-        touches) or "empty" (it touches none: the model is not called).  Decided once per job, on the first evaluation that asks -- the host
+        touches), "empty" (it touches none: the model is not called) or "lattice" (--mdtile-jitter-inpaint-skip with the grid moving: step_lattice
+        decides the active tiles of every step's lattice).  Decided once per job, on the first evaluation that asks -- the host
         computes p.nmask after the delegate is built.  own_evaluation: an evaluation that always runs full-canvas names itself here."""
         if not self.inpaint_skip_requested():
             return "full"
@@ -474,6 +539,9 @@ class AbstractDiffusion:
         mask = self._inpaint_mask()
         if mask is None:
             return "full"
+        if self.jitter_inpaint_skip_active():      # the grid moves: which tiles the mask touches is asked of every step's lattice (step_lattice)
+            self.skip_mask = mask
+            return "lattice"
         active = mdtile.tile_activity(self.plan, mask)
         Ta, T = sum(1 for a in active if a), len(active)
         print(f"[Tiled Diffusion] inpaint mask touches {Ta} of {T} tiles")

@@ -133,11 +133,17 @@ class MultiDiffusion(AbstractDiffusion):
             (sx, sy), batched_bboxes = self.step_shift(None if own_evaluation is None else self.NOISE_INVERSION_UNSHIFTED)
         if jitter is not None:
             lattice, batched_bboxes = jitter
+            if batched_bboxes is None:      # --mdtile-jitter-inpaint-skip: the mask touches no tile of this step's grid
+                return x_in.clone()
+        # --mdtile-jitter-inpaint-skip: the step's active tiles only, in compact batches (step_lattice hands the full lattice where all are active)
+        lattice_subset = jitter is not None and isinstance(lattice, mdtile.LatticeSubset)
 
         tile_outs: List[Tensor] = []
         if self.draw_background:
             # K2: every tile batch, one launch
-            if jitter is not None:
+            if lattice_subset:
+                x_tiles = mdtile.gather_all_lattice_sparse(lattice, x_in)
+            elif jitter is not None:
                 x_tiles = mdtile.gather_all_lattice(lattice, x_in)
             else:
                 x_tiles = mdtile.gather_all_shift(plan, x_in, sx, sy) if self.grid_shift else mdtile.gather_all(plan, x_in)
@@ -168,7 +174,9 @@ class MultiDiffusion(AbstractDiffusion):
             self.x_buffer = mdtile.blend_sparse(plan, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in, weights=self.weights)
             return self.x_buffer
         if jitter is not None:    # every tile where its lattice box lies; the step's weight sum is formed in the kernel
-            if self.jitter_regions:      # then the regions, where they are: only the grid moves
+            if lattice_subset:           # live pixels as the full lattice blend has them, x_in everywhere else (no regions on this path)
+                self.x_buffer = mdtile.blend_lattice_sparse(lattice, mdtile.METHOD_MD, tile_outs, N, C, fill=x_in)
+            elif self.jitter_regions:    # then the regions, where they are: only the grid moves
                 self.x_buffer = self.blend_lattice_regions(mdtile.METHOD_MD, lattice, tile_outs, region_outs, x_in)
             else:
                 self.x_buffer = mdtile.blend_lattice(lattice, mdtile.METHOD_MD, tile_outs, N, C)

@@ -472,6 +472,58 @@ int mdtile_gather_all_lattice_sparse(const mdtile_lattice_subset* sub, int dtype
 int mdtile_blend_lattice_sparse(const mdtile_lattice_subset* sub, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                                 const void* d_fill, mdtile_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Free-form mask regions beside the rectangles (csrc/mask_regions.hip, the blend kernel in csrc/blend.hip).  Nothing upstream
+ * corresponds to it.  A region keeps its rectangle (its bounding box: what is gathered, conditioned and evaluated) and gains a COVERAGE map,
+ * [h, w] bytes: region R covers canvas pixel (yc, xc) iff the pixel lies in R's rectangle and (cover == NULL or cover[off] != 0), off = ry * w + rx.
+ * Coverage is not a zero weight: upstream counts every pixel of a rectangle in fcnt and in the weight sums whatever its feather is, so two regions
+ * whose boxes overlap and whose shapes do not would leak into each other at half weight.  A region that does not cover a pixel takes no part in it.
+ *
+ * mdtile_mask_cover_u8: a painted mask d_mask [Hm, Wm] (device bytes; Hm >= H, Wm >= W, e.g. 8192 x 8192 for H = W = 1024) -> d_cover [H, W] bytes
+ *   (0 / 1) and d_box (device int32[5]).  Cell (y, x) owns mask rows [y*Hm/H, (y+1)*Hm/H) and columns [x*Wm/W, (x+1)*Wm/W) (integer division; never
+ *   empty); with s the byte sum and n the pixel count of that box, cover = (2*s >= 255*n) ? 1 : 0.  d_box = {xmin, ymin, xmax+1, ymax+1, count} of the
+ *   covered cells, {0,0,0,0,0} when there is none.  Two launches write every output; nothing is cleared beforehand; integers only, the same bits every
+ *   run.  Limits: H * W < 2^31 and at most 2^22 mask pixels per cell.
+ * mdtile_mask_region: the dense tensors of the region with rectangle (x, y, w, h) on the [H, W] coverage d_cover: d_rcover[i, j] = d_cover[y+i, x+j] != 0
+ *   (bytes 0 / 1) and, unless d_feather is NULL, its feather [h, w] fp32: R = int(min(w/2, h/2) * feather_ratio) as mdtile_feather_mask forms it (integer
+ *   halves, double product, truncation); for a covered cell k = the chessboard distance max(|di|, |dj|) to the nearest cell that is not covered, cells
+ *   outside the rectangle counting as not covered (k >= 1); d = k - 1; feather = d >= R ? 1.0f : (float)((double)d / (double)R)^2 -- the double
+ *   expression of mdtile_feather_mask; 0.0f in a cell that is not covered.  The search goes no further than R.  Chessboard and not Euclidean distance: it
+ *   is integer arithmetic and so has a bitwise definition, and for a fully covered rectangle with even w and h it is upstream's feather_mask bit for bit.
+ *   For odd w or h upstream leaves the middle row / column at 1.0 (a quirk of its quadrant loop); the distance form does NOT reproduce that.
+ * mdtile_blend_mask_regions: mdtile_blend on a plain plan where a region enters a pixel only if it covers it: the grid tiles in ascending tile index,
+ *   then the covering BG regions in list order (MD buf += v, MoD buf += v * weight[off], weight premultiplied as mdtile_blend takes it), MD's
+ *   weights > 1 ? buf / weights : buf, then the composite over the covering FG regions in list order (fbuf += v, fmask += weight[off], fcnt += 1,
+ *   averaged where fcnt > 1, x = x * (1 - fmask) + fbuf * fmask where fcnt > 0); fp32 without contraction, half I/O rounded once at the store.
+ *   num_batches == 0: regions only.  A region's output and weight are NOT READ at a pixel it does not cover.  d_weights / d_rescale are the host's maps,
+ *   made with the covers (MD: the cover as 0.0 / 1.0 through mdtile_weight_map_add_rect; MoD: gaussian * cover).  With every cover NULL or all ones the
+ *   result is mdtile_blend's bit for bit.  Always the register form of the kernel (no LDS form).
+ * mdtile_region_noise_masked: mdtile_region_noise with the same coverage rule; with every cover NULL it is mdtile_region_noise bit for bit.
+ * REFUSED (MDTILE_E_ARG, the text names the reason, nothing is written): null required pointers; bad sizes, dtypes, methods or modes; a rectangle that
+ *   leaves the canvas; more than MDTILE_MAX_REGIONS regions; and by mdtile_blend_mask_regions a wrap-around plan, a sparse plan, any MDTILE_BLEND_* flag
+ *   and a row band; by mdtile_mask_cover_u8 a mask smaller than the latent canvas on either axis (Wm < W or Hm < H: a cell would own no mask pixel).
+ * What mask regions are NOT combined with, each refused or set aside by name:
+ *   wrap-around canvases (--mdtile-wrap-x / --mdtile-wrap-y), with or without --mdtile-wrap-regions   the plugin raises RuntimeError; this call refuses the plan
+ *   Noise Inversion                                               the plugin raises RuntimeError (mdtile_noise_inverse_blend knows rectangles only)
+ *   --mdtile-grid-jitter with --mdtile-jitter-regions             the fixed grid runs, one line through the jitter note (mdtile_blend_lattice_regions takes no cover)
+ *   --mdtile-inpaint-skip                                         stands down as with every region job (this call refuses a sparse plan)
+ *   ShardedBlend (mdtile/sharding.py, the multi-GPU blend)        refuses a region with a cover (this call refuses partial sums, tile ranges and row bands)
+ *   a mask smaller than the latent canvas on either axis          the plugin raises RuntimeError before the call; the call refuses it too
+ * -------------------------------------------------------------------------------------------------------- */
+/* The struct has a tag and no typedef: the function mdtile_mask_region owns the plain name, so the type is written `struct mdtile_mask_region` (C and
+ * C++ both keep tags apart from functions). */
+struct mdtile_mask_region {
+    mdtile_region r;
+    const unsigned char* cover;   /* [h, w], NULL = the whole rectangle */
+};
+int mdtile_mask_cover_u8(const unsigned char* d_mask, int Wm, int Hm, int W, int H, unsigned char* d_cover, int* d_box, mdtile_stream_t stream);
+int mdtile_mask_region(const unsigned char* d_cover, int W, int H, int x, int y, int w, int h, double feather_ratio, unsigned char* d_rcover,
+                       float* d_feather /* may be NULL */, mdtile_stream_t stream);
+int mdtile_blend_mask_regions(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                              const struct mdtile_mask_region* regions, int num_regions, mdtile_stream_t stream);
+int mdtile_region_noise_masked(float* d_noise, int N, int C, int H, int W, const struct mdtile_mask_region* regions, int num_regions,
+                               mdtile_stream_t stream);
+
 /* Per-region initial noise (scripts/tilediffusion.py:486-529, create_random_tensors_hijack): d_noise [N,C,H,W] fp32 is the job's
  * noise, updated in place.  regions[i].out = the region's own noise [1,C,h,w] fp32 (drawn by the host with the region's CPU
  * seed, shared by all N samples), .mode = MDTILE_REGION_BG / _FG, .weight unused.  Per layer: sum + hit count over the regions

@@ -48,6 +48,13 @@ struct BlendParams {
     const void* batch[MDTILE_MAX_BATCHES];
 };
 static_assert(sizeof(BlendParams) <= 4096, "kernel argument block must stay under 4 KiB");
+// mdtile_blend_mask_regions: the same block with one coverage map per region behind it, [h, w] bytes or null = the whole rectangle.
+// Only the MASKED instantiations of k_blend take it; every other kernel keeps BlendParams.
+struct BlendParamsMasked : BlendParams {
+    const unsigned char* cover[MDTILE_MAX_REGIONS];
+};
+static_assert(sizeof(BlendParamsMasked) <= 4096, "kernel argument block must stay under 4 KiB");
+template <bool MASKED> using BlendArgs = std::conditional_t<MASKED, BlendParamsMasked, BlendParams>;
 
 // Shared epilogue: MD normalisation (multidiffusion.py:208) and the foreground feather composite
 // (multidiffusion.py:211-216 == mixtureofdiffusers.py:170-175), for one pixel.
@@ -150,22 +157,53 @@ __device__ __forceinline__ const T* tile_base(const BlendParams& P, int t) {
     return reinterpret_cast<const T*>(P.batch[b]) + (size_t)i * P.N * P.C * tile_elems;
 }
 
+// MASKED: which of the quad's pixels region R COVERS in its row ry (0 <= ry < R.h), bit j = pixel x0 + j: inside the rectangle's columns and, with a
+// coverage map, a non-zero byte at off = ry * R.w + rx.  A quad that lies inside the rectangle takes its 4 cover bytes with ONE load (a byte-aligned
+// dword: gfx950 runs in unaligned-access mode), shared by every plane of the thread; a quad that straddles the rectangle's edge reads per pixel.
+struct __attribute__((packed, aligned(1))) u8x4_u { unsigned v; };
+__device__ __forceinline__ unsigned cover_bits(const mdtile_region& R, const unsigned char* cover, int ry, int x0, int nvalid) {
+    const int rx0 = x0 - R.x;
+    unsigned m = 0u;
+    if (cover && nvalid == 4 && rx0 >= 0 && rx0 + 3 < R.w) {
+        const unsigned c4 = reinterpret_cast<const u8x4_u*>(cover + (size_t)ry * R.w + rx0)->v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m |= ((c4 >> (8 * j)) & 0xffu) ? 1u << j : 0u;
+        return m;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int rx = rx0 + j;
+        if (j >= nvalid || rx < 0 || rx >= R.w) continue;
+        if (!cover || cover[(size_t)ry * R.w + rx] != 0) m |= 1u << j;
+    }
+    return m;
+}
+
 // Shared tail of both blend kernels, for one thread's quad x PP planes: background regions (in list order, after every grid tile:
 // multidiffusion.py:189-190, mixtureofdiffusers.py:152-153), MD normalisation (:208), foreground feather composite (:191-198, :211-216 ==
 // mixtureofdiffusers.py:154-161, :170-175), store.  wq = the MD weight sum of the quad (loaded up front by the caller).
-template <typename T, int METHOD, int PP>
-__device__ __forceinline__ void blend_tail(const BlendParams& P, float (&acc)[PP][4], const float (&wq)[4], int y, int x0, int p0, int nvalid) {
+// MASKED (mdtile_blend_mask_regions): a region enters a pixel only where it COVERS it (cover_bits); its output and weight are not read elsewhere.  The
+// arithmetic per pixel is the same, term for term and in the same order.
+template <typename T, int METHOD, int PP, bool MASKED = false>
+__device__ __forceinline__ void blend_tail(const BlendArgs<MASKED>& P, float (&acc)[PP][4], const float (&wq)[4], int y, int x0, int p0, int nvalid) {
     // background regions, in list order, after every grid tile (multidiffusion.py:189-190, mixtureofdiffusers.py:152-153)
     for (int k = 0; k < P.num_regions; ++k) {
         const mdtile_region& R = P.regions[k];
         if (R.mode != MDTILE_REGION_BG) continue;
         const int ry = y - R.y;
         if (ry < 0 || ry >= R.h) continue;
+        unsigned cm = 0xfu;
+        if constexpr (MASKED) {
+            cm = cover_bits(R, P.cover[k], ry, x0, nvalid);
+            if (!cm) continue;
+        }
         const size_t rplane = (size_t)R.h * R.w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int rx = x0 + j - R.x;
             if (j >= nvalid || rx < 0 || rx >= R.w) continue;
+            if constexpr (MASKED)
+                if (!((cm >> j) & 1u)) continue;
             const size_t off = (size_t)ry * R.w + rx;
             const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
             const float wgt = METHOD == MDTILE_METHOD_MOD ? R.weight[off] : 1.0f;
@@ -216,7 +254,50 @@ __device__ __forceinline__ void blend_tail(const BlendParams& P, float (&acc)[PP
     }
 
     // foreground feather composite (multidiffusion.py:191-198, 211-216 == mixtureofdiffusers.py:154-161, 170-175)
-    if (P.num_fg > 0) {
+    if constexpr (MASKED) {
+        // regions outside, pixels inside: one cover load per region and quad.  Each pixel still sums its covering regions in list order.
+        if (P.num_fg > 0) {
+            float fbuf[PP][4], fmask[4], fcnt[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                fmask[j] = 0.0f;
+                fcnt[j] = 0.0f;
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) fbuf[pp][j] = 0.0f;
+            }
+            for (int k = 0; k < P.num_regions; ++k) {
+                const mdtile_region& R = P.regions[k];
+                if (R.mode != MDTILE_REGION_FG) continue;
+                const int ry = y - R.y;
+                if (ry < 0 || ry >= R.h) continue;
+                const unsigned cm = cover_bits(R, P.cover[k], ry, x0, nvalid);
+                if (!cm) continue;
+                const size_t rplane = (size_t)R.h * R.w;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!((cm >> j) & 1u)) continue;
+                    const size_t off = (size_t)ry * R.w + (x0 + j - R.x);
+                    const T* src = reinterpret_cast<const T*>(R.out) + (size_t)p0 * rplane + off;
+#pragma unroll
+                    for (int pp = 0; pp < PP; ++pp) fbuf[pp][j] += to_f32<T>(src[(size_t)pp * rplane]);
+                    fmask[j] += R.weight[off];
+                    fcnt[j] += 1.0f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= nvalid || !(fcnt[j] > 0.0f)) continue;
+                float fm = fmask[j];
+                if (fcnt[j] > 1.0f) fm = fm / fcnt[j];
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) {
+                    float fb = fbuf[pp][j];
+                    if (fcnt[j] > 1.0f) fb = fb / fcnt[j];
+                    acc[pp][j] = acc[pp][j] * (1.0f - fm) + fb * fm;
+                }
+            }
+        }
+    } else if (P.num_fg > 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= nvalid) continue;
@@ -259,8 +340,8 @@ __device__ __forceinline__ void blend_tail(const BlendParams& P, float (&acc)[PP
     }
 }
 
-template <typename T, int METHOD, int PP, int G, bool PACKED>
-__global__ __launch_bounds__(256) void k_blend(const BlendParams P) {
+template <typename T, int METHOD, int PP, int G, bool PACKED, bool MASKED = false>
+__global__ __launch_bounds__(256) void k_blend(const BlendArgs<MASKED> P) {
     const int W4 = (P.W + 3) >> 2;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= W4 * P.nrows) return;
@@ -419,7 +500,7 @@ __global__ __launch_bounds__(256) void k_blend(const BlendParams P) {
         }
     }
 
-    blend_tail<T, METHOD, PP>(P, acc, wq, y, x0, p0, nvalid);
+    blend_tail<T, METHOD, PP, MASKED>(P, acc, wq, y, x0, p0, nvalid);
 }
 
 // ---- the LDS-staged form (see the file header) ------------------------------------------------------------------------
@@ -621,6 +702,14 @@ void launch_blend_cfg(const BlendParams& P, int method, hipStream_t s) {
     }
 }
 
+// the MASKED instantiations (mdtile_blend_mask_regions: no flags, so never packed)
+template <typename T, int PP, int G>
+void launch_blend_masked_cfg(const BlendParamsMasked& P, int method, hipStream_t s) {
+    dim3 grid(cdiv((long long)P.nrows * ((P.W + 3) / 4), 256), (P.N * P.C) / PP), block(256);
+    if (method == MDTILE_METHOD_MD) hipLaunchKernelGGL((k_blend<T, MDTILE_METHOD_MD, PP, G, false, true>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((k_blend<T, MDTILE_METHOD_MOD, PP, G, false, true>), grid, block, 0, s, P);
+}
+
 // k_blend_lds: does it take this launch, and in what shape?
 //   WHERE IT PAYS (profiles/r6e, cold, same process): grids whose tile origins are not all multiples of 4 -- the 96 / 48 class, upstream's
 //   default tile settings -- where k_blend's edge quads take per-element loads and nearly every wave runs both branches: 4096^2
@@ -660,13 +749,13 @@ struct BlendDispatch {
 
 // census: also count k_blend's quads per load path (the query's extra; a launch has no use for it and does not pay for it)
 static BlendDispatch blend_dispatch(const mdtile_plan* plan, int elem_bytes, int N, int C, int flags, int num_batches, bool ptrs_aligned16,
-                                    int row_lo, int nrows, bool census) {
+                                    int row_lo, int nrows, bool census, bool lds_allowed = true) {
     BlendDispatch D = {MDTILE_BLEND_KERNEL_PLAIN, 0, 0, 0, 0, 0, 0, 0};
     (void)flags;      // tile range, partial sums and the packed form are runtime branches of both kernels: today no flag moves a launch to the other one
     const int planes = N * C, W = plan->w, tw = plan->tw;
     // k_blend_lds: does it take this launch?  (see the comment above launch_blend_lds_cfg)
     const int row_bytes = tw * elem_bytes;
-    bool lds_ok = num_batches > 0 && row_bytes % 16 == 0 && row_bytes <= 1024 && plan->nc_max <= 3 && plan->nr_max <= 3 && plan->nc_max >= 1 &&
+    bool lds_ok = lds_allowed && num_batches > 0 && row_bytes % 16 == 0 && row_bytes <= 1024 && plan->nc_max <= 3 && plan->nr_max <= 3 && plan->nc_max >= 1 &&
                   ptrs_aligned16;
     if (lds_ok) {
         int SQ = 256, lpp_forced = 0;
@@ -825,6 +914,30 @@ int fill_params(BlendParams& P, const mdtile_plan* p, const mdtile_blend_args* a
 }
 
 }  // namespace
+
+// mdtile_blend_mask_regions (mask_regions.hip) has checked the plan, the flags, the row band and the list; fill_params repeats mdtile_blend's tests of the rest.
+// Always k_blend: the masked call has no LDS form.
+int mdt::blend_masked(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches, const struct mdtile_mask_region* regions,
+                      int num_regions, hipStream_t s) {
+    mdtile_region plain[MDTILE_MAX_REGIONS];
+    for (int k = 0; k < num_regions; ++k) plain[k] = regions[k].r;
+    BlendParamsMasked P;
+    memset(static_cast<void*>(&P), 0, sizeof(P));
+    if (int rc = fill_params(P, plan, args, batch_out, num_batches, plain, num_regions)) return rc;
+    for (int k = 0; k < num_regions; ++k) P.cover[k] = regions[k].cover;
+    const int method = args->method;
+    return with_dtype(args->dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        const BlendDispatch D = blend_dispatch(plan, (int)sizeof(T), P.N, P.C, P.flags, P.num_batches, batch_ptrs_aligned16(P), P.row_lo, P.nrows, false, false);
+        // the four (planes, candidates) forms the heuristic reaches; (8,4) and (4,2) exist for the probes' MDTILE_BLEND_CFG only and have no MASKED twin
+        if (D.planes == 8) launch_blend_masked_cfg<T, 8, 2>(P, method, s);
+        else if (D.planes == 4) launch_blend_masked_cfg<T, 4, 4>(P, method, s);
+        else if (D.planes == 2) launch_blend_masked_cfg<T, 2, 4>(P, method, s);
+        else launch_blend_masked_cfg<T, 1, 4>(P, method, s);
+        MDT_LAUNCH_CHECK();
+        return (int)MDTILE_OK;
+    });
+}
 
 extern "C" int mdtile_blend(const mdtile_plan* plan, const mdtile_blend_args* args, const void* const* batch_out, int num_batches,
                             const mdtile_region* regions, int num_regions, mdtile_stream_t stream) {

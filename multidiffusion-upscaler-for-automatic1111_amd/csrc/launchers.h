@@ -27,6 +27,11 @@ int walk_blend_regions(const struct ::mdtile_plan* plan, const ::mdtile_blend_ar
 // what every shifted entry point (wrap.hip, wrap_regions.hip) asks of the plan and the shift before anything else is looked at; errors name `fn`
 int shift_check(const char* fn, const struct ::mdtile_plan* plan, int sx, int sy);
 
+// ---- blend.hip: the plain blend with a coverage map per region: mdtile_blend_mask_regions (mask_regions.hip) has refused what the call does not
+// take and checked the list; k_blend<..., MASKED = true>, whose text has the arithmetic
+int blend_masked(const struct ::mdtile_plan* plan, const ::mdtile_blend_args* args, const void* const* batch_out, int num_batches,
+                 const struct ::mdtile_mask_region* regions, int num_regions, hipStream_t s);
+
 // ---- vae_assemble.hip: mdtile_vae_assemble in two halves, for vae_skip.hip (mdtile_vae_assemble_sparse pastes its tiles with them).
 // vae_assemble_check: every test of the table and the result, the peer mapping of every source device; errors name `who`.
 int device_of(const void* p);      // the device that owns `p` (device memory of this process), or -1

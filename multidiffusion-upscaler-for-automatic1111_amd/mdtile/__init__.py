@@ -53,6 +53,10 @@ class _Region(ctypes.Structure):
                 ("out", c_void_p), ("weight", c_void_p)]
 
 
+class _MaskRegion(ctypes.Structure):
+    _fields_ = [("r", _Region), ("cover", c_void_p)]
+
+
 class _P2P(ctypes.Structure):
     _fields_ = [("peer", c_int), ("send", c_void_p), ("send_bytes", c_size_t), ("recv", c_void_p), ("recv_bytes", c_size_t)]
 
@@ -134,6 +138,10 @@ _SIGNATURES = {
     "mdtile_lattice_subset_bboxes": (c_int, [POINTER(_LatticeSubset), _IP, _IP, _IP]),
     "mdtile_gather_all_lattice_sparse": (c_int, [POINTER(_LatticeSubset), c_int, c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_void_p]),
     "mdtile_blend_lattice_sparse": (c_int, [POINTER(_LatticeSubset), POINTER(_BlendArgs), POINTER(c_void_p), c_int, c_void_p, c_void_p]),
+    "mdtile_mask_cover_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mdtile_mask_region": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "mdtile_blend_mask_regions": (c_int, [c_void_p, POINTER(_BlendArgs), POINTER(c_void_p), c_int, POINTER(_MaskRegion), c_int, c_void_p]),
+    "mdtile_region_noise_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_MaskRegion), c_int, c_void_p]),
     "mdtile_region_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_noise_inverse_blend": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(_Region), c_int, c_void_p]),
     "mdtile_retouch_mask_ws_size": (c_size_t, [c_int, c_int, c_int]),
@@ -589,6 +597,55 @@ def region_noise(noise: torch.Tensor, regions) -> torch.Tensor:
     return noise
 
 
+def region_noise_masked(noise: torch.Tensor, regions) -> torch.Tensor:
+    """region_noise where a region counts only at the pixels it covers.  regions: [(x, y, w, h, mode, rand, cover)], cover = uint8 [h, w] on the
+    device or None (the whole rectangle)."""
+    _dev_tensor(noise, "noise", torch.float32)
+    N, C, H, W = noise.shape
+    plain, keep = _noise_regions_array(noise, [r[:6] for r in regions])
+    arr = (_MaskRegion * max(1, len(regions)))()
+    for i, r in enumerate(regions):
+        arr[i] = _MaskRegion(plain[i], _cover_ptr(r[6], r[2], r[3], f"regions[{i}].cover", keep))
+    _check(lib().mdtile_region_noise_masked(_p(noise), N, C, H, W, arr, len(regions), _stream()), "mdtile_region_noise_masked")
+    return noise
+
+
+def _cover_ptr(cover, w: int, h: int, name: str, keep: list) -> int:
+    """The address of a region's coverage map (uint8 [h, w], contiguous, on the device), or 0 for None."""
+    if cover is None:
+        return 0
+    _dev_tensor(cover, name, torch.uint8)
+    assert cover.numel() == w * h, f"{name} {tuple(cover.shape)} vs rect {h}x{w}"
+    keep.append(cover)
+    return cover.data_ptr()
+
+
+def mask_cover_u8(mask: torch.Tensor, w: int, h: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A painted mask [Hm, Wm] (uint8 on the device, Hm >= h, Wm >= w) -> (cover uint8 [h, w] of 0 / 1, box int32[5] = {xmin, ymin, xmax + 1,
+    ymax + 1, count} of the covered cells, zeros when there is none), both on the device: a cell is covered when at least half of the mask pixels it
+    owns, weighted by their value, are set (2 * sum >= 255 * count).  No synchronisation: read the box with .tolist() when it is needed."""
+    _dev_tensor(mask, "mask", torch.uint8)
+    assert mask.dim() == 2, f"mask {tuple(mask.shape)}"
+    cover = torch.empty((int(h), int(w)), dtype=torch.uint8, device=mask.device)
+    box = torch.empty(5, dtype=torch.int32, device=mask.device)
+    _check(lib().mdtile_mask_cover_u8(_p(mask), mask.shape[1], mask.shape[0], int(w), int(h), _p(cover), _p(box), _stream()), "mdtile_mask_cover_u8")
+    return cover, box
+
+
+def mask_region(cover: torch.Tensor, x: int, y: int, w: int, h: int, feather_ratio: Optional[float] = None):
+    """The dense tensors of the region (x, y, w, h) on a canvas coverage [H, W]: (rcover uint8 [h, w], feather fp32 [h, w] or None when
+    feather_ratio is None).  The feather falls off with the chessboard distance to the nearest cell that is not covered (include/mdtile.h)."""
+    _dev_tensor(cover, "cover", torch.uint8)
+    assert cover.dim() == 2, f"cover {tuple(cover.shape)}"
+    H, W = cover.shape
+    ok = w > 0 and h > 0      # the library refuses the rest by name; a bad size must not reach torch.empty
+    rcover = torch.empty((h, w) if ok else (1, 1), dtype=torch.uint8, device=cover.device)
+    feather = None if feather_ratio is None else torch.empty((h, w) if ok else (1, 1), dtype=torch.float32, device=cover.device)
+    _check(lib().mdtile_mask_region(_p(cover), W, H, int(x), int(y), int(w), int(h), float(feather_ratio or 0.0), _p(rcover), _p(feather), _stream()),
+           "mdtile_mask_region")
+    return rcover, feather
+
+
 def noise_inverse_blend(noise: torch.Tensor, inverse_noise: torch.Tensor, renoise_mask: torch.Tensor, regions=()) -> torch.Tensor:
     """Renoise composite of Noise Inversion (abstractdiffusion.py:651-676).  noise / inverse_noise [N,C,H,W] fp32, renoise_mask
     [H,W] fp32; regions: [(x, y, w, h, mode, feather [h,w] fp32 or None)] -- pass them only when the grid is disabled (:658)."""
@@ -936,10 +993,11 @@ def gather_rect_wrap(x_in: torch.Tensor, x: int, y: int, w: int, h: int, *, wrap
 class RegionSpec:
     """One custom region for the blend: rect, mode, its model output and (optional) weight / feather map."""
 
-    __slots__ = ("x", "y", "w", "h", "mode", "out", "weight")
+    __slots__ = ("x", "y", "w", "h", "mode", "out", "weight", "cover")
 
-    def __init__(self, x, y, w, h, mode, out, weight=None):
+    def __init__(self, x, y, w, h, mode, out, weight=None, cover=None):
         self.x, self.y, self.w, self.h, self.mode, self.out, self.weight = x, y, w, h, mode, out, weight
+        self.cover = cover      # uint8 [h, w] on the device: where the region counts (blend_mask_regions); None = the whole rectangle
 
 
 def _regions_array(regions: Sequence[RegionSpec], dtype, limit: bool = True):
@@ -1133,6 +1191,21 @@ def blend_wrap_regions(plan: Plan, method: int, batch_out: Sequence[torch.Tensor
     rarr, _keep = _region_operands(regions, N, C, dtype)
     wr = _WrapRegions(rarr, len(regions), _p(grid_w).value, _p(region_w).value, int(sx), int(sy))
     _check(lib().mdtile_blend_wrap_regions(plan.handle, ctypes.byref(a), ptrs, len(batch_out), ctypes.byref(wr), _stream()), "mdtile_blend_wrap_regions")
+    return out
+
+
+def blend_mask_regions(plan: Plan, method: int, batch_out: Sequence[torch.Tensor], N: int, C: int, *, regions: Sequence[RegionSpec] = (), weights=None,
+                       tile_w=None, rescale=None, out: Optional[torch.Tensor] = None, dtype=None, device=None, flags: int = 0, row_range=None) -> torch.Tensor:
+    """blend on a plain plan where region r enters a pixel only if it covers it (r.cover, uint8 [h, w]; None = the whole rectangle), one launch.  A
+    region's output and weight are not read elsewhere.  weights / rescale are the host's maps, made WITH the covers; a BG region's weight under Mixture
+    of Diffusers is premultiplied as blend takes it.  flags / row_range exist only to be refused: the library takes neither here."""
+    dtype, device = _batch_operands(plan, batch_out, N, C, dtype, device, strict=False, regions=regions)
+    out, a, ptrs = _blend_operands(plan, method, batch_out, N, C, dtype, dtype, device, out, weights, tile_w, rescale, flags, None, row_range)
+    rarr, keep = _region_operands(regions, N, C, dtype)
+    marr = (_MaskRegion * max(1, len(regions)))()
+    for i, r in enumerate(regions):
+        marr[i] = _MaskRegion(rarr[i], _cover_ptr(r.cover, r.w, r.h, f"region[{i}].cover", keep))
+    _check(lib().mdtile_blend_mask_regions(plan.handle, ctypes.byref(a), ptrs, len(batch_out), marr, len(regions), _stream()), "mdtile_blend_mask_regions")
     return out
 
 

@@ -433,6 +433,7 @@ class ShardedBlend:
     so the shared rows are not counted twice), a foreground region is composited by every rank on the rows it finalises.
 
         sb = ShardedBlend(shard, W, H, tile_w, tile_h, overlap, tile_bs, method, regions=[(x, y, w, h, mode, feather_ratio)])
+    (a region with a cover -- a mask region, DESIGN.md 3.22 -- is refused by name)
         outs = sb.step(xs, tile_fn, region_fn)      xs / outs: one [N, C, H, W] canvas per LOCAL rank, on that rank's device
     After step() canvas i is complete on the rows band i touches (what its tiles need for the next evaluation); allgather_rows()
     completes all of them (single-process contexts)."""
@@ -440,7 +441,11 @@ class ShardedBlend:
     def __init__(self, shard, W: int, H: int, tile_w: int, tile_h: int, overlap: int, tile_bs: int, method: int, regions=()):
         import mdtile
         self.E, self.shard, self.method, self.W, self.H = mdtile, shard, method, W, H
-        self.regions = list(regions)
+        for k, r in enumerate(regions):      # (x, y, w, h, mode, feather_ratio[, cover]): a seventh field may only say "no cover"
+            if len(r) > 6 and r[6] is not None:
+                raise mdtile.MdtileError(f"ShardedBlend: region {k} has a cover (a mask region): mask regions are not combined with the multi-GPU "
+                                         "path (row bands, partial sums); blend on one device with mdtile.blend_mask_regions")
+        self.regions = [tuple(r[:6]) for r in regions]
         self.local = []
         for i, dev in enumerate(shard.devices):
             with torch.cuda.device(dev):

@@ -84,3 +84,13 @@ def preload(parser):
              "step to step. Without this option such a job skips tiles on the fixed grid, as before. Ignored (one line) without one of the two "
              "options it builds on. Region control, wrap-around canvases and a job without a mask run as with --mdtile-grid-jitter alone; Noise "
              "Inversion's own evaluations stay on the fixed grid with every tile; DemoFusion does not read it. Default: off.")
+    parser.add_argument(
+        "--mdtile-region-masks", type=str, default=None, metavar="DIR",
+        help="Tiled Diffusion region prompt control (MultiDiffusion, Mixture of Diffusers): free-form regions. A file DIR/region<k>.png (k = the "
+             "region's number in the UI, from 1; any image Pillow reads, taken as greyscale) is region k's painted mask: the region counts "
+             "exactly where at least half of a latent pixel's mask is painted, its rectangle becomes the mask's bounding box (the x, y, w, h "
+             "of the UI are ignored), and a foreground region feathers along the painted shape. API callers set p.mdtile_region_masks = {k: PIL "
+             "image or path}, which wins over DIR. Regions without a file stay rectangles. Refused by name: wrap-around canvases "
+             "(--mdtile-wrap-x / --mdtile-wrap-y, with or without --mdtile-wrap-regions), Noise Inversion, a mask smaller than the latent canvas on "
+             "either axis, and ShardedBlend (the multi-GPU blend). With --mdtile-grid-jitter and --mdtile-jitter-regions the fixed grid runs "
+             "(one line); --mdtile-inpaint-skip stands down as with every region job. Default: not set, every region is a rectangle.")

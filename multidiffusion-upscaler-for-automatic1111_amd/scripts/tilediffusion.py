@@ -179,6 +179,8 @@ class Script(scripts.Script):
                              "NoiseInv Renoise strength": noise_inverse_renoise_strength, "NoiseInv Kernel size": noise_inverse_renoise_kernel})
         if bbox_settings:
             info["Region control"] = {f"Region {i + 1}": s._asdict() for i, s in bbox_settings.items()}
+            # --mdtile-region-masks / p.mdtile_region_masks: a region that is a painted mask gets its "mask" entry (the file name, or "<image>")
+            # from the delegate's init_custom_bbox, once it is known that the mask covers anything
         if not hasattr(p, "extra_generation_params") or p.extra_generation_params is None:
             p.extra_generation_params = {}
         p.extra_generation_params["Tiled Diffusion"] = info
@@ -313,22 +315,38 @@ class Script(scripts.Script):
         # on the circle, and each region's noise goes where its rectangle is
         d = self.delegate
         wrap_x, wrap_y = (d.wrap_x, d.wrap_y) if d is not None and d.wrap_regions else (False, False)
+        # mask regions: the delegate has turned every painted mask into a rectangle (the mask's bounding box) and a cover; a region's noise is drawn
+        # for that box and pasted where the region covers.  A mask that covers nothing has no region at the delegate and none here
+        # Noise of another size than the delegate's canvas (a hires pass): a mask region has no rectangle there -- its fx, fy, fw, fh are
+        # ignored by definition -- so it draws no noise of its own; the rectangles are laid by the rule as before
+        painted = set(getattr(d, "mask_region_indices", ())) if d is not None else set()
+        masked = bool(painted) and (d.w, d.h) == (width, height)
+        laid = {b.index: b for b in d.custom_bboxes} if masked else {}
         regions = []
         for i, v in bbox_settings.items():
+            if i in painted and i not in laid:      # dropped (its mask covers nothing), or the noise is not the canvas's size
+                continue
             seed = get_fixed_seed(v.seed)
-            x, y, w, h = region_rect(v.x, v.y, v.w, v.h, width, height, wrap_x, wrap_y)
+            cover = None
+            if masked:
+                b = laid[i]
+                x, y, w, h, cover = b.x, b.y, b.w, b.h, b.cover
+            else:
+                x, y, w, h = region_rect(v.x, v.y, v.w, v.h, width, height, wrap_x, wrap_y)
             torch.manual_seed(seed)
             rand = torch.randn((1, noise.shape[1], h, w), device=devices.cpu)
             mode = BlendMode(v.blend_mode)
             if mode not in (BlendMode.BACKGROUND, BlendMode.FOREGROUND):
                 raise NotImplementedError
             regions.append((x, y, w, h, mdtile.REGION_BG if mode == BlendMode.BACKGROUND else mdtile.REGION_FG,
-                            rand.to(device=noise.device, dtype=torch.float32).contiguous()))
+                            rand.to(device=noise.device, dtype=torch.float32).contiguous()) + ((cover,) if masked else ()))
             key = "Region " + str(i + 1)
             if key in region_info:
                 region_info[key]["seed"] = seed
         work = noise.to(torch.float32).contiguous()
-        if wrap_x or wrap_y:
+        if masked:
+            mdtile.region_noise_masked(work, regions)
+        elif wrap_x or wrap_y:
             mdtile.region_noise_wrap(work, regions, wrap_x=wrap_x, wrap_y=wrap_y)
         else:
             mdtile.region_noise(work, regions)

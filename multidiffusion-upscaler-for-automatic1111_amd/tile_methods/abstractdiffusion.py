@@ -25,7 +25,7 @@ from modules.processing import opt_f
 
 import mdtile
 from tile_utils.utils import (BBox, BBoxSettings, BlendMode, Condition, CustomBBox, NoiseInverseCache, Prompt, get_retouch_mask, grid_shift,
-                              lattice_shift, region_rect, shifted_bboxes)
+                              lattice_shift, load_region_mask, region_mask_sources, region_rect, shifted_bboxes)
 
 try:  # isinstance targets; absent in a bare test host
     from modules.sd_samplers_kdiffusion import KDiffusionSampler
@@ -117,6 +117,10 @@ class AbstractDiffusion:
         # sum WITH the regions (Noise Inversion's own evaluations and every other fixed-grid evaluation of the job need it), region_w holds the
         # background regions' sum alone: the lattice blend adds it to the step's grid sum per pixel
         self.jitter_regions = False
+        # mask regions (--mdtile-region-masks / p.mdtile_region_masks): at least one region is a painted mask, its rectangle the
+        # mask's bounding box and its CustomBBox.cover the pixels it counts for.  The evaluation's blend then goes through blend_mask_regions
+        self.mask_regions = False
+        self.mask_region_indices: set = set()        # keys of bbox_settings whose region is a painted mask, the dropped ones included
 
         # optional extensions, armed by the init_* calls of the Script
         self.noise_inverse_enabled = False
@@ -440,6 +444,8 @@ class AbstractDiffusion:
         if own_evaluation is not None:
             return self._jitter_note(own_evaluation)
         if not self.jitter_regions and (self.enable_custom_bbox or not self.draw_background):
+            if self.mask_regions and self.jitter_regions_requested():
+                return self._jitter_note(self.MASK_REGIONS_FIXED_GRID)
             if self.jitter_regions_requested() and not self.draw_background:
                 return self._jitter_note(self.NO_BACKGROUND_TO_MOVE)
             return self._jitter_note("region prompt control is enabled (custom regions, or no background to draw)")
@@ -574,8 +580,46 @@ class AbstractDiffusion:
             raise RuntimeError(f"[Tiled Diffusion] {opts} cannot be combined with {what}: the wrap-around blend has no "
                                "region path. Turn one of them off." + hint)
 
-    # ------------------------------------------------------------------------------------------------ regions
+    MASK_REGIONS_FIXED_GRID = "a region is a painted mask (mask regions are not combined with --mdtile-jitter-regions)"
+
+    def _mask_region(self, number: int, src, blend_mode: str, feather_ratio: float):
+        """(x, y, w, h, cover, feather) of the region painted in mask `src`, or None when the mask covers no latent pixel: the rectangle is the
+        bounding box of the coverage (the one small copy to the host per region and job), cover and feather come from mdtile.mask_region."""
+        mask = load_region_mask(src)
+        if mask.shape[0] < self.h or mask.shape[1] < self.w:
+            raise RuntimeError(f"[Tiled Diffusion] the mask of region {number} ({mask.shape[1]} x {mask.shape[0]} px) is smaller than the latent canvas "
+                               f"({self.w} x {self.h}) on an axis: paint it at the size of the image (or any size from the latent canvas up).")
+        cover, box = mdtile.mask_cover_u8(mask, self.w, self.h)
+        x0, y0, x1, y1, count = box.tolist()
+        if count == 0:
+            print(f"[Tiled Diffusion] region {number} dropped: its mask covers no pixel of the {self.w} x {self.h} latent canvas.")
+            return None
+        fg = BlendMode(blend_mode) == BlendMode.FOREGROUND
+        ratio = max(min(feather_ratio, 1.0), 0.0)      # CustomBBox's clamp
+        rcover, feather = mdtile.mask_region(cover, x0, y0, x1 - x0, y1 - y0, ratio if fg else None)
+        return x0, y0, x1 - x0, y1 - y0, rcover, feather
+
+    def _record_mask(self, index: int, name: Optional[str]):
+        """extra_generation_params["Tiled Diffusion"]["Region control"]["Region k"]["mask"] = the file name or "<image>" of a mask that takes part;
+        a mask that covered nothing (name None) dropped its region and is not recorded."""
+        info = (getattr(self.p, "extra_generation_params", None) or {}).get("Tiled Diffusion")
+        region = info.get("Region control", {}).get(f"Region {index + 1}") if isinstance(info, dict) else None
+        if isinstance(region, dict):
+            if name is None:
+                region.pop("mask", None)
+            else:
+                region["mask"] = name
+
     def init_custom_bbox(self, bbox_settings: Dict[int, BBoxSettings], draw_background: bool, causal_layers: bool):
+        masks = region_mask_sources(self.p, [i for i, s in bbox_settings.items() if s.enable])
+        if masks and (self.wrap_x or self.wrap_y):
+            opts = " / ".join(o for o, on in (("--mdtile-wrap-x", self.wrap_x), ("--mdtile-wrap-y", self.wrap_y)) if on)
+            raise RuntimeError(f"[Tiled Diffusion] mask regions (--mdtile-region-masks / p.mdtile_region_masks) cannot be combined with {opts}, with or "
+                               "without --mdtile-wrap-regions: the masked blend runs on a plain canvas only. Turn one of them off.")
+        if masks and self.noise_inverse_enabled:
+            raise RuntimeError("[Tiled Diffusion] mask regions (--mdtile-region-masks / p.mdtile_region_masks) cannot be combined with Noise Inversion: "
+                               "its renoise composite and its own evaluations know rectangles only. Turn one of them off.")
+        self.mask_region_indices = set(masks)
         wrap_regions = self.wrap_regions_requested()
         if wrap_regions and not (self.wrap_x or self.wrap_y):
             print("[Tiled Diffusion] --mdtile-wrap-regions ignored: no axis of the canvas wraps around (--mdtile-wrap-x / --mdtile-wrap-y); the "
@@ -593,12 +637,22 @@ class AbstractDiffusion:
             self.weights.zero_()
 
         self.custom_bboxes = []
-        for s in bbox_settings.values():
+        for index, s in bbox_settings.items():
             enable, fx, fy, fw, fh, prompt, neg, blend_mode, feather_ratio, seed = s
+            if enable and index in masks:      # a painted mask: fx, fy, fw, fh are ignored, the rectangle is the mask's bounding box
+                made = self._mask_region(index + 1, masks[index][0], blend_mode, feather_ratio)
+                self._record_mask(index, masks[index][1] if made is not None else None)
+                if made is not None:
+                    x, y, w, h, cover, feather = made
+                    self.custom_bboxes.append(CustomBBox(x, y, w, h, prompt, neg, blend_mode, feather_ratio, seed, cover=cover, feather=feather))
+                    self.custom_bboxes[-1].index = index
+                continue
             if not enable or fx > 1.0 or fy > 1.0 or fw <= 0.0 or fh <= 0.0:
                 continue
             x, y, w, h = region_rect(fx, fy, fw, fh, self.w, self.h, wrap_regions and self.wrap_x, wrap_regions and self.wrap_y)
             self.custom_bboxes.append(CustomBBox(x, y, w, h, prompt, neg, blend_mode, feather_ratio, seed))
+            self.custom_bboxes[-1].index = index      # the region's key in bbox_settings: the noise hijack finds its rectangle and cover by it
+        self.mask_regions = any(b.cover is not None for b in self.custom_bboxes)
         if not self.custom_bboxes:
             self.enable_custom_bbox = False
             self.wrap_regions = False
@@ -617,7 +671,10 @@ class AbstractDiffusion:
         # evaluations still happen in such a job (Noise Inversion's own, the hires pass of another size), so self.weights and the premultiplied
         # region weights are kept as they are and region_w is built beside them
         if self.jitter_regions_requested() and not self._jitter_regions_alone():
-            if not draw_background:
+            if self.mask_regions:
+                if self.grid_jitter:
+                    self._jitter_note(self.MASK_REGIONS_FIXED_GRID)
+            elif not draw_background:
                 self._jitter_note(self.NO_BACKGROUND_TO_MOVE)
             elif self.grid_jitter:
                 self.jitter_regions = True
@@ -649,7 +706,7 @@ class AbstractDiffusion:
         specs = []
         for bbox, out, wgt in zip(self.custom_bboxes, outs, self.region_weights(raw)):
             mode = mdtile.REGION_FG if bbox.blend_mode == BlendMode.FOREGROUND else mdtile.REGION_BG
-            specs.append(mdtile.RegionSpec(bbox.x, bbox.y, bbox.w, bbox.h, mode, out, wgt))
+            specs.append(mdtile.RegionSpec(bbox.x, bbox.y, bbox.w, bbox.h, mode, out, wgt, cover=bbox.cover))
         return specs
 
     def gather_region(self, x_in: Tensor, bbox: CustomBBox) -> Tensor:
@@ -660,7 +717,8 @@ class AbstractDiffusion:
 
     def add_region_weight(self, bbox: CustomBBox, rect_w: Optional[Tensor]):
         """A background region's weight (rect_w None: 1.0) into the weight sum: self.weights, or with --mdtile-wrap-regions the canvas map region_w;
-        with --mdtile-jitter-regions both -- self.weights for the fixed-grid evaluations, region_w for the lattice blend."""
+        with --mdtile-jitter-regions both -- self.weights for the fixed-grid evaluations, region_w for the lattice blend.
+        A mask region counts where it covers: the caller hands its cover as 0.0 / 1.0 floats (MultiDiffusion) or its Gaussian times the cover."""
         if self.wrap_regions:
             mdtile.weight_map_add_rect_wrap(self.region_w, bbox.x, bbox.y, bbox.w, bbox.h, rect_w, 1.0, wrap_x=self.wrap_x, wrap_y=self.wrap_y)
         else:

@@ -54,6 +54,11 @@ class MixtureOfDiffusers(AbstractDiffusion):
         for bbox in self.custom_bboxes:
             if bbox.blend_mode == BlendMode.BACKGROUND:
                 cw = self.get_weight(bbox.w, bbox.h)
+                if bbox.cover is not None:
+                    # a mask region counts where it covers: Gaussian * cover (exact: * 0.0 or * 1.0).  init_done multiplies it by the reciprocal map,
+                    # which may be inf under a pixel nobody paints: 0 * inf = NaN there -- at a pixel the region does not cover, which the masked
+                    # blend never reads
+                    cw = cw * bbox.cover.to(torch.float32)
                 self.add_region_weight(bbox, cw)
                 self.custom_weights.append(cw.unsqueeze(0).unsqueeze(0))
                 self.raw_custom_weights.append(cw.clone().unsqueeze(0).unsqueeze(0) if self.jitter_regions else None)
@@ -172,6 +177,11 @@ class MixtureOfDiffusers(AbstractDiffusion):
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MOD, tile_outs, N, C, sx=sx, sy=sy, tile_w=self.get_tile_weights(),
                                                rescale=self.rescale_factor)
+            return self.x_buffer
+        if self.mask_regions:     # a region enters a pixel only where its mask covers it; every other region is its whole rectangle
+            self.x_buffer = mdtile.blend_mask_regions(self.blend_plan(), mdtile.METHOD_MOD, tile_outs, N, C,
+                                                      tile_w=self.get_tile_weights() if tile_outs else None, rescale=self.rescale_factor,
+                                                      regions=self.region_specs(region_outs), dtype=x_in.dtype, device=x_in.device)
             return self.x_buffer
         # K4 + K6 + K7 in one launch; pixels nobody paints stay 0, as upstream
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MOD, tile_outs, N, C, tile_w=self.get_tile_weights() if tile_outs else None,

@@ -42,8 +42,8 @@ class MultiDiffusion(AbstractDiffusion):
     def init_custom_bbox(self, *args):
         super().init_custom_bbox(*args)
         for bbox in self.custom_bboxes:  # a background region counts as one more uniform-weight layer
-            if bbox.blend_mode == BlendMode.BACKGROUND:
-                self.add_region_weight(bbox, None)
+            if bbox.blend_mode == BlendMode.BACKGROUND:   # a mask region counts where it covers: its cover as 0.0 / 1.0
+                self.add_region_weight(bbox, None if bbox.cover is None else bbox.cover.to(torch.float32))
 
     @torch.no_grad()
     def kdiff_forward(self, x_in: Tensor, sigma_in: Tensor, cond) -> Tensor:
@@ -186,6 +186,10 @@ class MultiDiffusion(AbstractDiffusion):
             return self.x_buffer
         if self.grid_shift:       # the blend of the plan, stored (sy, sx) further on the circle
             self.x_buffer = mdtile.blend_shift(plan, mdtile.METHOD_MD, tile_outs, N, C, sx=sx, sy=sy, weights=self.weights)
+            return self.x_buffer
+        if self.mask_regions:     # a region enters a pixel only where its mask covers it; every other region is its whole rectangle
+            self.x_buffer = mdtile.blend_mask_regions(self.blend_plan(), mdtile.METHOD_MD, tile_outs, N, C, weights=self.weights,
+                                                      regions=self.region_specs(region_outs), dtype=x_in.dtype, device=x_in.device)
             return self.x_buffer
         # K3 + K5 + K6 + K7 in one launch
         self.x_buffer = mdtile.blend(self.blend_plan(), mdtile.METHOD_MD, tile_outs, N, C, weights=self.weights,

@@ -15,6 +15,7 @@ Prompt / cond helpers stay thin host-side Python (they only forward to `modules.
 from __future__ import annotations
 
 import math
+import os
 from collections import namedtuple
 from enum import Enum
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -108,19 +109,57 @@ def region_rect(fx: float, fy: float, fw: float, fh: float, W: int, H: int, wrap
 
 
 class CustomBBox(BBox):
-    """Region-prompt rectangle.  Foreground regions carry their feather mask (built on the GPU by the engine)."""
+    """Region-prompt rectangle.  Foreground regions carry their feather mask (built on the GPU by the engine).
+    cover: a mask region's coverage, dense uint8 [h, w] on the device (the rectangle is the mask's bounding box), with its feather from
+    mdtile.mask_region for a foreground region; None: the region is its whole rectangle."""
 
     def __init__(self, x: int, y: int, w: int, h: int, prompt: str, neg_prompt: str, blend_mode: str,
-                 feather_radio: float, seed: int):
+                 feather_radio: float, seed: int, cover: Optional[Tensor] = None, feather: Optional[Tensor] = None):
         super().__init__(x, y, w, h)
         self.prompt, self.neg_prompt = prompt, neg_prompt
         self.blend_mode = BlendMode(blend_mode)
         self.feather_ratio = max(min(feather_radio, 1.0), 0.0)
         self.seed = seed
-        self.feather_mask = feather_mask(w, h, self.feather_ratio) if self.blend_mode == BlendMode.FOREGROUND else None
+        self.cover = cover
+        self.index: Optional[int] = None      # the region's key in the job's bbox_settings (init_custom_bbox sets it)
+        if self.blend_mode != BlendMode.FOREGROUND:
+            self.feather_mask = None
+        else:
+            self.feather_mask = feather if cover is not None else feather_mask(w, h, self.feather_ratio)
         self.cond = None
         self.extra_network_data = None
         self.uncond = None
+
+
+def region_mask_sources(p, indices) -> Dict[int, Tuple[Any, str]]:
+    """{region index (0-based): (a PIL image or a file path, the name recorded in the generation parameters)} of the regions that are painted
+    masks: p.mdtile_region_masks = {k: PIL image or path} with k the 1-based region number, else DIR/region<k>.png of --mdtile-region-masks DIR.
+    The attribute wins over the directory."""
+    given = getattr(p, "mdtile_region_masks", None) or {}
+    folder = getattr(shared.cmd_opts, "mdtile_region_masks", None)
+    out: Dict[int, Tuple[Any, str]] = {}
+    for i in indices:
+        k = i + 1
+        src = given.get(k, given.get(str(k)))
+        if src is not None:
+            out[i] = (src, os.path.basename(src) if isinstance(src, (str, os.PathLike)) else "<image>")
+        elif folder:
+            path = os.path.join(folder, f"region{k}.png")
+            if os.path.isfile(path):
+                out[i] = (path, os.path.basename(path))
+    return out
+
+
+def load_region_mask(src) -> Tensor:
+    """A region's painted mask as uint8 [Hm, Wm] on the device: the image (or the file, read with Pillow) converted to "L"."""
+    import numpy as np
+    from PIL import Image
+    if isinstance(src, (str, os.PathLike)):
+        with Image.open(src) as img:
+            a = np.array(img.convert("L"), dtype=np.uint8)
+    else:
+        a = np.array(src.convert("L"), dtype=np.uint8)
+    return torch.from_numpy(a).to(devices.device)
 
 
 class Prompt:

@@ -774,7 +774,7 @@ int mdtile_conv2d_gn_stats(const float* d_x, const float* d_coef, const float* d
  *   MDTILE_CONV_REC_X_F16                      mdtile_conv2d_rec(_stats): d_x_rec is the fp16 form AND d_w_packed is the plane of mdtile_conv_pack_f16
  *   MDTILE_CONV_REC_Y_F16                      mdtile_conv2d_rec / mdtile_upconv2d_rec_window: d_y_rec is to be the fp16 form
  * A tag that disagrees with what the mode writes (fp16 asked outside MDTILE_PRECISION_F16 or for a raw record; an activated record output in that
- * mode without _Y_F16; _X_F16 on an upsample conv) is MDTILE_E_ARG with "record format mismatch" in the error text -- never a reinterpretation. */
+ * mode without _Y_F16; _X_F16 on an upsample conv; _Y_F16 on a direct conv whose input record is a bf16 split) is MDTILE_E_ARG with "record format mismatch" in the error text -- never a reinterpretation. */
 #define MDTILE_REC_BF16X2 0
 #define MDTILE_REC_F16 1
 #define MDTILE_CONV_REC_X_F16 32

@@ -558,6 +558,10 @@ static int rec_call(RecConvCall& c, const char* who, int flags, const void* d_x_
     const int want = (d_y_rec && rec_writes_f16(d_y_coef)) ? 1 : 0;
     MDT_CHECK_ARG(y16 == want, "%s: record format mismatch: the call %s MDTILE_CONV_REC_Y_F16 but its record output is %s (mode %d, d_y_coef %s)", who,
                   y16 ? "sets" : "does not set", want ? "the fp16 form" : "a bf16 split or absent", mdtile_get_precision(), d_y_coef ? "given" : "NULL");
+    // the fp16 record-out epilogue exists in the fp16 direct kernels and in the sub-pixel kernels only: a direct conv on a bf16 split input would
+    // run a kernel that writes a bf16 split into an image the caller holds as the fp16 form
+    MDT_CHECK_ARG(!y16 || up || x16, "%s: record format mismatch: no direct kernel writes an activated fp16 record from a bf16 split input record "
+                  "(MDTILE_CONV_REC_Y_F16 without MDTILE_CONV_REC_X_F16, mode %d)", who, mdtile_get_precision());
     c.x_rec = d_x_rec; c.bias = d_bias; c.res = d_residual; c.y32 = d_y; c.y_rec = d_y_rec; c.y_coef = d_y_coef;
     c.w_rec = x16 ? d_w_packed : d_w_packed + f32_packed_floats(cout, cin, 3);      // (x16: d_w_packed IS the fp16 plane)
     c.B = B; c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.up = up;

@@ -11,7 +11,8 @@ orders agree, the wrong kernels above change bits.  Two operand classes: the lat
 from K, the precondition asserted on the actual tensors) and small integers (lo = 0: every mode must return the same bits).
 Shapes: the smallest that reach every block variant and a ragged edge (lattice_ref's case tables), not the workload's.
 A mismatch message gives the count of differing elements, the first index and the difference in units of the grain g.
-Out of scope by construction: the fp16 kernels (fp16 rounding leaves the lattice).  The fused GroupNorm + SiLU input, the activated record
+The fp16 kernels of MDTILE_PRECISION_F16 have a module of their own, tests/test_gpu_f16_exact.py: they form the whole product, lo*lo
+included, so there the fine bits go to one operand only and sub-ulp bits probe the conversion (tests/f16_exact_ref.py).  The fused GroupNorm + SiLU input, the activated record
 output and the statistics epilogues have a module of their own, tests/test_gpu_gn_exact.py: SiLU is the identity on a saturated set, and
 the statistics are exact on small integers.  The attention has a module of its own, tests/test_gpu_attn_exact.py: its softmax is exact where the live keys
 of a query tie and every other key lies 160 below in the log2 domain.  Every test leaves the default precision mode behind."""

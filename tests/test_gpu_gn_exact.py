@@ -10,8 +10,8 @@ and every assertion is torch.equal; a mismatch message gives the count of differ
 grains.  The only tolerance in the module is the derived 4 ulp bound of the unsaturated SiLU.  tests/test_gn_exact_host.py proves the
 instrument: the orders agree, every precondition holds for every case row, the wrong kernels a tolerance lets through change bits.
 The first two tests probe what the rest supposes about the hardware: rcp(1.0f) == 1.0f, and an exact sqrtf / division on powers of 4 / 2.
-Out of scope: MDTILE_PRECISION_F16 (fp16 rounding leaves the lattice) and mdtile vae_fast_input (its renormalisation divides by a standard
-deviation: no exact class).  Every test leaves the default precision mode behind."""
+MDTILE_PRECISION_F16 runs the same chain on fp16 operands: tests/test_gpu_f16_exact.py covers it on operand classes of its own
+(tests/f16_exact_ref.py).  Out of scope: mdtile vae_fast_input (its renormalisation divides by a standard deviation: no exact class).  Every test leaves the default precision mode behind."""
 import pytest
 import torch
 
